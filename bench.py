@@ -18,11 +18,16 @@ parameters are a few KB): each rank owns 32 signals, parameter gradients are all
 scaling.  The bin-sharded forms are timed beside it when more than one rank runs: "bin_sharded" in the
 JSON line (config 2 through two all-to-alls per direction; the config-5 structure through the all-gather).
 
-The one JSON line also carries (rank 0): `roofline` (dominant kernel) and `kernels` (every hot kernel's launch time,
-algorithmic bytes and fraction of the HBM peak), `step_roofline` (the unfused 1.057 GB/step count and the
-fused pipeline's own count against the step time), `input_grad` (the same step with the gradient of the input),
-`secondary` (BASELINE configs[2..4] on one GPU: bin-solves/s, solve TFLOP/s), `device` (what rocminfo / a copy probe say)
-and `cpu_baseline` (the oracle's torch-CPU graph on the host cores).
+A plain run sets up (capture, the device brought to its sustained state), runs the W warm-up steps, times the K steps and
+prints the headline line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and what was timed);
+`--dump-outputs DIR` writes the last timed step's loss and parameter gradients as DIR/<name>.npy.
+
+With --full the one JSON line also carries (rank 0): `ms_per_step_steady` / `ms_per_step_unsettled` (re-timings),
+`roofline` (dominant kernel) and `kernels` (every hot kernel's launch time, algorithmic bytes and fraction of the HBM peak),
+`step_roofline` (the unfused 1.057 GB/step count and the fused pipeline's own count against the step time),
+`input_grad` (the same step with the gradient of the input), `objectives`, `variants`, `secondary` (BASELINE configs[2..4]
+on one GPU: bin-solves/s, solve TFLOP/s), `device` (what rocminfo / a copy probe say), `cpu_baseline` (the oracle's
+torch-CPU graph on the host cores) and, with more than one rank, `bin_sharded`.
 """
 import os as _os_env
 _os_env.environ.setdefault("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "0")   # see flamo_amd/__init__.py: must precede HIP runtime init
@@ -515,6 +520,21 @@ def launch_plan(gpus, argv, env=None, port=None):
     return {"cmd": cmd, "ranks": ranks, "backend": "nccl (RCCL)", "env_common": {"HSA_ENABLE_IPC_MODE_LEGACY": env.get("HSA_ENABLE_IPC_MODE_LEGACY", "0")}}
 
 
+def dump_outputs(dirname, loss, grads):
+    """--dump-outputs: what the timed step handed its caller in its last iteration -- the loss and the gradient of every
+    learnable parameter (name -> tensor) -- as DIR/loss.npy and DIR/grad_<name>.npy, float32 or float64 as the run's
+    dtype (a few KB in all).  The inputs are fixed (tests/golden/bench_params.npz, seeded input draw), so two builds run with
+    the same arguments can be compared array for array."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"loss": loss, **{f"grad_{k}": g for k, g in grads.items()}}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"bench.py --dump-outputs: {name} is {a.dtype}, not float32 / float64")
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -528,7 +548,17 @@ def main():
     ap.add_argument("--no-graph", action="store_true",
                     help="time eager steps instead of replaying the step from a HIP graph")
     ap.add_argument("--dtype", default="f32", choices=["f32", "f64"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the unsettled and steady re-timings, the dominant "
+                         "kernel's device-clock stamps, the roofline / per-kernel legs, the bin-sharded legs (ranks > 1), the "
+                         "input-gradient, objective, variant, secondary-workload and device legs and the CPU baselines (the "
+                         "--no-* options above drop single legs of such a run)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one handed its caller -- the loss and every parameter "
+                         "gradient (summed over ranks) -- as DIR/<name>.npy in the run's precision")
     args = ap.parse_args()
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
     warnings.simplefilter("ignore")
 
     # ---- one rank per GPU.  Under a launcher (torch.distributed.run sets WORLD_SIZE) this process IS a rank; started bare with
@@ -614,8 +644,9 @@ def main():
         from flamo_amd.graph import GraphedStep
         from flamo_amd import _lib as _fl
         # the dominant kernel's launches INSIDE the replayed graph stamp the device's constant-rate clock per workgroup (two
-        # 8-byte stores each): its duration in the timed region itself, where HIP events cannot be recorded (roofline leg below)
-        if rank == 0 and dtype == torch.float32 and ops._walk_applies(NFFT, BATCH, NCH, NCH):
+        # 8-byte stores each): its duration in the timed region itself, where HIP events cannot be recorded (roofline leg below;
+        # --full only)
+        if args.full and rank == 0 and dtype == torch.float32 and ops._walk_applies(NFFT, BATCH, NCH, NCH):
             walk_stamps = torch.zeros(2 * 1024 + 1, dtype=torch.int64, device=dev)
             walk_wgs_n = _fl.lib().fl_spec_walk_workgroups(NFFT, BATCH)
             _fl.lib().fl_debug_set_walk_stamps(walk_stamps.data_ptr())
@@ -656,36 +687,45 @@ def main():
     # (no collective: every rank does this on its own) is repeated in blocks of ten until two consecutive blocks agree
     # within 1 %, at most 300 times (0.12 s); eager steps additionally include allocator growth and first-launch costs.
     local_step = (lambda: gs.replay()) if gs is not None else (lambda: eager_step(False))
-    # the figure measured the way rounds 1-2 measured it (three replays + W warm-ups behind the capture, then K timed): kept in
-    # the line so that rounds stay comparable -- `value` is taken after the device has settled
-    for _ in range(3 + args.warmup):
-        local_step()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        local_step()
-    torch.cuda.synchronize()
-    ms_unsettled = (time.perf_counter() - t0) / args.steps * 1e3
+    ms_unsettled = None
+    if args.full:
+        # the figure measured the way rounds 1-2 measured it (three replays + W warm-ups behind the capture, then K timed): kept
+        # in the --full line so that rounds stay comparable -- `value` is taken after the device has settled
+        for _ in range(3 + args.warmup):
+            local_step()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            local_step()
+        torch.cuda.synchronize()
+        ms_unsettled = (time.perf_counter() - t0) / args.steps * 1e3
     settle = settle_device(local_step)
     for _ in range(args.warmup):
         step()
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        loss = step()
+    reduced = getattr(pending[-1], "reduced", None) if pending else None     # collective path: the sums stay in its buffer
     fence()
     elapsed = time.perf_counter() - t0
-    # the same step over >= 50 more iterations (SURVEY 8-d1's count), every rank: box-to-box and run-to-run noise of a timed
-    # region of K x 0.4 ms shows as the difference between the two
-    n_steady = max(50, args.steps)
-    t0 = time.perf_counter()
-    for _ in range(n_steady):
-        step()
-    fence()
-    elapsed_steady = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        grads = reduced if reduced is not None else [p.grad for p in params]
+        dump_outputs(args.dump_outputs, loss, dict(zip(("mix", "eq"), grads)))
+    n_steady, elapsed_steady = None, None
+    if args.full:
+        # the same step over >= 50 more iterations (SURVEY 8-d1's count), every rank: box-to-box and run-to-run noise of a timed
+        # region of K x 0.4 ms shows as the difference between the two
+        n_steady = max(50, args.steps)
+        t0 = time.perf_counter()
+        for _ in range(n_steady):
+            step()
+        fence()
+        elapsed_steady = time.perf_counter() - t0
     # the dominant kernel's launch duration inside the replayed step, from the stamps its workgroups leave: max(end) - min(start)
     # of the launch of each of 30 more replays of the SAME graph (a synchronisation and a 4 KB read-back behind each; the kernel
-    # itself runs behind its real predecessor inside the graph, exactly as in the timed replays)
+    # itself runs behind its real predecessor inside the graph, exactly as in the timed replays); --full only (the stamps are
+    # only set then)
     walk_clock = None
     if gs is not None and walk_stamps is not None:
         khz = _fl.lib().fl_wall_clock_khz()
@@ -703,16 +743,18 @@ def main():
                       "active_ms": sum(active) / len(active), "launches": len(durs), "clock_khz": khz}
     ranks_seen = 1
     if dist_on:                     # max over ranks; before rank 0 goes on alone into the roofline leg
-        t = torch.tensor([elapsed, elapsed_steady], device=ctl, dtype=torch.float64)
+        t = torch.tensor([elapsed, elapsed_steady or 0.0], device=ctl, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, elapsed_steady = t.tolist()
+        elapsed, steady_max = t.tolist()
+        if elapsed_steady is not None:
+            elapsed_steady = steady_max
         ones = torch.ones(1, device=ctl)
         dist.all_reduce(ones)       # how many ranks RCCL actually carried
         ranks_seen = int(ones.item())
 
     # ---- bin-sharded forms: every rank takes part (collectives), before rank 0 goes on alone
     sharded = None
-    if dist_on and not args.no_bin_sharded and dtype == torch.float32:
+    if args.full and dist_on and not args.no_bin_sharded and dtype == torch.float32:
         try:
             sharded = bin_sharded(dev, model, params, x, args.steps)
         except Exception as e:      # noqa: BLE001 -- the headline line must survive a failure of a side leg
@@ -726,8 +768,8 @@ def main():
     products_per_step = 2 * BATCH * M * NCH * NCH * world   # two per-bin MIMO modules (Matrix, GEQ)
     ms = elapsed / args.steps * 1e3
     out = None
-    if rank == 0:
-        # ---- roofline leg: HIP events cannot be read back from inside a captured graph, so every hot kernel's launch
+    if rank == 0 and args.full:
+        # ---- roofline leg (--full): HIP events cannot be read back from inside a captured graph, so every hot kernel's launch
         # time is taken with events on the launch stream in eager steps of the same workload, run by this same command
         # right after the timed replays, each timed launch queued behind ~0.2 ms of streaming copies so that it starts
         # from a busy queue (an event recorded on an idle stream is stamped at once and would add the host's launch
@@ -854,6 +896,19 @@ def main():
                 roof["replayed_frac_rocprofv3"] = alg[key] / (prof_us * 1e-6) / 1e9 / HBM_PEAK_GBS
         unfused_bytes = (2 * sig + hb) + (3 * sig + 2 * hb) + (2 * sig) + (3 * sig)      # GEQ fwd/bwd + Matrix fwd/bwd
         fused_bytes = sum(alg.get(k, 0) * v["launches_per_step"] for k, v in kernels.items())
+        legs = {"ms_per_step_steady": {"ms_per_step": elapsed_steady / n_steady * 1e3, "steps": n_steady,
+                                       "what": "the same step over this many more iterations right after the timed region"},
+                "ms_per_step_unsettled": {"ms_per_step": ms_unsettled, "what": "rounds 1-2's method: 3 replays + W warm-ups right "
+                                          "behind the capture, then K timed (inside the device's clock ramp); local step, rank 0"},
+                "roofline": roof,
+                "step_roofline": {"unfused_bytes_per_step": unfused_bytes, "unfused_floor_ms": unfused_bytes / (HBM_PEAK_GBS * 1e9) * 1e3,
+                                  "frac_of_unfused_floor": unfused_bytes / (HBM_PEAK_GBS * 1e9) * 1e3 / ms,
+                                  "pipeline_bytes_per_step": fused_bytes, "pipeline_floor_ms": fused_bytes / (HBM_PEAK_GBS * 1e9) * 1e3,
+                                  "frac_of_pipeline_floor": fused_bytes / (HBM_PEAK_GBS * 1e9) * 1e3 / ms,
+                                  "note": "unfused = the einsum passes of SURVEY 8-d3 alone (1.057 GB); pipeline = every streaming "
+                                          "pass of the step as built (transforms, product, objective, gradients)"},
+                "kernels": kernels}
+    if rank == 0:
         out = {"metric": "freq-bin*channel products/sec (fwd+bwd), nfft=96000 8x8ch", "value": products_per_step / (ms * 1e-3),
                "unit": "products/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -864,27 +919,17 @@ def main():
                                                "two consecutive blocks agree within 0.5 % (the device's clock ramp: the first ~100 "
                                                "replays run up to 10-18 % slower); then the W warm-up steps, then the K timed steps",
                                        **settle},
-               "ms_per_step_steady": {"ms_per_step": elapsed_steady / n_steady * 1e3, "steps": n_steady,
-                                      "what": "the same step over this many more iterations right after the timed region"},
-               "ms_per_step_unsettled": {"ms_per_step": ms_unsettled, "what": "rounds 1-2's method: 3 replays + W warm-ups right "
-                                         "behind the capture, then K timed (inside the device's clock ramp); local step, rank 0"},
                "rccl_ranks_seen": ranks_seen if dist_on else None,
                "collective_backend": ("nccl (RCCL)" if backend == "nccl" else f"{backend} (test rig, host-staged)") if dist_on else None,
                "config": {"workload": "BASELINE configs[1]: Shell(FFT -> Series(Matrix 8x8, GEQ 8x8) -> iFFT), nfft=96000, "
                                       "batch 32 per GPU, fwd+bwd of (y**2).mean(), parameter grads",
                           "nfft": NFFT, "channels": NCH, "batch_per_gpu": BATCH, "parallelism": f"dp{world} (batch)",
-                          "input_grad": False},
-               "roofline": roof,
-               "step_roofline": {"unfused_bytes_per_step": unfused_bytes, "unfused_floor_ms": unfused_bytes / (HBM_PEAK_GBS * 1e9) * 1e3,
-                                 "frac_of_unfused_floor": unfused_bytes / (HBM_PEAK_GBS * 1e9) * 1e3 / ms,
-                                 "pipeline_bytes_per_step": fused_bytes, "pipeline_floor_ms": fused_bytes / (HBM_PEAK_GBS * 1e9) * 1e3,
-                                 "frac_of_pipeline_floor": fused_bytes / (HBM_PEAK_GBS * 1e9) * 1e3 / ms,
-                                 "note": "unfused = the einsum passes of SURVEY 8-d3 alone (1.057 GB); pipeline = every streaming "
-                                         "pass of the step as built (transforms, product, objective, gradients)"},
-               "kernels": kernels}
+                          "input_grad": False}}
+        if args.full:
+            out.update(legs)
         if sharded is not None:
             out["bin_sharded"] = sharded
-        if not args.no_extras and dtype == torch.float32:
+        if args.full and not args.no_extras and dtype == torch.float32:
             try:
                 out["input_grad"] = input_grad_leg(model, params, x, args.steps, products_per_step // world)
                 # SURVEY 8-d1 counts the input's gradient too: the d1-conforming figure at top level, beside `value`
@@ -914,7 +959,7 @@ def main():
                 out["secondary"] = {"error": f"{type(e).__name__}: {e}"[:300]}
             out["device"] = device_info(dev)
         out["params"] = "tests/golden/bench_params.npz (reference constructors, seed 130709)" if fixture_params() else "seeded draws (fixture missing)"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(params[0], params[1])
             if isinstance(out.get("secondary"), dict) and "error" not in out["secondary"]:
                 try:        # configs[2] at full size and the configs[4] structure at 1/10 length, same thread count

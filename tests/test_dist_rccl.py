@@ -174,7 +174,7 @@ def test_bench_line_over_rccl(world):
     the weak-scaling (batch) figure as `value` and the strong-scaling bin-sharded figures beside it."""
     _need(world)
     out = _torchrun(world, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1",
-                    "--no-cpu-baseline", timeout=1200).stdout
+                    "--full", "--no-cpu-baseline", timeout=1200).stdout
     lines = [ln for ln in out.splitlines() if ln.strip().startswith("{")]
     assert len(lines) == 1
     d = json.loads(lines[0])
@@ -193,8 +193,8 @@ def test_bench_line_two_ranks_on_one_device():
     bench.py's test-rig hooks): the multi-rank branch of bench.py -- gradient all-reduce after every replay, max over ranks,
     the bin-sharded legs -- executed end to end on a one-GPU box.  The figures of such a line mean nothing (shared device)."""
     _need(1)
-    out = _torchrun(2, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-                    timeout=900, env={"BENCH_ALLOW_SHARED_GPU": "1", "BENCH_BACKEND": "gloo"}).stdout
+    out = _torchrun(2, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
+                    "--no-cpu-baseline", timeout=900, env={"BENCH_ALLOW_SHARED_GPU": "1", "BENCH_BACKEND": "gloo"}).stdout
     lines = [ln for ln in out.splitlines() if ln.strip().startswith("{")]
     assert len(lines) == 1
     d = json.loads(lines[0])

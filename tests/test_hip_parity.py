@@ -734,7 +734,7 @@ def test_bench_contract_line(gpu):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                          "--no-cpu-baseline"], check=True, timeout=600, cwd=root, capture_output=True, text=True).stdout
+                          "--full", "--no-cpu-baseline"], check=True, timeout=600, cwd=root, capture_output=True, text=True).stdout
     lines = [ln for ln in out.splitlines() if ln.strip()]
     assert len(lines) == 1
     d = json.loads(lines[0])
@@ -769,3 +769,42 @@ def test_bench_contract_line(gpu):
         assert sec[k]["ms_per_step"] > 0 and sec[k]["bin_solves_per_s"] > 0, k
     assert 0 < sec["config3_fdn16_batch1"]["solve"]["frac_fp32_vector_peak"] < 1
     assert d["device"]["hbm_copy_probe_GBs"] > 1000
+
+
+def test_bench_plain_line_and_dumped_outputs(gpu, tmp_path):
+    """bench.py without --full: the headline line alone (no side legs), and --dump-outputs writes the last timed step's loss
+    and parameter gradients -- the same values an eager step of the same workload on the same inputs computes."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+    from conftest import relerr
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
+                          "--dump-outputs", str(tmp_path)], check=True, timeout=600, cwd=root, capture_output=True, text=True).stdout
+    lines = [ln for ln in out.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 4 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["unit"] == "products/s" and d["dtype"] == "f32"
+    M = 96000 // 2 + 1
+    assert abs(d["value"] - 2 * 32 * M * 8 * 8 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-9
+    for k in ("roofline", "kernels", "step_roofline", "ms_per_step_steady", "input_grad", "secondary", "device", "cpu_baseline"):
+        assert k not in d, k
+    dumped = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert sorted(dumped) == ["grad_eq", "grad_mix", "loss"]
+    assert all(a.dtype == np.float32 for a in dumped.values())
+    sys.path.insert(0, root)
+    import bench
+    from flamo_amd import ops
+    torch.manual_seed(130709)
+    model, params = bench.build_model(gpu, torch.float32)
+    torch.manual_seed(130709 + 1)
+    x = torch.randn(bench.BATCH, bench.NFFT, bench.NCH, device=gpu)
+    loss = ops.mean_square(model(x))
+    loss.backward()
+    assert relerr(torch.from_numpy(dumped["loss"]), loss.detach().cpu()) < 1e-5
+    for name, p in zip(("grad_mix", "grad_eq"), params):
+        assert dumped[name].shape == tuple(p.shape)
+        assert relerr(torch.from_numpy(dumped[name]), p.grad.cpu()) < 1e-5, name
