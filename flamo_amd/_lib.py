@@ -232,6 +232,7 @@ def build(force: bool = False) -> str:
 
 # A launch pair is open on this thread (ops.paired_launch): a recorded response launch must go out before ANY other library
 # call than the column pass that carries it -- every call site fetches the handle through lib(), which is where that is enforced.
+# _pair.stream_of / _pair.issued: ops' hooks (the current stream; drop the references that kept the record's buffers alive).
 _pair = threading.local()
 
 
@@ -242,6 +243,7 @@ def lib(pair_ok: bool = False) -> C.CDLL:
     if not pair_ok and getattr(_pair, "stream_of", None) is not None and _lib is not None and _lib.fl_launch_pair_pending():
         rc = _lib.fl_launch_pair_flush(_pair.stream_of())
         _lib.fl_launch_pair_begin()
+        _pair.issued()
         if rc != 0:
             raise RuntimeError(f"libflamo_hip launch pair flush failed (code {rc}): " + _lib.fl_last_error().decode("utf-8", "replace"))
     if _lib is None:

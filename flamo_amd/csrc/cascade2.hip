@@ -616,6 +616,11 @@ int rc_ba_launch(const void* b, const void* a, int S, int No, int Nmid, int Ni, 
     p.args = RcBaArgs{(const double*)b, (const double*)a, S, No * Nmid, Nmid, (const float*)Wr, gamma, (const cx<double>*)Wd, nfft, bin0,
                       m_local, (cx<float>*)G, g_pitch, (cx<float>*)H, h_pitch, gd, stream_policy()};
     if (pair_mode()) {        // recorded: the next forward column pass carries it (fusedfwd.h)
+        PendingRc old;
+        if (pending_rc_take(old)) {      // one slot: a launch recorded before this one goes out first, on this call's stream
+            const int r = rc_ba_launch_now(old, (hipStream_t)stream);
+            if (r) return r;
+        }
         pending_rc_put(p);
         return FL_OK;
     }

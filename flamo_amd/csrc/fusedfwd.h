@@ -6,7 +6,10 @@
 // Host protocol ("launch pair"): between fl_launch_pair_begin() and fl_launch_pair_flush() on a thread, rc_ba_launch
 // (cascade2.hip) RECORDS its launch instead of issuing it; the next forward column pass (spectral.hip: cols_launch) issues both
 // as one grid when it has the shape for it, otherwise the recorded launch goes out first, alone.  flush issues whatever is
-// still recorded.  The caller guarantees that nothing reads the response between the two (flamo_amd/ops.py: paired_launch).
+// still recorded.  The caller guarantees that nothing reads the response between the two (flamo_amd/ops.py: paired_launch)
+// and keeps every buffer the record points at alive until it is issued (ops._cascade_rc_forward).  There is ONE slot: a second
+// rc_ba_launch in pair mode issues the recorded one first, and fl_launch_pair_begin with a launch recorded fails (FL_ERR_BAD_ARG)
+// and leaves it recorded -- a record is never dropped.
 #pragma once
 #include "rc_ba_body.h"
 

@@ -98,8 +98,11 @@ using namespace fl;
 extern "C" {
 
 int fl_launch_pair_begin(void) {
+    if (t_have) {      // a recorded launch would be lost: the caller flushes it first
+        set_error("launch pair: begin while a recorded response launch is pending (flush it first)");
+        return FL_ERR_BAD_ARG;
+    }
     t_pair_mode = true;
-    t_have = false;
     return FL_OK;
 }
 

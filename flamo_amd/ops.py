@@ -797,7 +797,8 @@ class paired_launch:
     pass in the same grid (csrc/fusedfwd.h): the response's packed arithmetic runs beside the column pass's HBM traffic instead of
     in front of it.  Any other library call in between issues the recorded launch first (flamo_amd/_lib.py: lib()), exit issues
     one that is still recorded; torch operations that READ the response in between must be preceded by ``flush()`` -- the
-    only user, Shell's fused forward (processor/system.py), does that."""
+    only user, Shell's fused forward (processor/system.py), does that.  The buffers the record points at are kept alive until it
+    is issued (_cascade_rc_forward), also where no autograd graph holds them (no_grad, inference_mode)."""
 
     def __init__(self, enabled: bool = True):
         self.enabled = bool(enabled and LAUNCH_PAIRS)
@@ -807,22 +808,73 @@ class paired_launch:
             if getattr(_lib._pair, "stream_of", None) is not None:      # nested: the outer region owns the mode
                 self.enabled = False
             else:
-                _lib.lib().fl_launch_pair_begin()
+                _lib.check(_lib.lib().fl_launch_pair_begin(), "launch pair begin")
                 _lib._pair.stream_of = _stream
+                _lib._pair.issued = _pair_issued
         return self
 
     def flush(self):
-        if self.enabled and getattr(_lib._pair, "stream_of", None) is not None:
-            L = _lib.lib(pair_ok=True)
-            if L.fl_launch_pair_pending():
-                _lib.check(L.fl_launch_pair_flush(_stream()), "launch pair flush")
-                L.fl_launch_pair_begin()
+        if self.enabled:
+            flush_launch_pair()
 
     def __exit__(self, *exc):
         if self.enabled:
             _lib._pair.stream_of = None
-            _lib.check(_lib.lib().fl_launch_pair_flush(_stream()), "launch pair flush")
+            try:
+                _lib.check(_lib.lib().fl_launch_pair_flush(_stream()), "launch pair flush")
+            except Exception as e:
+                if exc[0] is None:
+                    raise
+                raise exc[1] from e        # the body's exception stays the one raised; the flush's failure is its cause
+            finally:
+                _pair_issued()
         return False
+
+
+def flush_launch_pair():
+    """Issue a response launch recorded in the open launch pair now, on the current stream, and stay in the pair's mode
+    (no-op outside one, or with nothing recorded)."""
+    if getattr(_lib._pair, "stream_of", None) is None:
+        return
+    L = _lib.lib(pair_ok=True)
+    if L.fl_launch_pair_pending():
+        rc = L.fl_launch_pair_flush(_stream())
+        L.fl_launch_pair_begin()
+        _pair_issued()
+        _lib.check(rc, "launch pair flush")
+
+
+def _pair_keep(tensors):
+    """The launch just made was recorded (paired_launch): hold every tensor whose pointer the record holds until it is issued.
+    Without an autograd graph (no_grad, inference_mode) nothing else does, and the caching allocator would hand their blocks to
+    the next allocation -- the deferred kernel would then read (b, a, Wr, ...) or write (G, H, and the designed b, a) memory
+    that someone else owns."""
+    keep = getattr(_lib._pair, "keep", None)
+    if keep is None:
+        keep = _lib._pair.keep = []
+    keep.append((_stream(), tensors))
+
+
+def _pair_issued():
+    """The recorded launch went out on the current stream: drop _pair_keep's references.  Blocks of a record made on ANOTHER
+    stream (the side stream of Shell's response region) return to that stream's pool, where a later side region of the same
+    forward pass could be handed them while the main-stream kernel still runs: they live as long as the forward's memo, as the
+    response itself does (processor/system.py: _run_response) -- outside a forward pass, record_stream marks them."""
+    keep = getattr(_lib._pair, "keep", None)
+    if not keep:
+        return
+    _lib._pair.keep = None
+    cur = _stream()
+    for st, ts in keep:
+        if st == cur:
+            continue
+        memo = forward_memo()
+        if memo is not None:
+            memo.setdefault("_keep_alive", []).extend(ts)
+        else:
+            s = torch.cuda.current_stream()
+            for t in ts:
+                t.record_stream(s)
 
 
 def _spec_cols_fwd(x, nfft, env_log2, site=0):
@@ -842,6 +894,8 @@ def _spec_cols_fwd(x, nfft, env_log2, site=0):
     finally:
         if site:
             L.fl_set_stream_policy(0xFFFFFFFF, 0)
+        elif getattr(_lib._pair, "keep", None):
+            _pair_issued()      # this launch carried the recorded one
     return S
 
 
@@ -1056,8 +1110,10 @@ class _SpectralApply(torch.autograd.Function):
         ctx.cfg = (nfft, scale_f, env_f, scale_i, env_i, T, NI, NO, walk)
         ctx.speculated = key if Sg is not None else None
         # what an objective computed from y alone can reuse (mean_square): the partial sums the inverse pass left behind, and
-        # everything the backward pass needs -- see _SpectralMeanSquare
-        y._flamo_sa = _SpectralTag(x, Hrm, Hp, Xs, ctx.cfg, parts, y._version, Sg, key)
+        # everything the backward pass needs -- see _SpectralMeanSquare (not on an inference tensor: it has no version counter,
+        # and nothing differentiates it)
+        if not y.is_inference():
+            y._flamo_sa = _SpectralTag(x, Hrm, Hp, Xs, ctx.cfg, parts, y._version, Sg, key)
         return y
 
     @staticmethod
@@ -2312,30 +2368,34 @@ def _cascade_rc_forward(b, a, Wr, gamma, nfft, real, float_eval, geq=None):
     G = _empty_rows((No, Nmid), m_local, _cdtype(real), dev)
     H = _empty_rows((No, Ni), m_local, _cdtype(real), dev)
     Wc = Wr.contiguous()
+    Wd = twiddles(nfft, torch.float64, dev)
     P = _pitch(m_local)
     with kernel_timer.span("sos_response_rc"):
         if f64 and geq is not None:
             xc, kind, consts = geq
             _lib.check(_lib.lib().fl_geq_response_rc_c128(xc.data_ptr(), kind, S, consts.data_ptr(), b.data_ptr(), a.data_ptr(), No, Nmid, Ni,
-                                                          Wc.data_ptr(), float(gamma), twiddles(nfft, torch.float64, dev).data_ptr(), nfft,
+                                                          Wc.data_ptr(), float(gamma), Wd.data_ptr(), nfft,
                                                           bin0, m_local, G.data_ptr(), P, H.data_ptr(), P, _stream()), "geq_response_rc")
         elif f64:
             _lib.check(_lib.lib().fl_sos_response_rc_c128(b.data_ptr(), a.data_ptr(), S, No, Nmid, Ni, Wc.data_ptr(), float(gamma),
-                                                          twiddles(nfft, torch.float64, dev).data_ptr(), nfft, bin0, m_local,
+                                                          Wd.data_ptr(), nfft, bin0, m_local,
                                                           G.data_ptr(), P, H.data_ptr(), P, _stream()), "sos_response_rc")
         elif geq is not None:
             xc, kind, consts = geq
             _lib.check(_lib.lib().fl_geq_response_rc_c64(xc.data_ptr(), kind, S, consts.data_ptr(), b.data_ptr(), a.data_ptr(), No, Nmid, Ni,
-                                                         Wc.data_ptr(), float(gamma), twiddles(nfft, torch.float64, dev).data_ptr(), nfft,
+                                                         Wc.data_ptr(), float(gamma), Wd.data_ptr(), nfft,
                                                          bin0, m_local, G.data_ptr(), P, H.data_ptr(), P,
                                                          int(bool(float_eval and FLOAT_CASCADE_EVAL)), _stream()), "geq_response_rc")
         else:
             _lib.check(_lib.lib().fl_sos_response_rc_c64(b.data_ptr(), a.data_ptr(), S, No, Nmid, Ni, Wc.data_ptr(), float(gamma),
-                                                         twiddles(nfft, torch.float64, dev).data_ptr(), nfft, bin0, m_local,
+                                                         Wd.data_ptr(), nfft, bin0, m_local,
                                                          G.data_ptr(), P, H.data_ptr(), P, int(bool(float_eval and FLOAT_CASCADE_EVAL)),
                                                          _stream()), "sos_response_rc")
-    if kernel_timer.enabled and _lib.lib(pair_ok=True).fl_launch_pair_pending():
-        kernel_timer.drop_last("sos_response_rc")       # recorded, not issued: it rides in the input's column pass
+    if getattr(_lib._pair, "stream_of", None) is not None and _lib.lib(pair_ok=True).fl_launch_pair_pending():
+        # recorded, not issued: it rides in the input's column pass
+        _pair_keep((b, a, Wc, Wd, G, H) + ((geq[0], geq[2]) if geq is not None else ()))
+        if kernel_timer.enabled:
+            kernel_timer.drop_last("sos_response_rc")
     return H.movedim(-1, 0), G, (float(gamma), nfft, S, No * Nmid, bin0, m_local, real)
 
 

@@ -297,6 +297,10 @@ class Series(nn.Sequential):
                             shp2[2] = module.output_channels
                             H = nxt._response_times_matrix(nxt._param_for_fusion(shp2, ext_of(nxt_key)), Wr)
                             if H is not None:
+                                if i + 2 < len(run):
+                                    # modules behind the pair compose with H, also through torch operations (_compose's
+                                    # dtype promotion): its launch cannot wait for the input's column pass (ops.paired_launch)
+                                    ops.flush_launch_pair()
                                 acc = (H, False)
                                 shp[2] = nxt.output_channels
                                 i += 2

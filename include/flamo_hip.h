@@ -787,7 +787,8 @@ int fl_eig_c128(const void* A, long a_pitch, int N, int M, void* lam, long l_pit
  * half of torch.fft.rfft, dsp.py:88).  Between begin and flush on the calling thread the response launch is RECORDED; the next
  * fl_spec_cols_fwd_f32 issues both (shapes it does not take: the recorded launch first, alone); flush issues a launch that is
  * still recorded and ends the mode.  The caller guarantees that nothing reads the response's outputs in between.
- * fl_launch_pair_pending: 1 while a launch is recorded.  FLAMO_LAUNCH_PAIR=0 turns recording off. */
+ * fl_launch_pair_pending: 1 while a launch is recorded.  FLAMO_LAUNCH_PAIR=0 turns recording off.  One launch is recorded at a
+ * time: a second one issues the first on its own stream; begin while one is recorded returns FL_ERR_BAD_ARG and keeps it. */
 int fl_launch_pair_begin(void);
 int fl_launch_pair_pending(void);
 long fl_debug_launch_pair_count(void);      /* grids issued with both roles so far (process-wide) */
