@@ -764,7 +764,7 @@ using namespace fl;
 
 extern "C" {
 int fl_debug_set_cascade_lanes(int on, int blocks_per_cu, int tile_bins) {
-    const int prev = g_lanes;
+    const int prev = g_lanes | ((g_lanes && !g_lanes_fwd) ? 2 : 0);      // (the previous `on`, the forward split included)
     if (on >= 0) {
         g_lanes = on & 1;
         g_lanes_fwd = (on & 1) && !(on & 2);      // (on = 3: second-generation backward, first-generation forward)

@@ -237,7 +237,17 @@ __device__ __forceinline__ void rc_ba_body(const RcBaArgs& A, int bx, int m, cha
         for (int q = 0; q < 2; ++q) {
             const float Bx = Pr[q].x, By = Pi[q].x, Ax = Pr[q].y, Ay = Pi[q].y;
             f2 hf;
-            if (Ax != 0.f || Ay != 0.f) {
+            if (float_cascade_tiny(Ax, Ay)) {      // (see float_cascade_tiny): the same tables walked in double
+                const f4* tq = tab + (size_t)(j * 2 + (low[q] ? 0 : 1)) * Seff * 2;
+                cx<double> Bd(1, 0), Ad(1, 0);
+                for (int se = 0; se < Seff; ++se) {
+                    const f4 e0 = tq[2 * se], e1 = tq[2 * se + 1];
+                    Bd = Bd * cx<double>((double)e0.x + (double)e0.z * (double)xr[q], (double)e1.x * (double)xi[q]);
+                    Ad = Ad * cx<double>((double)e0.y + (double)e0.w * (double)xr[q], (double)e1.y * (double)xi[q]);
+                }
+                const cx<float> h = quotient_of(Bd, Ad);
+                hf = f2{h.x, h.y};
+            } else if (Ax != 0.f || Ay != 0.f) {
                 const float inv = __builtin_amdgcn_rcpf(Ax * Ax + Ay * Ay);      // (1 ulp; an IEEE division is ten instructions per bin and cascade)
                 hf = f2{(Bx * Ax + By * Ay) * inv, (By * Ax - Bx * Ay) * inv};
             } else {

@@ -257,7 +257,10 @@ __global__ void __launch_bounds__(256) sos_response_rc_fast_kernel(const double*
             const float Bx = pbr[q].x * pbr[q].y - pbi[q].x * pbi[q].y, By = pbr[q].x * pbi[q].y + pbi[q].x * pbr[q].y;
             const float Ax = par[q].x * par[q].y - pai[q].x * pai[q].y, Ay = par[q].x * pai[q].y + pai[q].x * par[q].y;
             cx<float> hf;
-            if (Ax != 0.f || Ay != 0.f) {
+            if (float_cascade_tiny(Ax, Ay)) {
+                hf = quotient_from_tables(cf + ((size_t)j * 4 + (low[q] ? 0 : 2)) * 3 * SP, cf + ((size_t)j * 4 + (low[q] ? 0 : 2) + 1) * 3 * SP,
+                                          SP, xr[q], xi[q]);
+            } else if (Ax != 0.f || Ay != 0.f) {
                 const float inv = __builtin_amdgcn_rcpf(Ax * Ax + Ay * Ay);      // (1 ulp; an IEEE division is ten instructions per bin and cascade)
                 hf = cx<float>((Bx * Ax + By * Ay) * inv, (By * Ax - Bx * Ay) * inv);
             } else {
@@ -334,7 +337,9 @@ __global__ void __launch_bounds__(256) sos_response_apply_fast_kernel(const doub
         const float Bx = pbr.x * pbr.y - pbi.x * pbi.y, By = pbr.x * pbi.y + pbi.x * pbr.y;
         const float Ax = par.x * par.y - pai.x * pai.y, Ay = par.x * pai.y + pai.x * par.y;
         cx<float> hf;
-        if (Ax != 0.f || Ay != 0.f) {
+        if (float_cascade_tiny(Ax, Ay)) {
+            hf = quotient_from_tables(cb, ca, SP, xr, xi);
+        } else if (Ax != 0.f || Ay != 0.f) {
             const float inv = 1.0f / (Ax * Ax + Ay * Ay);
             hf = cx<float>((Bx * Ax + By * Ay) * inv, (By * Ax - Bx * Ay) * inv);
         } else {
@@ -410,7 +415,9 @@ __global__ void __launch_bounds__(256) sos_response_fast_kernel(const double* __
         const float Bx = pbr.x * pbr.y - pbi.x * pbi.y, By = pbr.x * pbi.y + pbi.x * pbr.y;
         const float Ax = par.x * par.y - pai.x * pai.y, Ay = par.x * pai.y + pai.x * par.y;
         cx<float> hf;
-        if (Ax != 0.f || Ay != 0.f) {
+        if (float_cascade_tiny(Ax, Ay)) {
+            hf = quotient_from_tables(cb, ca, SP, xr, xi);
+        } else if (Ax != 0.f || Ay != 0.f) {
             const float inv = 1.0f / (Ax * Ax + Ay * Ay);
             hf = cx<float>((Bx * Ax + By * Ay) * inv, (By * Ax - Bx * Ay) * inv);
         } else {
@@ -1215,15 +1222,19 @@ int fl_sos_response_c128(const void* b, const void* a, int S, int C, double gamm
     return sos_impl<double>(b, a, S, C, gamma, Wd, nfft, bin0, m_local, H, h_pitch, stream);
 }
 int fl_sos_bwd_blocks(int m_local, int C, int S, int mixed) { return sos_blocks(m_local, C, S, mixed != 0); }
+// (test hooks: both return the previous setting; a negative argument only asks for it)
 int fl_debug_set_rc_fast(int on) {
-    g_rc_fast = on;
-    return FL_OK;
+    const int prev = g_rc_fast;
+    if (on >= 0) g_rc_fast = on;
+    return prev;
 }
 int fl_debug_set_sos_chunk(int sections_per_thread) {
+    const int prev = g_sos_blocks * 100 + g_sos_chunk;
+    if (sections_per_thread < 0) return prev;
     g_sos_blocks = sections_per_thread / 100;      // hundreds digit(s): blocks per channel (0 = default)
     sections_per_thread %= 100;
     g_sos_chunk = sections_per_thread;
-    return FL_OK;
+    return prev;
 }
 
 int fl_geq_sections(const void* gain, int in_kind, int nb, int C, const void* consts, void* b, void* a, void* stream) {

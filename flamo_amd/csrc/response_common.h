@@ -206,6 +206,29 @@ __device__ inline void half_turn_tables(double t0, double t1, double t2, double 
     hi[0] = (float)(T - S); hi[pitch] = (float)S;    hi[2 * pitch] = (float)D;
 }
 
+// The float evaluations form prod B_s and prod A_s in float.  Near DC every peak section of a graphic equaliser nearly vanishes
+// (A_s(1) = 2 sqrt(g) (1 - cos wc)): the products of an octave equaliser with attenuating gains fall to ~1e-22, where |A|^2
+// underflows, and those of a third-octave one leave the float range inside the chain.  Where |A| < 2^-60 (float_cascade_tiny)
+// the bin is evaluated again from the same float tables with double products (quotient_from_tables): a handful of bins near
+// DC; every other bin keeps the float result bit for bit.
+__device__ __forceinline__ bool float_cascade_tiny(float Ax, float Ay) { return fmaxf(fabsf(Ax), fabsf(Ay)) < 0x1p-60f; }
+
+__device__ __forceinline__ cx<float> quotient_of(cx<double> B, cx<double> A) {
+    if (A.x == 0 && A.y == 0) return cx<float>(eps_of<float>(), 0.f);
+    const cx<double> h = cdiv(B, A);
+    return cx<float>((float)h.x, (float)h.y);
+}
+
+// half-turn tables [3][SP] of the numerator (cb) and denominator (ca): section s is (c0 + c1 x) + i c2 sin(omega)
+__device__ __noinline__ cx<float> quotient_from_tables(const float* cb, const float* ca, int SP, float xr, float xi) {
+    cx<double> B(1, 0), A(1, 0);
+    for (int s = 0; s < SP; ++s) {
+        B = B * cx<double>((double)cb[s] + (double)cb[SP + s] * (double)xr, (double)cb[2 * SP + s] * (double)xi);
+        A = A * cx<double>((double)ca[s] + (double)ca[SP + s] * (double)xr, (double)ca[2 * SP + s] * (double)xi);
+    }
+    return quotient_of(B, A);
+}
+
 struct GeqDesign {
     const void* gain;      // (nb, C) command gains / raw parameters, or null: sections are read from b, a
     int in_kind;
