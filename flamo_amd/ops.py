@@ -14,7 +14,8 @@ from __future__ import annotations
 
 import math
 import threading
-from typing import Optional, Tuple
+from collections import namedtuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -2054,69 +2055,68 @@ FLOAT_CASCADE_EVAL = True
 SOS_BWD_MIXED = True
 
 
-def _sos_forward_launch(bc, ac, gamma, nfft, real, float_eval=False):
-    """bc, ac: contiguous float64 (3, S, chan...) on the GPU -> (H rows buffer (chan..., pitch)[..., :m_local], cfg)"""
+class _CascadeCfg(NamedTuple):
+    """what a cascade's forward launch hands its backward"""
+    gamma: float
+    nfft: int
+    S: int             # sections
+    C: int             # cascades (channel pairs)
+    bin0: int          # first bin of the shard; -L2: row-major order (see _bin0_arg)
+    m_local: int       # bins of the shard; 0: an empty one, for which no kernel is launched (they refuse null pointers)
+    real: torch.dtype
+
+
+def _cascade_cfg(gamma, nfft, S, C_, real) -> _CascadeCfg:
+    return _CascadeCfg(float(gamma), nfft, S, C_, *_bin0_arg(nfft), real)
+
+
+def _zero_part(cfg, dev):
+    """the cascade backward's partial sums for an empty bin shard: no bin contributes"""
+    return torch.zeros((1, 2, 3, cfg.S, cfg.C), dtype=torch.float64, device=dev)
+
+
+def _sos_forward_launch(bc, ac, gamma, nfft, real, float_eval=False, geq=None):
+    """bc, ac: contiguous float64 (3, S, chan...) on the GPU -> (H rows buffer (chan..., pitch)[..., :m_local], cfg).
+    geq = (raw gains, in_kind, band constants), float32 only: bc, ac are OUTPUTS, designed by the same launch (the float kernel
+    designs the sections in its prologue: fl_geq_response_c64)."""
     dev = bc.device
-    S = bc.shape[1]
     chan = tuple(bc.shape[2:])
-    C_ = max(_prod(chan), 1)
-    bin0, m_local = _bin0_arg(nfft)
-    H = _empty_rows(chan, m_local, _cdtype(real), dev)
+    cfg = _cascade_cfg(gamma, nfft, bc.shape[1], max(_prod(chan), 1), real)
+    H = _empty_rows(chan, cfg.m_local, _cdtype(real), dev)
     L = _lib.lib()
-    if real == torch.float32:
-        fn = L.fl_sos_response_f32eval_c64 if (float_eval and FLOAT_CASCADE_EVAL) else L.fl_sos_response_c64
-    else:
-        fn = L.fl_sos_response_c128
-    if m_local == 0:      # an empty bin shard: nothing to evaluate (the kernels refuse the empty buffers' null pointers)
-        return H, (float(gamma), nfft, S, C_, bin0, m_local, real)
+    if cfg.m_local == 0 and geq is None:      # nothing to evaluate (a designing launch still has bc, ac to write)
+        return H, cfg
     Wd = twiddles(nfft, torch.float64, dev)
+    tail = (cfg.C, cfg.gamma, Wd.data_ptr(), nfft, cfg.bin0, cfg.m_local, H.data_ptr(), _pitch(cfg.m_local))
+    float_eval = bool(float_eval and FLOAT_CASCADE_EVAL)
     with kernel_timer.span("sos_response"):
-        _lib.check(fn(bc.data_ptr(), ac.data_ptr(), S, C_, float(gamma), Wd.data_ptr(), nfft, bin0, m_local,
-                      H.data_ptr(), _pitch(m_local), _stream()), "sos_response")
-    return H, (float(gamma), nfft, S, C_, bin0, m_local, real)
+        if geq is not None:
+            xc, kind, consts = geq
+            _lib.check(L.fl_geq_response_c64(xc.data_ptr(), kind, cfg.S, consts.data_ptr(), bc.data_ptr(), ac.data_ptr(), *tail,
+                                             int(float_eval), _stream()), "geq_response")
+        else:
+            fn = L.fl_sos_response_c128 if real == torch.float64 else \
+                (L.fl_sos_response_f32eval_c64 if float_eval else L.fl_sos_response_c64)
+            _lib.check(fn(bc.data_ptr(), ac.data_ptr(), cfg.S, *tail, _stream()), "sos_response")
+    return H, cfg
 
 
 def _sos_backward_launch(gH, Hf, bc, ac, cfg):
     """-> part: float64 (nblk, 2, 3, S, C) per-bin-block partial sums of (dL/db, dL/da)"""
-    gamma, nfft, S, C_, bin0, m_local, real = cfg
-    if m_local == 0:      # an empty bin shard: no bin contributes
-        return torch.zeros((1, 2, 3, S, C_), dtype=torch.float64, device=bc.device)
+    if cfg.m_local == 0:
+        return _zero_part(cfg, bc.device)
     g = _h_planar(gH.resolve_conj(), True)
     g_pitch = _lead_pitch(g.movedim(0, -1))
     L = _lib.lib()
-    nblk = L.fl_sos_bwd_blocks(m_local, C_, S, int(real == torch.float32 and Hf is not None))
-    part = torch.empty((nblk, 2, 3, S, C_), dtype=torch.float64, device=bc.device)   # every entry is written
-    fn = L.fl_sos_response_bwd_c64 if real == torch.float32 else L.fl_sos_response_bwd_c128
-    Wd = twiddles(nfft, torch.float64, bc.device)
+    nblk = L.fl_sos_bwd_blocks(cfg.m_local, cfg.C, cfg.S, int(cfg.real == torch.float32 and Hf is not None))
+    part = torch.empty((nblk, 2, 3, cfg.S, cfg.C), dtype=torch.float64, device=bc.device)   # every entry is written
+    fn = L.fl_sos_response_bwd_c64 if cfg.real == torch.float32 else L.fl_sos_response_bwd_c128
+    Wd = twiddles(cfg.nfft, torch.float64, bc.device)
     with kernel_timer.span("sos_response_bwd"):
-        _lib.check(fn(g.data_ptr(), g_pitch, None if Hf is None else Hf.data_ptr(), _pitch(m_local), bc.data_ptr(),
-                      ac.data_ptr(), S, C_, gamma, Wd.data_ptr(), nfft, bin0, m_local, part.data_ptr(), _stream()),
-                   "sos_response_bwd")
+        _lib.check(fn(g.data_ptr(), g_pitch, None if Hf is None else Hf.data_ptr(), _pitch(cfg.m_local), bc.data_ptr(),
+                      ac.data_ptr(), cfg.S, cfg.C, cfg.gamma, Wd.data_ptr(), cfg.nfft, cfg.bin0, cfg.m_local, part.data_ptr(),
+                      _stream()), "sos_response_bwd")
     return part
-
-
-class _Sos(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, b, a, gamma, nfft, real):
-        _require_gpu(b, a)
-        if b.shape != a.shape or b.shape[0] != 3 or b.dim() < 2:
-            raise ValueError("sos_response: b and a must both be (3, n_sections, ...)")
-        if b.dtype != torch.float64 or a.dtype != torch.float64:
-            raise TypeError("sos_response: coefficients are passed in float64")
-        bc, ac = b.contiguous(), a.contiguous()
-        # raw section coefficients: float evaluation only when no gradient will reuse the saved response (see FLOAT_CASCADE_EVAL)
-        H, ctx.cfg = _sos_forward_launch(bc, ac, gamma, nfft, real, not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]))
-        # the backward reuses the forward output instead of re-evaluating the cascade
-        keep = H if (real == torch.float64 or SOS_BWD_MIXED) else None
-        ctx.save_for_backward(bc, ac, *([keep] if keep is not None else []))
-        return H.movedim(-1, 0)
-
-    @staticmethod
-    def backward(ctx, gH):
-        bc, ac, *kept = ctx.saved_tensors
-        part = _sos_backward_launch(gH, kept[0] if kept else None, bc, ac, ctx.cfg)
-        tot = part.sum(dim=0)
-        return tot[0].view(bc.shape), tot[1].view(ac.shape), None, None, None
 
 
 def _geq_in_kind(t: torch.Tensor, linear: bool, sig: bool = False) -> int:
@@ -2127,18 +2127,38 @@ def _geq_in_kind(t: torch.Tensor, linear: bool, sig: bool = False) -> int:
     return (4 if sig else 2) if t.dtype == torch.float32 else (3 if sig else 1)
 
 
+def _empty_sections(gains: torch.Tensor):
+    """b, a (3, n_bands, *chan) float64 for a design kernel to fill from gains (n_bands, *chan)"""
+    b = torch.empty((3, *gains.shape), dtype=torch.float64, device=gains.device)
+    return b, torch.empty_like(b)
+
+
+def _geq_sections_bwd_launch(xc, kind, consts, gb_ptr, ga_ptr, blk_stride, nblk, partW=None, Wr=None):
+    """The design's backward: dL/d(b, a), given as nblk blocks blk_stride elements apart that the kernel sums, -> dL/dx (as xc).
+    With partW (nblk', No, Nmid, Ni) the same launch sums the constant factor's partials: -> (dL/dx, dL/dWr or None)."""
+    nb = xc.shape[0]
+    C_ = max(_prod(xc.shape[1:]), 1)
+    out = torch.empty_like(xc)
+    gW = None if partW is None else torch.empty_like(Wr, memory_format=torch.contiguous_format)
+    L = _lib.lib()
+    args = (xc.data_ptr(), kind, gb_ptr, ga_ptr, blk_stride, nblk, nb, C_, consts.data_ptr(), out.data_ptr())
+    if partW is None:
+        _lib.check(L.fl_geq_sections_bwd(*args, _stream()), "geq_sections_bwd")
+    else:
+        fn = L.fl_geq_sections_bwd_w64 if partW.dtype == torch.float64 else L.fl_geq_sections_bwd_w
+        _lib.check(fn(*args, partW.data_ptr(), partW.shape[0] * partW.shape[1], partW.shape[2] * partW.shape[3], gW.data_ptr(),
+                      _stream()), "geq_sections_bwd_w")
+    return out, gW
+
+
 class _GeqSections(torch.autograd.Function):
     @staticmethod
     def forward(ctx, gain_db, consts):
-        dev = _require_gpu(gain_db, consts)
+        _require_gpu(gain_db, consts)
         gd = gain_db.to(torch.float64).contiguous()
-        nb = gd.shape[0]
-        chan = tuple(gd.shape[1:])
-        C_ = max(_prod(chan), 1)
-        b = torch.empty((3, nb, *chan), dtype=torch.float64, device=dev)
-        a = torch.empty_like(b)
-        _lib.check(_lib.lib().fl_geq_sections(gd.data_ptr(), 0, nb, C_, consts.data_ptr(), b.data_ptr(), a.data_ptr(),
-                                              _stream()), "geq_sections")
+        b, a = _empty_sections(gd)
+        _lib.check(_lib.lib().fl_geq_sections(gd.data_ptr(), 0, gd.shape[0], max(_prod(gd.shape[1:]), 1), consts.data_ptr(),
+                                              b.data_ptr(), a.data_ptr(), _stream()), "geq_sections")
         ctx.save_for_backward(gd, consts)
         ctx.in_dtype = gain_db.dtype
         return b, a
@@ -2146,70 +2166,135 @@ class _GeqSections(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gb, ga):
         gd, consts = ctx.saved_tensors
-        nb = gd.shape[0]
-        C_ = max(_prod(gd.shape[1:]), 1)
-        out = torch.empty_like(gd)
         gb = torch.zeros_like(gd.new_empty((3, *gd.shape))) if gb is None else gb.to(torch.float64).contiguous()
         ga = torch.zeros_like(gb) if ga is None else ga.to(torch.float64).contiguous()
-        _lib.check(_lib.lib().fl_geq_sections_bwd(gd.data_ptr(), 0, gb.data_ptr(), ga.data_ptr(), 0, 1, nb, C_,
-                                                  consts.data_ptr(), out.data_ptr(), _stream()), "geq_sections_bwd")
+        out, _ = _geq_sections_bwd_launch(gd, 0, consts, gb.data_ptr(), ga.data_ptr(), 0, 1)
         return out.to(ctx.in_dtype), None
 
 
-class _GeqCascade(torch.autograd.Function):
-    """GEQ / parallelGEQ under the default map: raw parameters -> response in two launches
-    (design + cascade), gradient in two (cascade backward + design backward, which also sums the
-    bin-block partials)."""
+# ---- the cascade ops are a grid: where the sections come from (a design: RawSections | GeqGains) x what is done with the
+# response (a tail: _Cascade H | _CascadeRC H = G @ Wr | _CascadeApply Y = H X).  A design is a tuple of the tensors it starts
+# from -- what the modules hand over (dsp._cascade_spec) -- and the three tails as methods.  The autograd functions take it as
+# their first argument and its tensors once more behind it, where autograd sees them; they keep it for their backward (it
+# holds inputs only) and save what its sections() returns in front of their own tensors.
+class _Design:
+    __slots__ = ()
+
+    def response(self, gamma, nfft, dtype=torch.float32):
+        return _Cascade.apply(self, *self.tensors(), float(gamma), int(nfft), dtype)
+
+    def response_rc(self, Wr, gamma, nfft, dtype=torch.float32):
+        return _CascadeRC.apply(self, *self.tensors(), Wr.to(dtype), float(gamma), int(nfft), dtype)
+
+    def response_apply(self, X, gamma, nfft, dtype=torch.float32):
+        return _CascadeApply.apply(self, *self.tensors(), X, float(gamma), int(nfft), dtype)
+
+    def float_eval(self, ctx):
+        return self.float_with_grad or not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+
+    def lanes_grads(self, sec, gH, G, cfg, Wr=None):
+        return None      # no lanes-per-section backward but the graphic equaliser's
+
+
+class RawSections(_Design, namedtuple("RawSections", "kind b a")):
+    """("sos", b, a): the sections themselves, b, a (3, n_sections, *chan)"""
+    __slots__ = ()
+    float_with_grad = False    # float evaluation only when no gradient will reuse the saved response (see FLOAT_CASCADE_EVAL)
+    n_sections = property(lambda self: self.b.shape[1])
+    full = property(lambda self: self.b.dim() == 4)      # one cascade per (N_out, N_in) pair
+
+    def tensors(self):
+        return self.b.to(torch.float64), self.a.to(torch.float64)
+
+    def sections(self, b, a, op, prologue):
+        """-> (sec, None), sec = (b, a, b, a): the design's parameters (as the kernels read them) and its sections, contiguous
+        float64 -- here the same; what a tail saves for its backward"""
+        if b.shape != a.shape or b.shape[0] != 3 or (b.dim() != 4 if op else b.dim() < 2):
+            raise ValueError(f"sos_response{op}: b and a must both be (3, n_sections, {'N_out, N_in' if op else '...'})")
+        return (b.contiguous(), a.contiguous()) * 2, None
+
+    def param_grads(self, sec, part, partW=None, Wr=None):
+        """(dL/db, dL/da[, dL/dWr]) from the cascade backward's block partials"""
+        b, a = sec[2:]
+        tot = part.sum(dim=0)
+        g = (tot[0].view(b.shape), tot[1].view(a.shape))
+        return g if partW is None else g + (partW.sum(dim=(0, 1)).to(Wr.dtype),)
+
+
+class GeqGains(_Design, namedtuple("GeqGains", "kind x consts gain_map")):
+    """("geq", x, consts, gain_map): raw parameters x (n_bands, *chan) of a graphic equaliser under the map 20 log10|x|
+    ("abs") or 20 log10(sigmoid(x)) ("sigmoid"), with the map and its backward folded into the design kernels"""
+    __slots__ = ()
+    float_with_grad = True     # graphic-equaliser sections: always (see FLOAT_CASCADE_EVAL)
+    n_sections = property(lambda self: self.x.shape[0])
+    full = property(lambda self: self.x.dim() == 3)
+
+    def tensors(self):
+        return self.x, self.consts
+
+    def sections(self, x, consts, op, prologue):
+        """-> (sec, geq), sec = (xc, consts, b, a): b, a fresh; designed here (geq None), or left to a response kernel that
+        designs in its prologue and is handed geq = (xc, in_kind, consts)"""
+        if x.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"geq_cascade{op} expects float32 / float64 parameters")
+        xc = x.contiguous()
+        if op == "_apply" and xc.dim() != 3:
+            raise ValueError(f"geq_cascade{op} expects full (n_bands, N_out, N_in) parameters")
+        b, a = _empty_sections(xc)
+        geq = (xc, _geq_in_kind(xc, True, _is_sigmoid(self.gain_map)), consts)
+        if not prologue:
+            _lib.check(_lib.lib().fl_geq_sections(xc.data_ptr(), geq[1], xc.shape[0], max(_prod(xc.shape[1:]), 1),
+                                                  consts.data_ptr(), b.data_ptr(), a.data_ptr(), _stream()), "geq_sections")
+        return (xc, consts, b, a), geq if prologue else None
+
+    def lanes_grads(self, sec, gH, G, cfg, Wr=None):
+        """(dL/dx, None[, dL/dWr]) through the lanes-per-section backward (csrc/cascade2.hip: mode 0 the response's gradient,
+        mode 1 with the constant factor), or None where it does not apply: G is the kept response (cascade's, not the product's)"""
+        if G is None:
+            return None
+        mode = int(Wr is not None)
+        No, Nmid, Ni = (G.shape[0], G.shape[1], Wr.shape[1]) if mode else (cfg.C, 1, 0)
+        nbx = _geq_lanes_blocks(cfg, Nmid, Ni, mode)
+        if nbx <= 0:
+            return None
+        xc, consts, b, a = sec
+        out, gW = _geq_backward_lanes(mode, gH, G, b, a, Wr, cfg, No, Nmid, Ni, nbx, xc, consts, _is_sigmoid(self.gain_map))
+        return (out, None, gW) if mode else (out, None)
+
+    def param_grads(self, sec, part, partW=None, Wr=None):
+        """(dL/dx, None[, dL/dWr]): the design backward, which also sums the cascade backward's block partials
+        part (nblk, 2, 3, n_bands, C) -- dL/db at its start, dL/da three taps on, blocks six taps apart"""
+        xc, consts = sec[:2]
+        st = part.shape[3] * part.shape[4]
+        out, gW = _geq_sections_bwd_launch(xc, _geq_in_kind(xc, True, _is_sigmoid(self.gain_map)), consts, part.data_ptr(),
+                                           part.data_ptr() + 3 * st * part.element_size(), 6 * st, part.shape[0], partW, Wr)
+        return (out, None) if partW is None else (out, None, gW)
+
+
+class _Cascade(torch.autograd.Function):
+    """Response of a cascade.  Raw sections: one launch each way (+ the sum of the block partials).  Graphic equaliser: raw
+    parameters -> response in two launches (design + cascade; one in float32), gradient in two (cascade backward + design
+    backward, which also sums the bin-block partials; or the lanes pair)."""
 
     @staticmethod
-    def forward(ctx, x, consts, gamma, nfft, real, sig=False):
-        dev = _require_gpu(x, consts)
-        ctx.sig = bool(sig)
-        if x.dtype not in (torch.float32, torch.float64):
-            raise TypeError("geq_cascade expects float32 / float64 parameters")
-        xc = x.contiguous()
-        nb = xc.shape[0]
-        chan = tuple(xc.shape[1:])
-        C_ = max(_prod(chan), 1)
-        kind = _geq_in_kind(xc, True, sig)
-        b = torch.empty((3, nb, *chan), dtype=torch.float64, device=dev)
-        a = torch.empty_like(b)
-        if real == torch.float32:
-            # design + cascade in one launch (the float kernel designs the sections in its prologue)
-            bin0, m_local = _bin0_arg(nfft)
-            H = _empty_rows(chan, m_local, torch.complex64, dev)
-            with kernel_timer.span("sos_response"):
-                _lib.check(_lib.lib().fl_geq_response_c64(xc.data_ptr(), kind, nb, consts.data_ptr(), b.data_ptr(), a.data_ptr(), C_, float(gamma),
-                                                          twiddles(nfft, torch.float64, dev).data_ptr(), nfft, bin0, m_local, H.data_ptr(),
-                                                          _pitch(m_local), int(bool(FLOAT_CASCADE_EVAL)), _stream()), "geq_response")
-            ctx.cfg = (float(gamma), nfft, nb, C_, bin0, m_local, real)
-        else:
-            _lib.check(_lib.lib().fl_geq_sections(xc.data_ptr(), kind, nb, C_, consts.data_ptr(), b.data_ptr(), a.data_ptr(),
-                                                  _stream()), "geq_sections")
-            H, ctx.cfg = _sos_forward_launch(b, a, gamma, nfft, real, True)     # graphic-equaliser sections
-        keep = H if (real == torch.float64 or SOS_BWD_MIXED) else None
-        ctx.save_for_backward(xc, consts, b, a, *([keep] if keep is not None else []))
+    def forward(ctx, design, p, q, gamma, nfft, real):
+        _require_gpu(p, q)
+        ctx.design = design
+        sec, geq = design.sections(p, q, "", prologue=real == torch.float32)
+        H, ctx.cfg = _sos_forward_launch(*sec[2:], gamma, nfft, real, design.float_eval(ctx), geq)
+        # the backward reuses the forward output instead of re-evaluating the cascade
+        keep = [H] if (real == torch.float64 or SOS_BWD_MIXED) else []
+        ctx.save_for_backward(*sec, *keep)
         return H.movedim(-1, 0)
 
     @staticmethod
     def backward(ctx, gH):
-        xc, consts, b, a, *kept = ctx.saved_tensors
-        nbx = _geq_lanes_blocks(ctx.cfg, 1, 0, 0) if kept else 0
-        if nbx > 0:
-            C_ = ctx.cfg[3]
-            out, _ = _geq_backward_lanes(0, gH, kept[0], b, a, None, ctx.cfg, C_, 1, 0, nbx, xc, consts, ctx.sig)
-            return out, None, None, None, None, None
-        part = _sos_backward_launch(gH, kept[0] if kept else None, b, a, ctx.cfg)
-        nblk = part.shape[0]
-        nb = xc.shape[0]
-        C_ = max(_prod(xc.shape[1:]), 1)
-        st = nb * C_
-        out = torch.empty_like(xc)
-        esz = part.element_size()
-        _lib.check(_lib.lib().fl_geq_sections_bwd(xc.data_ptr(), _geq_in_kind(xc, True, ctx.sig), part.data_ptr(),
-                                                  part.data_ptr() + 3 * st * esz, 6 * st, nblk, nb, C_, consts.data_ptr(),
-                                                  out.data_ptr(), _stream()), "geq_sections_bwd")
-        return out, None, None, None, None, None
+        sec, kept = ctx.saved_tensors[:4], ctx.saved_tensors[4:]
+        Hf = kept[0] if kept else None
+        g = ctx.design.lanes_grads(sec, gH, Hf, ctx.cfg)
+        if g is None:
+            g = ctx.design.param_grads(sec, _sos_backward_launch(gH, Hf, *sec[2:], ctx.cfg))
+        return (None, *g, None, None, None)
 
 
 # ---- cascade response applied to a signal with few columns: Y = H X with dL/dH formed inside the cascade backward
@@ -2225,124 +2310,80 @@ def _sos_apply_forward(bc, ac, Xp, gamma, nfft, real, float_eval):
     S, No, Ni = bc.shape[1], bc.shape[2], bc.shape[3]
     B = Xp.shape[0]
     L = _lib.lib()
-    if _bin0_arg(nfft)[1] == 0:      # an empty bin shard: empty response and product
+    cfg = _cascade_cfg(gamma, nfft, S, No * Ni, real)
+    m_local = cfg.m_local
+    if m_local == 0 or not (float_eval and FLOAT_CASCADE_EVAL and real == torch.float32 and B <= 2
+                            and Ni <= L.fl_sos_response_apply_max_ni(S)):
         H, cfg = _sos_forward_launch(bc, ac, gamma, nfft, real, float_eval)
-        return H, _empty_planar((B, 0, No), _cdtype(real), bc.device), cfg
-    if not (float_eval and FLOAT_CASCADE_EVAL and real == torch.float32 and B <= 2 and Ni <= L.fl_sos_response_apply_max_ni(S)):
-        H, cfg = _sos_forward_launch(bc, ac, gamma, nfft, real, float_eval)
+        if m_local == 0:      # an empty bin shard: empty response and product
+            return H, _empty_planar((B, 0, No), _cdtype(real), bc.device), cfg
         return H, _mimo_launch(H.movedim(-1, 0), True, False, False, Xp), cfg
     dev = bc.device
-    bin0, m_local = _bin0_arg(nfft)
     _, M, Nx, K, xs_b, xs_n, _ = _bnk(Xp)
     assert K == 1 and Nx == Ni and M == m_local
     H = _empty_rows((No, Ni), m_local, torch.complex64, dev)
     Y = _empty_planar((B, m_local, No), torch.complex64, dev)
     _, _, _, _, ys_b, ys_m, _ = _bnk(Y)
     with kernel_timer.span("sos_response"):
-        _lib.check(L.fl_sos_response_apply_c64(bc.data_ptr(), ac.data_ptr(), S, No, Ni, Xp.data_ptr(), xs_b, xs_n, B, float(gamma),
-                                               twiddles(nfft, torch.float64, dev).data_ptr(), nfft, bin0, m_local, H.data_ptr(),
+        _lib.check(L.fl_sos_response_apply_c64(bc.data_ptr(), ac.data_ptr(), S, No, Ni, Xp.data_ptr(), xs_b, xs_n, B, cfg.gamma,
+                                               twiddles(nfft, torch.float64, dev).data_ptr(), nfft, cfg.bin0, m_local, H.data_ptr(),
                                                _pitch(m_local), Y.data_ptr(), ys_b, ys_m, _stream()), "sos_response_apply")
-    return H, Y, (float(gamma), nfft, S, No * Ni, bin0, m_local, real)
+    return H, Y, cfg
 
 
 def _sos_backward_outer_launch(gY, Xp, Hf, bc, ac, cfg, No, Ni):
     """part (nblk, 2, 3, S, C) with dL/dH[m][n] = sum_b gY[b][m] conj(X[b][n]) formed in the kernel"""
-    gamma, nfft, S, C_, bin0, m_local, real = cfg
-    if m_local == 0:
-        return torch.zeros((1, 2, 3, S, C_), dtype=torch.float64, device=bc.device)
+    if cfg.m_local == 0:
+        return _zero_part(cfg, bc.device)
     B, M, _, K, xs_b, xs_n, _ = _bnk(Xp)
     _, _, _, _, gs_b, gs_n, _ = _bnk(gY)
-    assert K == 1 and C_ == No * Ni and M == m_local
+    assert K == 1 and cfg.C == No * Ni and M == cfg.m_local
     L = _lib.lib()
-    part = torch.empty((L.fl_sos_bwd_blocks(m_local, C_, S, 1), 2, 3, S, C_), dtype=torch.float64, device=bc.device)
+    part = torch.empty((L.fl_sos_bwd_blocks(cfg.m_local, cfg.C, cfg.S, 1), 2, 3, cfg.S, cfg.C), dtype=torch.float64, device=bc.device)
     with kernel_timer.span("sos_response_bwd"):
         _lib.check(L.fl_sos_response_bwd_outer_c64(gY.data_ptr(), gs_b, gs_n, Xp.data_ptr(), xs_b, xs_n, B, No, Ni, Hf.data_ptr(),
-                                                   _pitch(m_local), bc.data_ptr(), ac.data_ptr(), S, gamma,
-                                                   twiddles(nfft, torch.float64, bc.device).data_ptr(), nfft, bin0, m_local,
-                                                   part.data_ptr(), _stream()), "sos_response_bwd_outer")
+                                                   _pitch(cfg.m_local), bc.data_ptr(), ac.data_ptr(), cfg.S, cfg.gamma,
+                                                   twiddles(cfg.nfft, torch.float64, bc.device).data_ptr(), cfg.nfft, cfg.bin0,
+                                                   cfg.m_local, part.data_ptr(), _stream()), "sos_response_bwd_outer")
     return part
 
 
-class _SosApply(torch.autograd.Function):
-    """Y[b,:,f] = sos_response(b, a)[f] X[b,:,f] for a full (N_out, N_in) cascade and a vector signal"""
+class _CascadeApply(torch.autograd.Function):
+    """Y[b,:,f] = response[f] X[b,:,f] for a full (N_out, N_in) cascade and a vector signal: (design +) cascade + product
+    forward; cascade backward (outer product formed in the kernel) (+ design backward)."""
 
     @staticmethod
-    def forward(ctx, b, a, X, gamma, nfft, real):
-        _require_gpu(b, a, X)
-        if b.shape != a.shape or b.shape[0] != 3 or b.dim() != 4:
-            raise ValueError("sos_response_apply: b and a must both be (3, n_sections, N_out, N_in)")
-        bc, ac = b.contiguous(), a.contiguous()
+    def forward(ctx, design, p, q, X, gamma, nfft, real):
+        _require_gpu(p, q, X)
+        ctx.design = design
+        sec, _ = design.sections(p, q, "_apply", prologue=False)
         Xp = to_planar(X.resolve_conj())
-        H, Y, ctx.cfg = _sos_apply_forward(bc, ac, Xp, gamma, nfft, real,
-                                           not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]))
-        ctx.save_for_backward(bc, ac, H, Xp)
+        H, Y, ctx.cfg = _sos_apply_forward(*sec[2:], Xp, gamma, nfft, real, design.float_eval(ctx))
+        ctx.save_for_backward(*sec, H, Xp)
         return Y
 
     @staticmethod
     def backward(ctx, gY):
-        bc, ac, H, Xp = ctx.saved_tensors
+        *sec, H, Xp = ctx.saved_tensors
+        b, a = sec[2:]
         gY = to_planar(gY.resolve_conj())
-        gb = ga = gX = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            tot = _sos_backward_outer_launch(gY, Xp, H, bc, ac, ctx.cfg, bc.shape[2], bc.shape[3]).sum(dim=0)
-            gb, ga = tot[0].view(bc.shape), tot[1].view(ac.shape)
-        if ctx.needs_input_grad[2]:
-            gX = _mimo_launch(H.movedim(-1, 0), True, False, True, gY) if ctx.cfg[5] else torch.zeros_like(Xp)
-        return gb, ga, gX, None, None, None
-
-
-class _GeqCascadeApply(torch.autograd.Function):
-    """Y = geq_cascade(x)[f] X[b,:,f]: design + cascade + product forward; cascade backward (outer product formed in the
-    kernel) + design backward."""
-
-    @staticmethod
-    def forward(ctx, x, consts, X, gamma, nfft, real, sig=False):
-        dev = _require_gpu(x, consts, X)
-        ctx.sig = bool(sig)
-        xc = x.contiguous()
-        if xc.dim() != 3:
-            raise ValueError("geq_cascade_apply expects full (n_bands, N_out, N_in) parameters")
-        nb = xc.shape[0]
-        chan = tuple(xc.shape[1:])
-        C_ = _prod(chan)
-        b = torch.empty((3, nb, *chan), dtype=torch.float64, device=dev)
-        a = torch.empty_like(b)
-        _lib.check(_lib.lib().fl_geq_sections(xc.data_ptr(), _geq_in_kind(xc, True, sig), nb, C_, consts.data_ptr(), b.data_ptr(),
-                                              a.data_ptr(), _stream()), "geq_sections")
-        Xp = to_planar(X.resolve_conj())
-        H, Y, ctx.cfg = _sos_apply_forward(b, a, Xp, gamma, nfft, real, True)
-        ctx.save_for_backward(xc, consts, b, a, H, Xp)
-        return Y
-
-    @staticmethod
-    def backward(ctx, gY):
-        xc, consts, b, a, H, Xp = ctx.saved_tensors
-        gY = to_planar(gY.resolve_conj())
-        out = gX = None
-        if ctx.needs_input_grad[0]:
-            part = _sos_backward_outer_launch(gY, Xp, H, b, a, ctx.cfg, xc.shape[1], xc.shape[2])
-            nblk, nb = part.shape[0], xc.shape[0]
-            C_ = _prod(xc.shape[1:])
-            st = nb * C_
-            out = torch.empty_like(xc)
-            esz = part.element_size()
-            _lib.check(_lib.lib().fl_geq_sections_bwd(xc.data_ptr(), _geq_in_kind(xc, True, ctx.sig), part.data_ptr(),
-                                                      part.data_ptr() + 3 * st * esz, 6 * st, nblk, nb, C_, consts.data_ptr(),
-                                                      out.data_ptr(), _stream()), "geq_sections_bwd")
-        if ctx.needs_input_grad[2]:
-            gX = _mimo_launch(H.movedim(-1, 0), True, False, True, gY) if ctx.cfg[5] else torch.zeros_like(Xp)
-        return out, None, gX, None, None, None, None
+        g, gX = (None, None), None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            g = ctx.design.param_grads(sec, _sos_backward_outer_launch(gY, Xp, H, b, a, ctx.cfg, b.shape[2], b.shape[3]))
+        if ctx.needs_input_grad[3]:
+            gX = _mimo_launch(H.movedim(-1, 0), True, False, True, gY) if ctx.cfg.m_local else torch.zeros_like(Xp)
+        return (None, *g, gX, None, None, None)
 
 
 def sos_response_apply(b, a, X, gamma: float, nfft: int, dtype=torch.float32) -> torch.Tensor:
     """sos_response(b, a)[f] @ X[b, f] for a vector signal X (B, M, N_in) -- dsp.py:922-924 over the cascade tail
     dsp.py:1520-1526: the response's gradient never exists as a tensor (cascade_apply_supported)."""
-    return _SosApply.apply(b.to(torch.float64), a.to(torch.float64), X, float(gamma), int(nfft), dtype)
+    return RawSections("sos", b, a).response_apply(X, gamma, nfft, dtype)
 
 
 def geq_cascade_apply(x, consts, X, gamma: float, nfft: int, dtype=torch.float32, gain_map: str = "abs") -> torch.Tensor:
     """geq_cascade(x, consts)[f] @ X[b, f] for a vector signal X (B, M, N_in) (dsp.py:922-924 over dsp.py:2573-2593)"""
-    return _GeqCascadeApply.apply(x, consts, X, float(gamma), int(nfft), dtype, gain_map == "sigmoid")
+    return GeqGains("geq", x, consts, gain_map).response_apply(X, gamma, nfft, dtype)
 
 
 def cascade_rc_supported(real: torch.dtype, n_in: int, n_mid: int = 1, n_sections: int = 1) -> bool:
@@ -2372,64 +2413,55 @@ def _cascade_rc_forward(b, a, Wr, gamma, nfft, real, float_eval, geq=None):
     if Wr.dim() != 2 or Wr.shape[0] != Nmid:
         raise ValueError(f"cascade_rc: the constant factor must be ({Nmid}, N_in), got {tuple(Wr.shape)}")
     Ni = Wr.shape[1]
-    bin0, m_local = _bin0_arg(nfft)
+    cfg = _cascade_cfg(gamma, nfft, S, No * Nmid, real)
     f64 = real == torch.float64
-    G = _empty_rows((No, Nmid), m_local, _cdtype(real), dev)
-    H = _empty_rows((No, Ni), m_local, _cdtype(real), dev)
+    G = _empty_rows((No, Nmid), cfg.m_local, _cdtype(real), dev)
+    H = _empty_rows((No, Ni), cfg.m_local, _cdtype(real), dev)
     Wc = Wr.contiguous()
     Wd = twiddles(nfft, torch.float64, dev)
-    P = _pitch(m_local)
-    if m_local == 0 and geq is None:      # an empty bin shard: nothing to evaluate
-        return H.movedim(-1, 0), G, (float(gamma), nfft, S, No * Nmid, bin0, m_local, real)
+    P = _pitch(cfg.m_local)
+    if cfg.m_local == 0 and geq is None:      # nothing to evaluate (a designing launch still has b, a to write)
+        return H.movedim(-1, 0), G, cfg
     with kernel_timer.span("sos_response_rc"):
-        if f64 and geq is not None:
+        L = _lib.lib()
+        if geq is not None:
             xc, kind, consts = geq
-            _lib.check(_lib.lib().fl_geq_response_rc_c128(xc.data_ptr(), kind, S, consts.data_ptr(), b.data_ptr(), a.data_ptr(), No, Nmid, Ni,
-                                                          Wc.data_ptr(), float(gamma), Wd.data_ptr(), nfft,
-                                                          bin0, m_local, G.data_ptr(), P, H.data_ptr(), P, _stream()), "geq_response_rc")
-        elif f64:
-            _lib.check(_lib.lib().fl_sos_response_rc_c128(b.data_ptr(), a.data_ptr(), S, No, Nmid, Ni, Wc.data_ptr(), float(gamma),
-                                                          Wd.data_ptr(), nfft, bin0, m_local,
-                                                          G.data_ptr(), P, H.data_ptr(), P, _stream()), "sos_response_rc")
-        elif geq is not None:
-            xc, kind, consts = geq
-            _lib.check(_lib.lib().fl_geq_response_rc_c64(xc.data_ptr(), kind, S, consts.data_ptr(), b.data_ptr(), a.data_ptr(), No, Nmid, Ni,
-                                                         Wc.data_ptr(), float(gamma), Wd.data_ptr(), nfft,
-                                                         bin0, m_local, G.data_ptr(), P, H.data_ptr(), P,
-                                                         int(bool(float_eval and FLOAT_CASCADE_EVAL)), _stream()), "geq_response_rc")
+            fn, name = (L.fl_geq_response_rc_c128 if f64 else L.fl_geq_response_rc_c64), "geq_response_rc"
+            args = (xc.data_ptr(), kind, S, consts.data_ptr(), b.data_ptr(), a.data_ptr())
         else:
-            _lib.check(_lib.lib().fl_sos_response_rc_c64(b.data_ptr(), a.data_ptr(), S, No, Nmid, Ni, Wc.data_ptr(), float(gamma),
-                                                         Wd.data_ptr(), nfft, bin0, m_local,
-                                                         G.data_ptr(), P, H.data_ptr(), P, int(bool(float_eval and FLOAT_CASCADE_EVAL)),
-                                                         _stream()), "sos_response_rc")
+            fn, name = (L.fl_sos_response_rc_c128 if f64 else L.fl_sos_response_rc_c64), "sos_response_rc"
+            args = (b.data_ptr(), a.data_ptr(), S)
+        args += (No, Nmid, Ni, Wc.data_ptr(), cfg.gamma, Wd.data_ptr(), nfft, cfg.bin0, cfg.m_local, G.data_ptr(), P, H.data_ptr(), P)
+        if not f64:      # the all-double entry points have no float evaluation to choose
+            args += (int(bool(float_eval and FLOAT_CASCADE_EVAL)),)
+        _lib.check(fn(*args, _stream()), name)
     if getattr(_lib._pair, "stream_of", None) is not None and _lib.lib(pair_ok=True).fl_launch_pair_pending():
         # recorded, not issued: it rides in the input's column pass
         _pair_keep((b, a, Wc, Wd, G, H) + ((geq[0], geq[2]) if geq is not None else ()))
         if kernel_timer.enabled:
             kernel_timer.drop_last("sos_response_rc")
-    return H.movedim(-1, 0), G, (float(gamma), nfft, S, No * Nmid, bin0, m_local, real)
+    return H.movedim(-1, 0), G, cfg
 
 
 def _cascade_rc_backward(gH, G, b, a, Wr, cfg):
     """-> (part: float64 (nblk, 2, 3, S, C), partW: (nblk, No, Nmid, Ni) in the response's real dtype)"""
-    gamma, nfft, S, C_, bin0, m_local, real = cfg
+    real = cfg.real
     No, Nmid = G.shape[0], G.shape[1]
     Ni = Wr.shape[1]
-    if m_local == 0:      # an empty bin shard: no bin contributes
-        return (torch.zeros((1, 2, 3, S, C_), dtype=torch.float64, device=b.device),
-                torch.zeros((1, No, Nmid, Ni), dtype=real, device=b.device))
+    if cfg.m_local == 0:
+        return _zero_part(cfg, b.device), torch.zeros((1, No, Nmid, Ni), dtype=real, device=b.device)
     g = _h_planar(gH.resolve_conj(), True)
     L = _lib.lib()
-    nblk = L.fl_sos_bwd_blocks(m_local, C_, S, 0 if real == torch.float64 else 1)
-    part = torch.empty((nblk, 2, 3, S, C_), dtype=torch.float64, device=b.device)
+    nblk = L.fl_sos_bwd_blocks(cfg.m_local, cfg.C, cfg.S, 0 if real == torch.float64 else 1)
+    part = torch.empty((nblk, 2, 3, cfg.S, cfg.C), dtype=torch.float64, device=b.device)
     partW = torch.empty((nblk, No, Nmid, Ni), dtype=real, device=b.device)
     Wc = Wr.contiguous()
     fn = L.fl_sos_response_bwd_rc_c128 if real == torch.float64 else L.fl_sos_response_bwd_rc_c64
     with kernel_timer.span("sos_response_bwd_rc"):
-        _lib.check(fn(g.data_ptr(), _lead_pitch(g.movedim(0, -1)), G.data_ptr(), _pitch(m_local),
-                                                b.data_ptr(), a.data_ptr(), S, No, Nmid, Ni, Wc.data_ptr(), gamma,
-                                                twiddles(nfft, torch.float64, b.device).data_ptr(), nfft, bin0, m_local,
-                                                part.data_ptr(), partW.data_ptr(), _stream()), "sos_response_bwd_rc")
+        _lib.check(fn(g.data_ptr(), _lead_pitch(g.movedim(0, -1)), G.data_ptr(), _pitch(cfg.m_local),
+                      b.data_ptr(), a.data_ptr(), cfg.S, No, Nmid, Ni, Wc.data_ptr(), cfg.gamma,
+                      twiddles(cfg.nfft, torch.float64, b.device).data_ptr(), cfg.nfft, cfg.bin0, cfg.m_local,
+                      part.data_ptr(), partW.data_ptr(), _stream()), "sos_response_bwd_rc")
     return part, partW
 
 
@@ -2442,13 +2474,12 @@ LANES_F64_ROW_MAJOR_RC = False
 
 def _geq_lanes_blocks(cfg, ppr: int, niw: int, mode: int) -> int:
     """bin blocks of the lanes-per-section backward (csrc/cascade2.hip) for this shape, 0 when it does not take it"""
-    gamma, nfft, S, C_, bin0, m_local, real = cfg
     if not SOS_BWD_MIXED:
         return 0
-    if real == torch.float64 and mode == 1 and bin0 < 0 and not LANES_F64_ROW_MAJOR_RC:
+    if cfg.real == torch.float64 and mode == 1 and cfg.bin0 < 0 and not LANES_F64_ROW_MAJOR_RC:
         return 0
-    fn = _lib.lib().fl_geq_bwd_lanes_blocks if real == torch.float32 else _lib.lib().fl_geq_bwd_lanes_blocks_f64
-    return int(fn(m_local, C_, S, nfft, bin0, int(ppr), int(niw), int(mode)))
+    fn = _lib.lib().fl_geq_bwd_lanes_blocks if cfg.real == torch.float32 else _lib.lib().fl_geq_bwd_lanes_blocks_f64
+    return int(fn(cfg.m_local, cfg.C, cfg.S, cfg.nfft, cfg.bin0, int(ppr), int(niw), int(mode)))
 
 
 def _geq_backward_lanes(mode, gH, G, b, a, Wr, cfg, No, Nmid, Ni, nbx, xc, consts, sig):
@@ -2481,79 +2512,37 @@ def _geq_backward_lanes(mode, gH, G, b, a, Wr, cfg, No, Nmid, Ni, nbx, xc, const
     return out, gW
 
 
-class _SosRC(torch.autograd.Function):
-    """sos_response(b, a) @ Wr with the composition's backward folded into the cascade's backward kernel"""
+class _CascadeRC(torch.autograd.Function):
+    """response @ Wr with the composition's backward folded into the cascade's backward kernel: (design +) cascade + product
+    in one launch forward; cascade backward (+ design backward, which also sums the constant factor's partials)."""
 
     @staticmethod
-    def forward(ctx, b, a, Wr, gamma, nfft, real):
-        _require_gpu(b, a, Wr)
-        if b.shape != a.shape or b.shape[0] != 3 or b.dim() != 4:
-            raise ValueError("sos_response_rc: b and a must both be (3, n_sections, N_out, N_mid)")
-        bc, ac = b.contiguous(), a.contiguous()
-        H, G, ctx.cfg = _cascade_rc_forward(bc, ac, Wr, gamma, nfft, real,
-                                            not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]))
-        ctx.save_for_backward(bc, ac, G, Wr)
+    def forward(ctx, design, p, q, Wr, gamma, nfft, real):
+        _require_gpu(p, q, Wr)
+        ctx.design = design
+        # a graphic equaliser's sections are designed in the response kernel's prologue (and written to b, a for the backward pass)
+        sec, geq = design.sections(p, q, "_rc", prologue=True)
+        H, G, ctx.cfg = _cascade_rc_forward(*sec[2:], Wr, gamma, nfft, real, design.float_eval(ctx), geq=geq)
+        ctx.save_for_backward(*sec, G, Wr)
         return H
 
     @staticmethod
     def backward(ctx, gH):
-        bc, ac, G, Wr = ctx.saved_tensors
-        part, partW = _cascade_rc_backward(gH, G, bc, ac, Wr, ctx.cfg)
-        tot = part.sum(dim=0)
-        return tot[0].view(bc.shape), tot[1].view(ac.shape), partW.sum(dim=(0, 1)).to(Wr.dtype), None, None, None
-
-
-class _GeqCascadeRC(torch.autograd.Function):
-    """geq_cascade(x) @ Wr: design + cascade + product forward; cascade backward (with the composition folded in) +
-    design backward."""
-
-    @staticmethod
-    def forward(ctx, x, consts, Wr, gamma, nfft, real, sig=False):
-        dev = _require_gpu(x, consts, Wr)
-        ctx.sig = bool(sig)
-        xc = x.contiguous()
-        nb = xc.shape[0]
-        chan = tuple(xc.shape[1:])
-        C_ = max(_prod(chan), 1)
-        b = torch.empty((3, nb, *chan), dtype=torch.float64, device=dev)
-        a = torch.empty_like(b)
-        # the sections are designed in the response kernel's prologue (and written to b, a for the backward pass)
-        H, G, ctx.cfg = _cascade_rc_forward(b, a, Wr, gamma, nfft, real, True, geq=(xc, _geq_in_kind(xc, True, sig), consts))
-        ctx.save_for_backward(xc, consts, b, a, G, Wr)
-        return H
-
-    @staticmethod
-    def backward(ctx, gH):
-        xc, consts, b, a, G, Wr = ctx.saved_tensors
-        nbx = _geq_lanes_blocks(ctx.cfg, G.shape[1], Wr.shape[1], 1)
-        if nbx > 0:
-            out, gW = _geq_backward_lanes(1, gH, G, b, a, Wr, ctx.cfg, G.shape[0], G.shape[1], Wr.shape[1], nbx, xc, consts, ctx.sig)
-            return out, None, gW, None, None, None, None
-        part, partW = _cascade_rc_backward(gH, G, b, a, Wr, ctx.cfg)
-        nblk = part.shape[0]
-        nb = xc.shape[0]
-        C_ = max(_prod(xc.shape[1:]), 1)
-        st = nb * C_
-        out = torch.empty_like(xc)
-        gW = torch.empty_like(Wr, memory_format=torch.contiguous_format)
-        esz = part.element_size()
-        # design backward (sums the bin-block partials) + the constant factor's partials, one launch
-        fn = _lib.lib().fl_geq_sections_bwd_w64 if partW.dtype == torch.float64 else _lib.lib().fl_geq_sections_bwd_w
-        _lib.check(fn(xc.data_ptr(), _geq_in_kind(xc, True, ctx.sig), part.data_ptr(),
-                      part.data_ptr() + 3 * st * esz, 6 * st, nblk, nb, C_, consts.data_ptr(),
-                      out.data_ptr(), partW.data_ptr(), partW.shape[0] * partW.shape[1],
-                      partW.shape[2] * partW.shape[3], gW.data_ptr(), _stream()), "geq_sections_bwd_w")
-        return out, None, gW, None, None, None, None
+        *sec, G, Wr = ctx.saved_tensors
+        g = ctx.design.lanes_grads(sec, gH, G, ctx.cfg, Wr)
+        if g is None:
+            g = ctx.design.param_grads(sec, *_cascade_rc_backward(gH, G, *sec[2:], Wr, ctx.cfg), Wr)
+        return (None, *g, None, None, None)
 
 
 def sos_response_rc(b, a, Wr, gamma: float, nfft: int, dtype=torch.float32) -> torch.Tensor:
     """sos_response(b, a) (M, N_out, N_mid) times the real constant matrix Wr (N_mid, N_in) on the right, per bin."""
-    return _SosRC.apply(b.to(torch.float64), a.to(torch.float64), Wr.to(dtype), float(gamma), int(nfft), dtype)
+    return RawSections("sos", b, a).response_rc(Wr, gamma, nfft, dtype)
 
 
 def geq_cascade_rc(x, consts, Wr, gamma: float, nfft: int, dtype=torch.float32, gain_map: str = "abs") -> torch.Tensor:
     """geq_cascade(x, ...) (M, N_out, N_mid) times the real constant matrix Wr (N_mid, N_in) on the right, per bin."""
-    return _GeqCascadeRC.apply(x, consts, Wr.to(dtype), float(gamma), int(nfft), dtype, _is_sigmoid(gain_map))
+    return GeqGains("geq", x, consts, gain_map).response_rc(Wr, gamma, nfft, dtype)
 
 
 def _is_sigmoid(gain_map: str) -> bool:
@@ -2567,7 +2556,7 @@ def geq_cascade(x: torch.Tensor, consts: torch.Tensor, gamma: float, nfft: int, 
     the default map 20 log10|x| -- same result as sos_response(*geq_sections(20 log10|x|)), with
     the map and its backward folded into the design kernels.  gain_map="sigmoid": the map 20 log10(sigmoid(x)) of the
     FDN attenuation filters (e8_fdn.py:97) folded the same way."""
-    return _GeqCascade.apply(x, consts, float(gamma), int(nfft), dtype, _is_sigmoid(gain_map))
+    return GeqGains("geq", x, consts, gain_map).response(gamma, nfft, dtype)
 
 
 def geq_sections(gain_db: torch.Tensor, consts: torch.Tensor):
@@ -2581,7 +2570,7 @@ def sos_response(b: torch.Tensor, a: torch.Tensor, gamma: float, nfft: int, dtyp
     coefficients b, a: (3, n_sections, ...) real (anti-alias radius gamma applied to the taps).
     The cascade is evaluated in float64 (coefficients are promoted); ``dtype`` (float32 |
     float64) selects the precision H is stored in."""
-    return _Sos.apply(b.to(torch.float64), a.to(torch.float64), float(gamma), int(nfft), dtype)
+    return RawSections("sos", b, a).response(gamma, nfft, dtype)
 
 
 # ----------------------------------------------------------------------------- scalar objective

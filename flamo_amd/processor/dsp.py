@@ -685,15 +685,13 @@ class _SOSMixin:
             return None
         spec = self._cascade_spec(param)
         # sections, cascades per output row, columns of the constant factor: the fused operator's kernel limits (LDS tables)
-        n_sections = spec[1].shape[0] if spec[0] == "geq" else spec[1].shape[1]
-        if not ops.cascade_rc_supported(self.dtype, Wr.shape[1], Wr.shape[0], n_sections):
+        if not ops.cascade_rc_supported(self.dtype, Wr.shape[1], Wr.shape[0], spec.n_sections):
             return None
-        if spec[0] == "geq":
-            return ops.geq_cascade_rc(spec[1], spec[2], Wr, self._gamma_f, self.nfft, dtype=self.dtype, gain_map=spec[3])
-        return ops.sos_response_rc(spec[1], spec[2], Wr, self._gamma_f, self.nfft, dtype=self.dtype)
+        return spec.response_rc(Wr, self._gamma_f, self.nfft, dtype=self.dtype)
 
     def _cascade_spec(self, param):
-        return ("sos", *self._sos_coeffs(self.map(param.double())))
+        """where this module's sections come from, as the cascade ops take it (ops.RawSections | ops.GeqGains)"""
+        return ops.RawSections("sos", *self._sos_coeffs(self.map(param.double())))
 
     # A full cascade applied to a signal with this many columns or fewer, outside a loop: the product and the response's
     # gradient go through ops.*_apply (dL/dH = gY (x) conj(X) formed inside the cascade backward; an (M, N_out, N_in)
@@ -716,11 +714,9 @@ class _SOSMixin:
                 or getattr(self, "_own_response", None) is not self.freq_response):
             return None
         spec = self._cascade_spec(param)
-        if spec[0] == "geq":
-            return ops.geq_cascade_apply(spec[1], spec[2], x, self._gamma_f, self.nfft, dtype=self.dtype, gain_map=spec[3])
-        if spec[1].dim() != 4:
+        if not spec.full:
             return None
-        return ops.sos_response_apply(spec[1], spec[2], x, self._gamma_f, self.nfft, dtype=self.dtype)
+        return spec.response_apply(x, self._gamma_f, self.nfft, dtype=self.dtype)
 
     def _sections_spectra(self, b, a):
         """B, A as the reference returns them from get_poly_coeff: rfft of the weighted taps."""
@@ -914,20 +910,16 @@ class GEQ(_SOSMixin, Filter):
 
     def get_freq_response(self):
         def response(param):
-            gm = self._folded_map()
-            if gm is not None and param.is_cuda and param.dtype in (torch.float32, torch.float64):
-                # default map: 10^(map(x)/20) = |x| (or sigmoid(x)), folded into the design kernel with its backward
-                return ops.geq_cascade(param, self._design.device_consts(param.device), self._gamma_f, self.nfft,
-                                       dtype=self.dtype, gain_map=gm)
-            return self._sos_to_response(*self._sos_coeffs(self.map(param.double())))
+            return self._cascade_spec(param).response(self._gamma_f, self.nfft, dtype=self.dtype)
         self.freq_response = response
         self._own_response = response
 
     def _cascade_spec(self, param):
         gm = self._folded_map()
         if gm is not None and param.is_cuda and param.dtype in (torch.float32, torch.float64):
-            return ("geq", param, self._design.device_consts(param.device), gm)
-        return ("sos", *self._sos_coeffs(self.map(param.double())))
+            # default map: 10^(map(x)/20) = |x| (or sigmoid(x)), folded into the design kernel with its backward
+            return ops.GeqGains("geq", param, self._design.device_consts(param.device), gm)
+        return super()._cascade_spec(param)
 
     def _sos_coeffs(self, gain_db):
         """command gains in dB -> float32 SOS (b, a) for every channel pair at once; the

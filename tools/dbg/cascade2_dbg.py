@@ -18,7 +18,7 @@ W = torch.randn(N, N, device=dev)
 S, C = 12, N * N
 M = nfft // 2 + 1
 spec = geq._cascade_spec(geq.param)
-xc, consts = spec[1].contiguous(), spec[2]
+xc, consts = spec.x.contiguous(), spec.consts
 b = torch.empty((3, S, N, N), dtype=torch.float64, device=dev)
 a = torch.empty_like(b)
 with ops.row_major_bins(nfft):
