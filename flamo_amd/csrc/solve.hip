@@ -1632,34 +1632,6 @@ long fl_solve_ws_bytes(int N, int M, int f64) {
     return f64 ? (long)solve_ws_slots<double>(N, M) * N * (N + 1) * (long)sizeof(cx<double>)
                : (long)solve_ws_slots<float>(N, M) * N * (N + 1) * (long)sizeof(cx<float>);
 }
-int fl_solve_ws_c64(const void* P, long p_pitch, int one_minus, int adjoint, const void* R, long rs_b, long rs_n, long rs_k, void* OUT,
-                    long os_b, long os_n, long os_k, int B, int M, int N, int K, void* ws, long ws_bytes, void* stream) {
-    Dud<float> none = {};
-    return solve_impl<float>(P, p_pitch, none, one_minus, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream, ws,
-                             ws_bytes > 0 ? (size_t)ws_bytes : 0);
-}
-int fl_solve_ws_c128(const void* P, long p_pitch, int one_minus, int adjoint, const void* R, long rs_b, long rs_n, long rs_k, void* OUT,
-                     long os_b, long os_n, long os_k, int B, int M, int N, int K, void* ws, long ws_bytes, void* stream) {
-    Dud<double> none = {};
-    return solve_impl<double>(P, p_pitch, none, one_minus, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream, ws,
-                              ws_bytes > 0 ? (size_t)ws_bytes : 0);
-}
-int fl_solve_c64(const void* P, long p_pitch, int one_minus, int adjoint, const void* R, long rs_b, long rs_n, long rs_k, void* OUT,
-                 long os_b, long os_n, long os_k, int B, int M, int N, int K, void* stream) {
-    Dud<float> none = {};
-    return solve_impl<float>(P, p_pitch, none, one_minus, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream);
-}
-int fl_solve_c128(const void* P, long p_pitch, int one_minus, int adjoint, const void* R, long rs_b, long rs_n, long rs_k, void* OUT,
-                  long os_b, long os_n, long os_k, int B, int M, int N, int K, void* stream) {
-    Dud<double> none = {};
-    return solve_impl<double>(P, p_pitch, none, one_minus, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream);
-}
-int fl_solve_scaled_c64(const void* P, long p_pitch, const void* l, long l_sn, int adjoint, const void* R, long rs_b, long rs_n,
-                        long rs_k, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, int K, void* stream) {
-    FL_REQUIRE(P && l, "solve_scaled: null pointer");
-    Dud<float> d = {(const cx<float>*)l, l_sn, 0, nullptr, nullptr, 0, 0};
-    return solve_impl<float>(P, p_pitch, d, 1, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream);
-}
 // elements of the kept-factor arrays for N channels and M bins (both tiled by the workgroup's bins: see Dud)
 static int kept_bpb(int N, bool f64) { return 256 / (N <= 4 ? 4 : N <= 8 ? 8 : N <= 16 ? 16 : N <= 32 ? 32 : 64); }
 size_t fl_solve_kept_lu_elems(int N, int M, int f64) {
@@ -1674,199 +1646,182 @@ size_t fl_solve_kept_piv_elems(int N, int M, int f64) {
 }
 // the FDN form, forward system, with w = A^-H cw^H beside OUT and cz (Dud::wadj): float32, 4 < N <= 16
 int fl_solve_fdn_wadj_supported(int N) { return (N > 4 && N <= 16 && g_solve_variant == 0 && g_solve_rpl2_16 != 1) ? 1 : 0; }
-int fl_solve_fdn_wadj_c64(const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U, const void* r,
-                          long r_sn, long r_sf, const void* rv, int rv_real, const void* rs, long rs_sb, const void* cw, int cw_real,
-                          void* cz, long cz_sb, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, void* wadj, long wadj_sn,
-                          void* stream) {
-    FL_REQUIRE(U && l2 && rv && rs && cw && wadj, "solve_fdn_wadj: null pointer");
-    FL_REQUIRE(fl_solve_fdn_wadj_supported(N), "solve_fdn_wadj: 4 < N <= 16 on the default kernels (fl_solve_fdn_wadj_supported)");
-    Dud<float> d = {(const cx<float>*)l, l_sn, l_sf, (const cx<float>*)U, (const cx<float>*)r, r_sn, r_sf,
-                    (const cx<float>*)l2, l2_sn, l2_sf, 1, rv, (const cx<float>*)rs, rs_sb, cw, (cx<float>*)cz, cz_sb, rv_real, cw_real};
-    d.wadj = (cx<float>*)wadj; d.wadj_sn = wadj_sn;
-    return solve_impl<float>(nullptr, 0, d, 1, 0, nullptr, 0, 0, 0, OUT, os_b, os_n, os_k, B, M, N, 1, stream);
-}
-int fl_solve_fdn_wadj_c128(const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U, const void* r,
-                           long r_sn, long r_sf, const void* rv, int rv_real, const void* rs, long rs_sb, const void* cw, int cw_real,
-                           void* cz, long cz_sb, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, void* wadj, long wadj_sn,
-                           void* stream) {
-    FL_REQUIRE(U && l2 && rv && rs && cw && wadj, "solve_fdn_wadj: null pointer");
-    FL_REQUIRE(fl_solve_fdn_wadj_supported(N), "solve_fdn_wadj: 4 < N <= 16 on the default kernels (fl_solve_fdn_wadj_supported)");
-    Dud<double> d = {(const cx<double>*)l, l_sn, l_sf, (const cx<double>*)U, (const cx<double>*)r, r_sn, r_sf,
-                     (const cx<double>*)l2, l2_sn, l2_sf, 1, rv, (const cx<double>*)rs, rs_sb, cw, (cx<double>*)cz, cz_sb, rv_real, cw_real};
-    d.wadj = (cx<double>*)wadj; d.wadj_sn = wadj_sn;
-    return solve_impl<double>(nullptr, 0, d, 1, 0, nullptr, 0, 0, 0, OUT, os_b, os_n, os_k, B, M, N, 1, stream);
-}
-int fl_solve_dud2_grads_w_c128(const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U, const void* r,
-                               long r_sn, long r_sf, const void* W, long w_sn, const void* gy, long gy_sb, const void* OUT, long s_b,
-                               long s_n, long s_k, int B, int M, int N, void* gl, long gl_sn, void* gr, long gr_sn, void* partU,
-                               void* gU, void* gR0, const void* sx, long sx_b, const void* sy, long sy_b, void* g_side_real,
-                               void* stream) {
-    FL_REQUIRE(l2 && W && gy, "solve_dud2_grads_w: null pointer");
-    FL_REQUIRE((sx == nullptr) == (sy == nullptr) && (!sx || (partU && gU)), "solve_dud2_grads_w: side reductions need sx, sy and the partial buffers");
-    Dud<double> d = {(const cx<double>*)l, l_sn, l_sf, (const cx<double>*)U, (const cx<double>*)r, r_sn, r_sf,
-                     (const cx<double>*)l2, l2_sn, l2_sf, 0};
-    d.wadj = (cx<double>*)const_cast<void*>(W); d.wadj_sn = w_sn; d.wgy = (const cx<double>*)gy; d.wgy_sb = gy_sb;
-    DudSide<double> side = {(const cx<double>*)sx, (const cx<double>*)sy, sx_b, sy_b, sx ? 1 : 0, (double*)g_side_real};
-    return dud_grads_impl<double>(d, nullptr, OUT, s_b, s_n, s_k, B, M, N, 1, gl, gl_sn, gr, gr_sn, partU, gU, stream, gR0, side);
-}
 // the FDN form (fl_solve_fdn_*) with kept factors: 8 < N <= 16 on the two-rows-per-lane kernel (its workgroup's 32 bins are a tile)
 int fl_solve_fdn_keep_tile(int N, int f64) {
     (void)f64;
     return (N > 8 && N <= 16 && g_solve_variant == 0 && g_solve_rpl2_16 != 1) ? 32 : 0;
 }
-int fl_solve_fdn_keep_c64(const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U, const void* r,
-                          long r_sn, long r_sf, const void* rv, int rv_real, const void* rs, long rs_sb, const void* cw, int cw_real,
-                          void* cz, long cz_sb, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, void* LU, void* piv,
-                          void* stream) {
-    FL_REQUIRE(U && l2 && rv && rs && (!cz || cw) && LU && piv, "solve_fdn_keep: null pointer");
-    FL_REQUIRE(fl_solve_fdn_keep_tile(N, 0) > 0, "solve_fdn_keep: 8 < N <= 16 on the default kernels (fl_solve_fdn_keep_tile)");
-    Dud<float> d = {(const cx<float>*)l, l_sn, l_sf, (const cx<float>*)U, (const cx<float>*)r, r_sn, r_sf,
-                    (const cx<float>*)l2, l2_sn, l2_sf, 1, rv, (const cx<float>*)rs, rs_sb, cw, (cx<float>*)cz, cz_sb, rv_real, cw_real};
-    d.lu_out = (cx<float>*)LU; d.piv_out = (int*)piv;
-    return solve_impl<float>(nullptr, 0, d, 1, 0, nullptr, 0, 0, 0, OUT, os_b, os_n, os_k, B, M, N, 1, stream);
+int fl_solve_dud_grads_blocks(int M, int N) { return dud_grads_blocks(M, N); }
 }
-int fl_solve_fdn_keep_c128(const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U, const void* r,
-                           long r_sn, long r_sf, const void* rv, int rv_real, const void* rs, long rs_sb, const void* cw, int cw_real,
-                           void* cz, long cz_sb, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, void* LU, void* piv,
-                           void* stream) {
-    FL_REQUIRE(U && l2 && rv && rs && (!cz || cw) && LU && piv, "solve_fdn_keep: null pointer");
-    FL_REQUIRE(fl_solve_fdn_keep_tile(N, 1) > 0, "solve_fdn_keep: 8 < N <= 16 on the default kernels (fl_solve_fdn_keep_tile)");
-    Dud<double> d = {(const cx<double>*)l, l_sn, l_sf, (const cx<double>*)U, (const cx<double>*)r, r_sn, r_sf,
-                     (const cx<double>*)l2, l2_sn, l2_sf, 1, rv, (const cx<double>*)rs, rs_sb, cw, (cx<double>*)cz, cz_sb, rv_real, cw_real};
-    d.lu_out = (cx<double>*)LU; d.piv_out = (int*)piv;
-    return solve_impl<double>(nullptr, 0, d, 1, 0, nullptr, 0, 0, 0, OUT, os_b, os_n, os_k, B, M, N, 1, stream);
+
+// The code object lists the kernels in the order in which their dispatchers are first instantiated.  That order is pinned here,
+// ahead of the entries, to the one the code object has always had: rearranging the entries below cannot move a kernel, so a
+// host-side change leaves the device code byte-identical (which is how such a change is checked).
+static void pin_kernel_order() {
+    (void)&solve_impl<float>, (void)&solve_impl<double>, (void)&dud_grads_impl<double>;
+    (void)&solve_kept_adjoint_impl<float>, (void)&solve_kept_adjoint_impl<double>;
+    (void)&solve_scaled_keep_impl<float>, (void)&solve_scaled_keep_impl<double>, (void)&dud_grads_impl<float>;
+}
+
+// ---------------------------------------------------------------- the entries that exist in both precisions
+// FL_SOLVE_ENTRY(name, (parameters), (arguments)) { body } writes such an entry ONCE: the body becomes
+// template <class T> static int name_entry(parameters), and the exported symbols name_c64 / name_c128 (declared in
+// include/flamo_hip.h: a parameter list that differs from the declaration does not compile) are one-line forwards to
+// name_entry<float> / name_entry<double>.
+#define FL_SOLVE_ENTRY(NAME, PARAMS, ARGS)                                                \
+    template <class T> static int NAME##_entry PARAMS;                                    \
+    extern "C" int NAME##_c64 PARAMS { return NAME##_entry<float> ARGS; }                 \
+    extern "C" int NAME##_c128 PARAMS { return NAME##_entry<double> ARGS; }               \
+    template <class T> static int NAME##_entry PARAMS
+
+// The factored loop A_f = I - diag(l (.) l2) U diag(r) as the kernels take it; every member this does not name stays zero.
+// l2: the second left factor of the fl_solve_dud2_* / fl_solve_fdn_* entries (nullptr: none); rhs_l2: the right-hand side is
+// l2 (.) R as well (forward system)
+template <class T>
+static Dud<T> dud_of(const void* l, long l_sn, long l_sf, const void* U, const void* r, long r_sn, long r_sf, const void* l2 = nullptr,
+                     long l2_sn = 0, long l2_sf = 0, int rhs_l2 = 0) {
+    Dud<T> d = {(const cx<T>*)l, l_sn, l_sf, (const cx<T>*)U, (const cx<T>*)r, r_sn, r_sf, (const cx<T>*)l2, l2_sn, l2_sf, rhs_l2};
+    return d;
+}
+// ... with the rank-one right-hand side rv rs and the contracted output cz = cw . OUT of the FDN form (fl_solve_fdn_*)
+template <class T>
+static Dud<T> dud_fdn(const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U, const void* r, long r_sn,
+                      long r_sf, int rhs_l2, const void* rv, int rv_real, const void* rs, long rs_sb, const void* cw, int cw_real,
+                      void* cz, long cz_sb) {
+    Dud<T> d = dud_of<T>(l, l_sn, l_sf, U, r, r_sn, r_sf, l2, l2_sn, l2_sf, rhs_l2);
+    d.rv = rv; d.rs = (const cx<T>*)rs; d.rs_sb = rs_sb; d.rv_real = rv_real;
+    d.cw = cw; d.cz = (cx<T>*)cz; d.cz_sb = cz_sb; d.cw_real = cw_real;
+    return d;
+}
+// the side reductions of the gradient pass (DudSide): on when sx is given
+template <class T>
+static DudSide<T> dud_side(const void* sx, long sx_b, const void* sy, long sy_b, void* g_side_real) {
+    return DudSide<T>{(const cx<T>*)sx, (const cx<T>*)sy, sx_b, sy_b, sx ? 1 : 0, (T*)g_side_real};
+}
+
+FL_SOLVE_ENTRY(fl_solve_ws, (const void* P, long p_pitch, int one_minus, int adjoint, const void* R, long rs_b, long rs_n, long rs_k,
+                             void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, int K, void* ws, long ws_bytes, void* stream),
+               (P, p_pitch, one_minus, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, ws, ws_bytes, stream)) {
+    return solve_impl<T>(P, p_pitch, Dud<T>{}, one_minus, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream, ws,
+                         ws_bytes > 0 ? (size_t)ws_bytes : 0);
+}
+FL_SOLVE_ENTRY(fl_solve, (const void* P, long p_pitch, int one_minus, int adjoint, const void* R, long rs_b, long rs_n, long rs_k, void* OUT,
+                          long os_b, long os_n, long os_k, int B, int M, int N, int K, void* stream),
+               (P, p_pitch, one_minus, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream)) {
+    return solve_impl<T>(P, p_pitch, Dud<T>{}, one_minus, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream);
+}
+FL_SOLVE_ENTRY(fl_solve_scaled, (const void* P, long p_pitch, const void* l, long l_sn, int adjoint, const void* R, long rs_b, long rs_n,
+                                 long rs_k, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, int K, void* stream),
+               (P, p_pitch, l, l_sn, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream)) {
+    FL_REQUIRE(P && l, "solve_scaled: null pointer");
+    return solve_impl<T>(P, p_pitch, dud_of<T>(l, l_sn, 0, nullptr, nullptr, 0, 0), 1, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k,
+                         B, M, N, K, stream);
+}
+FL_SOLVE_ENTRY(fl_solve_scaled_keep, (const void* P, long p_pitch, const void* l, long l_sn, const void* R, long rs_b, long rs_n, long rs_k,
+                                      void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, int K, void* LU, void* piv,
+                                      void* stream),
+               (P, p_pitch, l, l_sn, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, LU, piv, stream)) {
+    return solve_scaled_keep_impl<T>(P, p_pitch, l, l_sn, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, LU, piv, stream);
+}
+FL_SOLVE_ENTRY(fl_solve_kept_adjoint, (const void* LU, const void* piv, const void* R, long rs_b, long rs_n, long rs_k, void* OUT, long os_b,
+                                       long os_n, long os_k, int B, int M, int N, int K, void* stream),
+               (LU, piv, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream)) {
+    return solve_kept_adjoint_impl<T>(LU, piv, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream);
 }
 // A^-H (conj(rv) . rs) from factors kept by fl_solve_fdn_keep_* (tile_bins = fl_solve_fdn_keep_tile)
-int fl_solve_kept_adjoint_rank1_c64(const void* LU, const void* piv, int tile_bins, const void* rv, int rv_real, const void* rs, long rs_sb,
-                                    void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, void* stream) {
+FL_SOLVE_ENTRY(fl_solve_kept_adjoint_rank1, (const void* LU, const void* piv, int tile_bins, const void* rv, int rv_real, const void* rs,
+                                             long rs_sb, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, void* stream),
+               (LU, piv, tile_bins, rv, rv_real, rs, rs_sb, OUT, os_b, os_n, os_k, B, M, N, stream)) {
     FL_REQUIRE(rv && rs && tile_bins > 0, "solve_kept_adjoint_rank1: null pointer / tile");
-    return solve_kept_adjoint_impl<float>(LU, piv, nullptr, 0, 0, 0, OUT, os_b, os_n, os_k, B, M, N, 1, stream, tile_bins, rv, rv_real, rs, rs_sb);
+    return solve_kept_adjoint_impl<T>(LU, piv, nullptr, 0, 0, 0, OUT, os_b, os_n, os_k, B, M, N, 1, stream, tile_bins, rv, rv_real, rs, rs_sb);
 }
-int fl_solve_kept_adjoint_rank1_c128(const void* LU, const void* piv, int tile_bins, const void* rv, int rv_real, const void* rs, long rs_sb,
-                                     void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, void* stream) {
-    FL_REQUIRE(rv && rs && tile_bins > 0, "solve_kept_adjoint_rank1: null pointer / tile");
-    return solve_kept_adjoint_impl<double>(LU, piv, nullptr, 0, 0, 0, OUT, os_b, os_n, os_k, B, M, N, 1, stream, tile_bins, rv, rv_real, rs, rs_sb);
-}
-int fl_solve_scaled_keep_c64(const void* P, long p_pitch, const void* l, long l_sn, const void* R, long rs_b, long rs_n, long rs_k, void* OUT,
-                             long os_b, long os_n, long os_k, int B, int M, int N, int K, void* LU, void* piv, void* stream) {
-    return solve_scaled_keep_impl<float>(P, p_pitch, l, l_sn, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, LU, piv, stream);
-}
-int fl_solve_scaled_keep_c128(const void* P, long p_pitch, const void* l, long l_sn, const void* R, long rs_b, long rs_n, long rs_k, void* OUT,
-                              long os_b, long os_n, long os_k, int B, int M, int N, int K, void* LU, void* piv, void* stream) {
-    return solve_scaled_keep_impl<double>(P, p_pitch, l, l_sn, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, LU, piv, stream);
-}
-int fl_solve_kept_adjoint_c64(const void* LU, const void* piv, const void* R, long rs_b, long rs_n, long rs_k,
-                              void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, int K, void* stream) {
-    return solve_kept_adjoint_impl<float>(LU, piv, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream);
-}
-int fl_solve_kept_adjoint_c128(const void* LU, const void* piv, const void* R, long rs_b, long rs_n, long rs_k,
-                               void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, int K, void* stream) {
-    return solve_kept_adjoint_impl<double>(LU, piv, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream);
-}
-int fl_solve_scaled_c128(const void* P, long p_pitch, const void* l, long l_sn, int adjoint, const void* R, long rs_b, long rs_n,
-                         long rs_k, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, int K, void* stream) {
-    FL_REQUIRE(P && l, "solve_scaled: null pointer");
-    Dud<double> d = {(const cx<double>*)l, l_sn, 0, nullptr, nullptr, 0, 0};
-    return solve_impl<double>(P, p_pitch, d, 1, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream);
-}
-int fl_solve_dud_c64(const void* l, long l_sn, long l_sf, const void* U, const void* r, long r_sn, long r_sf, int adjoint,
-                     const void* R, long rs_b, long rs_n, long rs_k, void* OUT, long os_b, long os_n, long os_k,
-                     int B, int M, int N, int K, void* stream) {
+FL_SOLVE_ENTRY(fl_solve_dud, (const void* l, long l_sn, long l_sf, const void* U, const void* r, long r_sn, long r_sf, int adjoint,
+                              const void* R, long rs_b, long rs_n, long rs_k, void* OUT, long os_b, long os_n, long os_k, int B, int M,
+                              int N, int K, void* stream),
+               (l, l_sn, l_sf, U, r, r_sn, r_sf, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream)) {
     FL_REQUIRE(U, "solve_dud: null mixing matrix");
-    Dud<float> d = {(const cx<float>*)l, l_sn, l_sf, (const cx<float>*)U, (const cx<float>*)r, r_sn, r_sf};
-    return solve_impl<float>(nullptr, 0, d, 1, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream);
+    return solve_impl<T>(nullptr, 0, dud_of<T>(l, l_sn, l_sf, U, r, r_sn, r_sf), 1, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B,
+                         M, N, K, stream);
 }
-int fl_solve_dud_c128(const void* l, long l_sn, long l_sf, const void* U, const void* r, long r_sn, long r_sf, int adjoint,
-                      const void* R, long rs_b, long rs_n, long rs_k, void* OUT, long os_b, long os_n, long os_k,
-                      int B, int M, int N, int K, void* stream) {
-    FL_REQUIRE(U, "solve_dud: null mixing matrix");
-    Dud<double> d = {(const cx<double>*)l, l_sn, l_sf, (const cx<double>*)U, (const cx<double>*)r, r_sn, r_sf};
-    return solve_impl<double>(nullptr, 0, d, 1, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream);
-}
-int fl_solve_dud_grads_blocks(int M, int N) { return dud_grads_blocks(M, N); }
-int fl_solve_dud_grads_c64(const void* l, long l_sn, long l_sf, const void* U, const void* r, long r_sn, long r_sf, const void* gR,
-                           const void* OUT, long s_b, long s_n, long s_k, int B, int M, int N, int K, void* gl, long gl_sn, void* gr,
-                           long gr_sn, void* partU, void* gU, void* stream) {
-    Dud<float> d = {(const cx<float>*)l, l_sn, l_sf, (const cx<float>*)U, (const cx<float>*)r, r_sn, r_sf};
-    return dud_grads_impl<float>(d, gR, OUT, s_b, s_n, s_k, B, M, N, K, gl, gl_sn, gr, gr_sn, partU, gU, stream);
-}
-int fl_solve_dud_grads_c128(const void* l, long l_sn, long l_sf, const void* U, const void* r, long r_sn, long r_sf, const void* gR,
-                            const void* OUT, long s_b, long s_n, long s_k, int B, int M, int N, int K, void* gl, long gl_sn, void* gr,
-                            long gr_sn, void* partU, void* gU, void* stream) {
-    Dud<double> d = {(const cx<double>*)l, l_sn, l_sf, (const cx<double>*)U, (const cx<double>*)r, r_sn, r_sf};
-    return dud_grads_impl<double>(d, gR, OUT, s_b, s_n, s_k, B, M, N, K, gl, gl_sn, gr, gr_sn, partU, gU, stream);
+FL_SOLVE_ENTRY(fl_solve_dud_grads, (const void* l, long l_sn, long l_sf, const void* U, const void* r, long r_sn, long r_sf, const void* gR,
+                                    const void* OUT, long s_b, long s_n, long s_k, int B, int M, int N, int K, void* gl, long gl_sn,
+                                    void* gr, long gr_sn, void* partU, void* gU, void* stream),
+               (l, l_sn, l_sf, U, r, r_sn, r_sf, gR, OUT, s_b, s_n, s_k, B, M, N, K, gl, gl_sn, gr, gr_sn, partU, gU, stream)) {
+    return dud_grads_impl<T>(dud_of<T>(l, l_sn, l_sf, U, r, r_sn, r_sf), gR, OUT, s_b, s_n, s_k, B, M, N, K, gl, gl_sn, gr, gr_sn, partU,
+                             gU, stream);
 }
 /* two left factors: A_f = I - diag(l (.) l2) U diag(r); rhs_l2: the right-hand side is l2 (.) R (forward system) */
-int fl_solve_dud2_c64(const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, int rhs_l2, const void* U,
-                      const void* r, long r_sn, long r_sf, int adjoint, const void* R, long rs_b, long rs_n, long rs_k, void* OUT,
-                      long os_b, long os_n, long os_k, int B, int M, int N, int K, void* stream) {
+FL_SOLVE_ENTRY(fl_solve_dud2, (const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, int rhs_l2, const void* U,
+                               const void* r, long r_sn, long r_sf, int adjoint, const void* R, long rs_b, long rs_n, long rs_k,
+                               void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, int K, void* stream),
+               (l, l_sn, l_sf, l2, l2_sn, l2_sf, rhs_l2, U, r, r_sn, r_sf, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K,
+                stream)) {
     FL_REQUIRE(U && l2, "solve_dud2: null pointer");
-    Dud<float> d = {(const cx<float>*)l, l_sn, l_sf, (const cx<float>*)U, (const cx<float>*)r, r_sn, r_sf,
-                    (const cx<float>*)l2, l2_sn, l2_sf, rhs_l2};
-    return solve_impl<float>(nullptr, 0, d, 1, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream);
+    return solve_impl<T>(nullptr, 0, dud_of<T>(l, l_sn, l_sf, U, r, r_sn, r_sf, l2, l2_sn, l2_sf, rhs_l2), 1, adjoint, R, rs_b, rs_n, rs_k,
+                         OUT, os_b, os_n, os_k, B, M, N, K, stream);
 }
-int fl_solve_dud2_c128(const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, int rhs_l2, const void* U,
-                       const void* r, long r_sn, long r_sf, int adjoint, const void* R, long rs_b, long rs_n, long rs_k, void* OUT,
-                       long os_b, long os_n, long os_k, int B, int M, int N, int K, void* stream) {
-    FL_REQUIRE(U && l2, "solve_dud2: null pointer");
-    Dud<double> d = {(const cx<double>*)l, l_sn, l_sf, (const cx<double>*)U, (const cx<double>*)r, r_sn, r_sf,
-                     (const cx<double>*)l2, l2_sn, l2_sf, rhs_l2};
-    return solve_impl<double>(nullptr, 0, d, 1, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream);
-}
-int fl_solve_dud2_grads_c64(const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U, const void* r,
-                            long r_sn, long r_sf, const void* gR, const void* OUT, long s_b, long s_n, long s_k, int B, int M, int N,
-                            int K, void* gl, long gl_sn, void* gr, long gr_sn, void* partU, void* gU, void* gR0, const void* sx,
-                            long sx_b, const void* sy, long sy_b, void* g_side_real, void* stream) {
+FL_SOLVE_ENTRY(fl_solve_dud2_grads, (const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U,
+                                     const void* r, long r_sn, long r_sf, const void* gR, const void* OUT, long s_b, long s_n, long s_k,
+                                     int B, int M, int N, int K, void* gl, long gl_sn, void* gr, long gr_sn, void* partU, void* gU,
+                                     void* gR0, const void* sx, long sx_b, const void* sy, long sy_b, void* g_side_real, void* stream),
+               (l, l_sn, l_sf, l2, l2_sn, l2_sf, U, r, r_sn, r_sf, gR, OUT, s_b, s_n, s_k, B, M, N, K, gl, gl_sn, gr, gr_sn, partU, gU, gR0,
+                sx, sx_b, sy, sy_b, g_side_real, stream)) {
     FL_REQUIRE(l2, "solve_dud2_grads: null pointer");
     FL_REQUIRE((sx == nullptr) == (sy == nullptr) && (!sx || (K == 1 && partU && gU)), "solve_dud2_grads: side reductions need sx, sy, one column per batch item and the partial buffers");
-    Dud<float> d = {(const cx<float>*)l, l_sn, l_sf, (const cx<float>*)U, (const cx<float>*)r, r_sn, r_sf,
-                    (const cx<float>*)l2, l2_sn, l2_sf, 0};
-    DudSide<float> side = {(const cx<float>*)sx, (const cx<float>*)sy, sx_b, sy_b, sx ? 1 : 0, (float*)g_side_real};
-    return dud_grads_impl<float>(d, gR, OUT, s_b, s_n, s_k, B, M, N, K, gl, gl_sn, gr, gr_sn, partU, gU, stream, gR0, side);
-}
-int fl_solve_dud2_grads_c128(const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U, const void* r,
-                             long r_sn, long r_sf, const void* gR, const void* OUT, long s_b, long s_n, long s_k, int B, int M, int N,
-                             int K, void* gl, long gl_sn, void* gr, long gr_sn, void* partU, void* gU, void* gR0, const void* sx,
-                             long sx_b, const void* sy, long sy_b, void* g_side_real, void* stream) {
-    FL_REQUIRE(l2, "solve_dud2_grads: null pointer");
-    FL_REQUIRE((sx == nullptr) == (sy == nullptr) && (!sx || (K == 1 && partU && gU)), "solve_dud2_grads: side reductions need sx, sy, one column per batch item and the partial buffers");
-    Dud<double> d = {(const cx<double>*)l, l_sn, l_sf, (const cx<double>*)U, (const cx<double>*)r, r_sn, r_sf,
-                     (const cx<double>*)l2, l2_sn, l2_sf, 0};
-    DudSide<double> side = {(const cx<double>*)sx, (const cx<double>*)sy, sx_b, sy_b, sx ? 1 : 0, (double*)g_side_real};
-    return dud_grads_impl<double>(d, gR, OUT, s_b, s_n, s_k, B, M, N, K, gl, gl_sn, gr, gr_sn, partU, gU, stream, gR0, side);
+    return dud_grads_impl<T>(dud_of<T>(l, l_sn, l_sf, U, r, r_sn, r_sf, l2, l2_sn, l2_sf, 0), gR, OUT, s_b, s_n, s_k, B, M, N, K, gl, gl_sn,
+                             gr, gr_sn, partU, gU, stream, gR0, dud_side<T>(sx, sx_b, sy, sy_b, g_side_real));
 }
 // the same with the adjoint solution given as gR[b][n][f] = W[n][f] gy[b][f] (W from fl_solve_fdn_wadj_c64), formed in the kernel
-int fl_solve_dud2_grads_w_c64(const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U, const void* r,
-                              long r_sn, long r_sf, const void* W, long w_sn, const void* gy, long gy_sb, const void* OUT, long s_b,
-                              long s_n, long s_k, int B, int M, int N, void* gl, long gl_sn, void* gr, long gr_sn, void* partU,
-                              void* gU, void* gR0, const void* sx, long sx_b, const void* sy, long sy_b, void* g_side_real,
-                              void* stream) {
+FL_SOLVE_ENTRY(fl_solve_dud2_grads_w, (const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U,
+                                       const void* r, long r_sn, long r_sf, const void* W, long w_sn, const void* gy, long gy_sb,
+                                       const void* OUT, long s_b, long s_n, long s_k, int B, int M, int N, void* gl, long gl_sn, void* gr,
+                                       long gr_sn, void* partU, void* gU, void* gR0, const void* sx, long sx_b, const void* sy, long sy_b,
+                                       void* g_side_real, void* stream),
+               (l, l_sn, l_sf, l2, l2_sn, l2_sf, U, r, r_sn, r_sf, W, w_sn, gy, gy_sb, OUT, s_b, s_n, s_k, B, M, N, gl, gl_sn, gr, gr_sn,
+                partU, gU, gR0, sx, sx_b, sy, sy_b, g_side_real, stream)) {
     FL_REQUIRE(l2 && W && gy, "solve_dud2_grads_w: null pointer");
     FL_REQUIRE((sx == nullptr) == (sy == nullptr) && (!sx || (partU && gU)), "solve_dud2_grads_w: side reductions need sx, sy and the partial buffers");
-    Dud<float> d = {(const cx<float>*)l, l_sn, l_sf, (const cx<float>*)U, (const cx<float>*)r, r_sn, r_sf,
-                    (const cx<float>*)l2, l2_sn, l2_sf, 0};
-    d.wadj = (cx<float>*)const_cast<void*>(W); d.wadj_sn = w_sn; d.wgy = (const cx<float>*)gy; d.wgy_sb = gy_sb;
-    DudSide<float> side = {(const cx<float>*)sx, (const cx<float>*)sy, sx_b, sy_b, sx ? 1 : 0, (float*)g_side_real};
-    return dud_grads_impl<float>(d, nullptr, OUT, s_b, s_n, s_k, B, M, N, 1, gl, gl_sn, gr, gr_sn, partU, gU, stream, gR0, side);
+    Dud<T> d = dud_of<T>(l, l_sn, l_sf, U, r, r_sn, r_sf, l2, l2_sn, l2_sf, 0);
+    d.wadj = (cx<T>*)const_cast<void*>(W); d.wadj_sn = w_sn; d.wgy = (const cx<T>*)gy; d.wgy_sb = gy_sb;
+    return dud_grads_impl<T>(d, nullptr, OUT, s_b, s_n, s_k, B, M, N, 1, gl, gl_sn, gr, gr_sn, partU, gU, stream, gR0,
+                             dud_side<T>(sx, sx_b, sy, sy_b, g_side_real));
 }
 /* fl_solve_dud2 with the right-hand side built in the kernel, R_i = rv_i rs (rv conjugated for the adjoint system; scaled by
  * l2 for the forward one), and -- forward system, cz non-NULL -- the contracted output z = sum_i cw_i OUT_i beside OUT */
-int fl_solve_fdn_c64(const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U, const void* r,
-                     long r_sn, long r_sf, int adjoint, const void* rv, int rv_real, const void* rs, long rs_sb, const void* cw,
-                     int cw_real, void* cz, long cz_sb, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, void* stream) {
+FL_SOLVE_ENTRY(fl_solve_fdn, (const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U, const void* r,
+                              long r_sn, long r_sf, int adjoint, const void* rv, int rv_real, const void* rs, long rs_sb, const void* cw,
+                              int cw_real, void* cz, long cz_sb, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N,
+                              void* stream),
+               (l, l_sn, l_sf, l2, l2_sn, l2_sf, U, r, r_sn, r_sf, adjoint, rv, rv_real, rs, rs_sb, cw, cw_real, cz, cz_sb, OUT, os_b, os_n,
+                os_k, B, M, N, stream)) {
     FL_REQUIRE(U && l2 && rv && rs && (!cz || cw), "solve_fdn: null pointer");
-    Dud<float> d = {(const cx<float>*)l, l_sn, l_sf, (const cx<float>*)U, (const cx<float>*)r, r_sn, r_sf,
-                    (const cx<float>*)l2, l2_sn, l2_sf, adjoint ? 0 : 1, rv, (const cx<float>*)rs, rs_sb, cw, (cx<float>*)cz, cz_sb,
-                    rv_real, cw_real};
-    return solve_impl<float>(nullptr, 0, d, 1, adjoint, nullptr, 0, 0, 0, OUT, os_b, os_n, os_k, B, M, N, 1, stream);
+    Dud<T> d = dud_fdn<T>(l, l_sn, l_sf, l2, l2_sn, l2_sf, U, r, r_sn, r_sf, adjoint ? 0 : 1, rv, rv_real, rs, rs_sb, cw, cw_real, cz, cz_sb);
+    return solve_impl<T>(nullptr, 0, d, 1, adjoint, nullptr, 0, 0, 0, OUT, os_b, os_n, os_k, B, M, N, 1, stream);
 }
-int fl_solve_fdn_c128(const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U, const void* r,
-                      long r_sn, long r_sf, int adjoint, const void* rv, int rv_real, const void* rs, long rs_sb, const void* cw,
-                      int cw_real, void* cz, long cz_sb, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, void* stream) {
-    FL_REQUIRE(U && l2 && rv && rs && (!cz || cw), "solve_fdn: null pointer");
-    Dud<double> d = {(const cx<double>*)l, l_sn, l_sf, (const cx<double>*)U, (const cx<double>*)r, r_sn, r_sf,
-                     (const cx<double>*)l2, l2_sn, l2_sf, adjoint ? 0 : 1, rv, (const cx<double>*)rs, rs_sb, cw, (cx<double>*)cz, cz_sb,
-                     rv_real, cw_real};
-    return solve_impl<double>(nullptr, 0, d, 1, adjoint, nullptr, 0, 0, 0, OUT, os_b, os_n, os_k, B, M, N, 1, stream);
+// the FDN form, forward system, with w = A^-H cw^H beside OUT and cz (fl_solve_fdn_wadj_supported)
+FL_SOLVE_ENTRY(fl_solve_fdn_wadj, (const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U, const void* r,
+                                   long r_sn, long r_sf, const void* rv, int rv_real, const void* rs, long rs_sb, const void* cw,
+                                   int cw_real, void* cz, long cz_sb, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N,
+                                   void* wadj, long wadj_sn, void* stream),
+               (l, l_sn, l_sf, l2, l2_sn, l2_sf, U, r, r_sn, r_sf, rv, rv_real, rs, rs_sb, cw, cw_real, cz, cz_sb, OUT, os_b, os_n, os_k, B,
+                M, N, wadj, wadj_sn, stream)) {
+    FL_REQUIRE(U && l2 && rv && rs && cw && wadj, "solve_fdn_wadj: null pointer");
+    FL_REQUIRE(fl_solve_fdn_wadj_supported(N), "solve_fdn_wadj: 4 < N <= 16 on the default kernels (fl_solve_fdn_wadj_supported)");
+    Dud<T> d = dud_fdn<T>(l, l_sn, l_sf, l2, l2_sn, l2_sf, U, r, r_sn, r_sf, 1, rv, rv_real, rs, rs_sb, cw, cw_real, cz, cz_sb);
+    d.wadj = (cx<T>*)wadj; d.wadj_sn = wadj_sn;
+    return solve_impl<T>(nullptr, 0, d, 1, 0, nullptr, 0, 0, 0, OUT, os_b, os_n, os_k, B, M, N, 1, stream);
 }
+// the FDN form, forward system, with kept factors (fl_solve_fdn_keep_tile)
+FL_SOLVE_ENTRY(fl_solve_fdn_keep, (const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U, const void* r,
+                                   long r_sn, long r_sf, const void* rv, int rv_real, const void* rs, long rs_sb, const void* cw,
+                                   int cw_real, void* cz, long cz_sb, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N,
+                                   void* LU, void* piv, void* stream),
+               (l, l_sn, l_sf, l2, l2_sn, l2_sf, U, r, r_sn, r_sf, rv, rv_real, rs, rs_sb, cw, cw_real, cz, cz_sb, OUT, os_b, os_n, os_k, B,
+                M, N, LU, piv, stream)) {
+    FL_REQUIRE(U && l2 && rv && rs && (!cz || cw) && LU && piv, "solve_fdn_keep: null pointer");
+    FL_REQUIRE(fl_solve_fdn_keep_tile(N, sizeof(T) == 8) > 0, "solve_fdn_keep: 8 < N <= 16 on the default kernels (fl_solve_fdn_keep_tile)");
+    Dud<T> d = dud_fdn<T>(l, l_sn, l_sf, l2, l2_sn, l2_sf, U, r, r_sn, r_sf, 1, rv, rv_real, rs, rs_sb, cw, cw_real, cz, cz_sb);
+    d.lu_out = (cx<T>*)LU; d.piv_out = (int*)piv;
+    return solve_impl<T>(nullptr, 0, d, 1, 0, nullptr, 0, 0, 0, OUT, os_b, os_n, os_k, B, M, N, 1, stream);
 }
+#undef FL_SOLVE_ENTRY

@@ -1452,26 +1452,35 @@ def mimo(H: torch.Tensor, X: torch.Tensor, diag: bool = False) -> torch.Tensor:
 
 
 # ----------------------------------------------------------------------------- closed-loop solve
-def _solve_launch(Pp, one_minus, adjoint, R):
-    real = _rdtype(R)
+# ---- one layer over the fl_solve_* entries, each called from ONE place: _solve_call (right-hand side in, solution out),
+# ---- _solve_fdn_call (the FDN form: the right-hand side is built in the kernel) and _dud_grads (the one-pass gradient kernel)
+def _solve_entry(name: str, real: torch.dtype):
+    return getattr(_lib.lib(), name + ("_c64" if real == torch.float32 else "_c128"))
+
+
+def _solve_call(name, span, R, *head, post=()):
+    """The solution OUT for the planar right-hand side R (B, M, N, K...), allocated like R, from the entry ``name``_c64 / _c128:
+    fn(*head, R and its strides, OUT and its strides, B, M, N, K, *post, stream)."""
     B, M, N, K, rs_b, rs_n, rs_k = _bnk(R)
     OUT = _empty_planar(R.shape, R.dtype, R.device)
     _, _, _, _, os_b, os_n, os_k = _bnk(OUT)
-    L = _lib.lib()
-    nws = int(L.fl_solve_ws_bytes(N, M, int(real == torch.float64)))
+    fn = _solve_entry(name, _rdtype(R))
+    with kernel_timer.span(span):
+        _lib.check(fn(*head, R.data_ptr(), rs_b, rs_n, rs_k, OUT.data_ptr(), os_b, os_n, os_k, B, M, N, K, *post, _stream()),
+                   name[3:])
+    return OUT
+
+
+def _solve_launch(Pp, one_minus, adjoint, R):
+    head = (Pp.data_ptr(), _lead_pitch(Pp.movedim(0, -1)), int(one_minus), int(adjoint))
+    span = "solve_adj" if adjoint else "solve"
+    M, N = R.shape[1], R.shape[2]
+    nws = int(_lib.lib().fl_solve_ws_bytes(N, M, int(_rdtype(R) == torch.float64)))
     if nws > 0:
         # loops beyond what one workgroup's LDS holds (N > 138 / 97): the factorisation's matrices in a workspace this call owns
         ws = torch.empty(nws, dtype=torch.uint8, device=R.device)
-        fn = L.fl_solve_ws_c64 if real == torch.float32 else L.fl_solve_ws_c128
-        with kernel_timer.span("solve_adj" if adjoint else "solve"):
-            _lib.check(fn(Pp.data_ptr(), _lead_pitch(Pp.movedim(0, -1)), int(one_minus), int(adjoint), R.data_ptr(), rs_b, rs_n,
-                          rs_k, OUT.data_ptr(), os_b, os_n, os_k, B, M, N, K, ws.data_ptr(), nws, _stream()), "solve_ws")
-        return OUT
-    fn = L.fl_solve_c64 if real == torch.float32 else L.fl_solve_c128
-    with kernel_timer.span("solve_adj" if adjoint else "solve"):
-        _lib.check(fn(Pp.data_ptr(), _lead_pitch(Pp.movedim(0, -1)), int(one_minus), int(adjoint), R.data_ptr(), rs_b, rs_n,
-                      rs_k, OUT.data_ptr(), os_b, os_n, os_k, B, M, N, K, _stream()), "solve")
-    return OUT
+        return _solve_call("fl_solve_ws", span, R, *head, post=(ws.data_ptr(), nws))
+    return _solve_call("fl_solve", span, R, *head)
 
 
 class _Solve(torch.autograd.Function):
@@ -1513,6 +1522,13 @@ def solve(P: torch.Tensor, R: torch.Tensor, one_minus: bool = True) -> torch.Ten
     return _Solve.apply(P, R, bool(one_minus))
 
 
+def _diag_factor(d: Optional[torch.Tensor]):
+    """An optional diagonal factor as the kernels read it: per-bin (M, N) bin-planar, constant (N,) contiguous, or None"""
+    if d is None:
+        return None
+    return _h_planar(d.resolve_conj(), True) if d.dim() == 2 else d.resolve_conj().contiguous()
+
+
 def _diag_args(d: Optional[torch.Tensor]):
     """(ptr, s_n, s_f) of an optional diagonal factor: per-bin (M, N), constant (N,) or None."""
     if d is None:
@@ -1522,76 +1538,106 @@ def _diag_args(d: Optional[torch.Tensor]):
     return d.data_ptr(), d.stride(1), d.stride(0)
 
 
-def _solve_dud_launch(l, U, r, adjoint, R):
-    real = _rdtype(R)
-    B, M, N, K, rs_b, rs_n, rs_k = _bnk(R)
-    OUT = _empty_planar(R.shape, R.dtype, R.device)
-    _, _, _, _, os_b, os_n, os_k = _bnk(OUT)
-    L = _lib.lib()
-    fn = L.fl_solve_dud_c64 if real == torch.float32 else L.fl_solve_dud_c128
-    lp, l_sn, l_sf = _diag_args(l)
-    rp, r_sn, r_sf = _diag_args(r)
-    with kernel_timer.span("solve_dud_adj" if adjoint else "solve_dud"):
-        _lib.check(fn(lp, l_sn, l_sf, U.data_ptr(), rp, r_sn, r_sf, int(adjoint), R.data_ptr(), rs_b, rs_n, rs_k,
-                      OUT.data_ptr(), os_b, os_n, os_k, B, M, N, K, _stream()), "solve_dud")
-    return OUT
+def _loop_args(l, l2, U, r, *mid):
+    """The factored loop A = I - diag(l . l2) U diag(r) as the C entries take it: l, l2, *mid, U, r -- without l2's triplet when
+    l2 is None (the fl_solve_dud_* entries have none)."""
+    return (*_diag_args(l), *(() if l2 is None else _diag_args(l2)), *mid, U.data_ptr(), *_diag_args(r))
+
+
+def _solve_dud_launch(l, l2, U, r, adjoint, R):
+    """A^-1 R or A^-H R (adjoint) for the factored loop; with l2 the forward system's right-hand side is l2 . R"""
+    span = "solve_dud_adj" if adjoint else "solve_dud"
+    if l2 is None:
+        return _solve_call("fl_solve_dud", span, R, *_loop_args(l, None, U, r), int(adjoint))
+    return _solve_call("fl_solve_dud2", span, R, *_loop_args(l, l2, U, r, int(not adjoint)), int(adjoint))
 
 
 # one-pass backward of the factored solve (fl_solve_dud_grads_*); False = the layered form (tests compare the two)
 FUSE_DUD_GRADS = True
 
 
-def _dud_grads_launch(lp, Uc, rp, gR, OUT, need_l, need_U, need_r):
-    """(gl (M, N) | None, gU (N, N) | None, gr (M, N) | None) from gR = A^-H g and OUT = A^-1 R (planar, same strides)."""
+def _dud_grads(l, l2, U, r, OUT, need_l, need_U, need_r, gR=None, Wadj=None, gyp=None, need_R0=False, Xp=None, gains=None,
+               need_gains=(False, False)):
+    """ONE pass over OUT = A^-1 R (planar) and the adjoint solution for the gradients of A = I - diag(l . l2) U diag(r):
+    -> (gl (M, N), gU (N, N), gr (M, N), gR0, g_b (N, 1), g_c (1, N)), None where not needed.
+    The adjoint solution is a tensor gR = A^-H g (planar, OUT's strides), or Wadj (1, M, N) with gyp (B, M, 1): gR[b] = Wadj gyp[b]
+    is then formed inside the kernel.  With l2: gR0 = conj(l2) . gR, the gradient of the right-hand side before l2 (need_R0), and
+    -- with Xp, gyp and gains = (b, c): ops.fdn_core -- the side reductions g_b, g_c of the gains around the loop (need_gains).
+    Entries: fl_solve_dud_grads_* (l2 is None), fl_solve_dud2_grads_* (gR) or fl_solve_dud2_grads_w_* (Wadj)."""
+    need_b, need_c = need_gains
+    side = need_b or need_c
+    if not (need_l or need_U or need_r or need_R0 or side):
+        return (None,) * 6
+    assert l2 is not None or not (need_R0 or side)
     real = _rdtype(OUT)
     B, M, N, K, s_b, s_n, s_k = _bnk(OUT)
-    assert _bnk(gR) == (B, M, N, K, s_b, s_n, s_k)
+    assert gR is None or _bnk(gR) == (B, M, N, K, s_b, s_n, s_k)
     dev = OUT.device
-    L = _lib.lib()
     gl = _empty_rows((N,), M, OUT.dtype, dev) if need_l else None
     gr = _empty_rows((N,), M, OUT.dtype, dev) if need_r else None
-    part = gU = None
-    if need_U:
-        part = torch.empty((L.fl_solve_dud_grads_blocks(M, N), N, N), dtype=OUT.dtype, device=dev)
-        gU = torch.empty((N, N), dtype=OUT.dtype, device=dev)
-    lptr, l_sn, l_sf = _diag_args(lp)
-    rptr, r_sn, r_sf = _diag_args(rp)
-    fn = L.fl_solve_dud_grads_c64 if real == torch.float32 else L.fl_solve_dud_grads_c128
+    gR0 = _empty_planar(OUT.shape, OUT.dtype, dev) if need_R0 else None
+    part = gUS = side_real = None
+    if need_U or side:
+        cnt = N * N + (2 * N if side else 0)        # [gU | g_b | g_c]
+        part = torch.empty((_lib.lib().fl_solve_dud_grads_blocks(M, N), cnt), dtype=OUT.dtype, device=dev)
+        gUS = torch.empty((cnt,), dtype=OUT.dtype, device=dev)
+        if side and not gains[0].is_complex() and not gains[1].is_complex():
+            side_real = torch.empty((2 * N,), dtype=real, device=dev)
     ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    outs = (ptr(gl), _pitch(M), ptr(gr), _pitch(M), ptr(part), ptr(gUS))
+    if l2 is not None:
+        xs_b = 0 if Xp is None else _bnk(Xp)[4]
+        gs_b = 0 if gyp is None else _bnk(gyp)[4]
+        outs += (ptr(gR0), Xp.data_ptr() if side else None, xs_b, gyp.data_ptr() if side else None, gs_b, ptr(side_real))
+    if Wadj is not None:
+        name, adj, sizes = "fl_solve_dud2_grads_w", (Wadj.data_ptr(), _bnk(Wadj)[5], gyp.data_ptr(), gs_b), (B, M, N)
+    else:
+        name, adj, sizes = ("fl_solve_dud_grads" if l2 is None else "fl_solve_dud2_grads"), (gR.data_ptr(),), (B, M, N, K)
+    fn = _solve_entry(name, real)
     with kernel_timer.span("solve_dud_grads"):
-        _lib.check(fn(lptr, l_sn, l_sf, Uc.data_ptr(), rptr, r_sn, r_sf, gR.data_ptr(), OUT.data_ptr(), s_b, s_n, s_k, B, M, N, K,
-                      ptr(gl), _pitch(M), ptr(gr), _pitch(M), ptr(part), ptr(gU), _stream()), "solve_dud_grads")
-    return (None if gl is None else gl.movedim(-1, 0)), gU, (None if gr is None else gr.movedim(-1, 0))
+        _lib.check(fn(*_loop_args(l, l2, U, r), *adj, OUT.data_ptr(), s_b, s_n, s_k, *sizes, *outs, _stream()), name[3:])
+    g_b = g_c = None
+    if side:
+        tail = side_real if side_real is not None else gUS[N * N:]
+        gb_full, gc_full = tail[:N].view(N, 1), tail[N:].view(1, N)
+        if side_real is None:        # mixed real / complex gains: the real one takes the real part
+            gb_full = gb_full if gains[0].is_complex() else gb_full.real
+            gc_full = gc_full if gains[1].is_complex() else gc_full.real
+        g_b = gb_full if need_b else None
+        g_c = gc_full if need_c else None
+    rows = lambda g: None if g is None else g.movedim(-1, 0)  # noqa: E731
+    return rows(gl), (gUS[:N * N].view(N, N) if need_U else None), rows(gr), gR0, g_b, g_c
 
 
 class _SolveDUD(torch.autograd.Function):
-    """OUT = (I - diag(l) U diag(r))^-1 R per bin; l, r: per-bin (M,N) / constant (N,) / None."""
+    """OUT = (I - diag(l) U diag(r))^-1 R per bin; l, r: per-bin (M,N) / constant (N,) / None.
+    With l2: OUT = (I - diag(l . l2) U diag(r))^-1 (l2 . R) per bin: the loop of a feedback delay network with the feedforward
+    path's diagonal l2 (no gradient) applied where the kernels load l and the right-hand side (fl_solve_dud2_*).
+    l, r: per-bin (M, N) or None; l2: per-bin (M, N)."""
 
     @staticmethod
-    def forward(ctx, l, U, r, R):
-        _require_gpu(U, R)
+    def forward(ctx, l, l2, U, r, R):
+        _require_gpu(l2, U, R)
         Rp = to_planar(R.resolve_conj())
         Uc = U.resolve_conj().contiguous()
-        lp = None if l is None else (_h_planar(l.resolve_conj(), True) if l.dim() == 2 else l.resolve_conj().contiguous())
-        rp = None if r is None else (_h_planar(r.resolve_conj(), True) if r.dim() == 2 else r.resolve_conj().contiguous())
-        OUT = _solve_dud_launch(lp, Uc, rp, False, Rp)
-        ctx.have = (l is not None, r is not None)
-        ctx.save_for_backward(*([t for t in (lp, rp) if t is not None] + [Uc, OUT]))
+        lp, l2p, rp = _diag_factor(l), _diag_factor(l2), _diag_factor(r)
+        OUT = _solve_dud_launch(lp, l2p, Uc, rp, False, Rp)
+        ctx.save_for_backward(lp, l2p, Uc, rp, OUT)         # absent factors are saved as None: no tensor is held for them
         return OUT
 
     @staticmethod
     def backward(ctx, gOUT):
-        saved = list(ctx.saved_tensors)
-        lp = saved.pop(0) if ctx.have[0] else None
-        rp = saved.pop(0) if ctx.have[1] else None
-        Uc, OUT = saved
-        gR = _solve_dud_launch(lp, Uc, rp, True, to_planar(gOUT.resolve_conj()))          # A^-H g
+        lp, l2p, Uc, rp, OUT = ctx.saved_tensors
+        gR = _solve_dud_launch(lp, l2p, Uc, rp, True, to_planar(gOUT.resolve_conj()))          # A^-H g
         gl = gU = gr = None
-        need_l, need_U, need_r = ctx.needs_input_grad[0] and lp is not None, ctx.needs_input_grad[1], \
-            ctx.needs_input_grad[2] and rp is not None
+        need_l, need_U, need_r, need_R = (ctx.needs_input_grad[0] and lp is not None, ctx.needs_input_grad[2],
+                                          ctx.needs_input_grad[3] and rp is not None, ctx.needs_input_grad[4])
+        if l2p is not None:      # the right-hand side's gradient is conj(l2) . gR, from the same pass
+            gl, gU, gr, gR0, _, _ = _dud_grads(lp, l2p, Uc, rp, OUT, need_l, need_U, need_r, gR=gR, need_R0=need_R)
+            return gl, None, gU, gr, gR0
         fusable = (lp is None or lp.dim() == 2) and (rp is None or rp.dim() == 2)      # per-bin or absent diagonal factors
-        if (need_l or need_U or need_r) and fusable and FUSE_DUD_GRADS:
-            gl, gU, gr = _dud_grads_launch(lp, Uc, rp, gR, OUT, need_l, need_U, need_r)
+        if fusable and FUSE_DUD_GRADS:
+            gl, gU, gr, _, _, _ = _dud_grads(lp, None, Uc, rp, OUT, need_l, need_U, need_r, gR=gR)
         elif need_l or need_U or need_r:
             # dP_ij = sum_b gR_i conj(out_j) with P_ij = l_i U_ij r_j, contracted without forming dP:
             t1 = OUT if rp is None else _mimo_launch(rp, rp.dim() == 2, True, False, OUT)   # r * out
@@ -1606,57 +1652,27 @@ class _SolveDUD(torch.autograd.Function):
                 w = _mimo_launch(Uc, False, False, True, t2)                                # U^H (conj(l)*gR)
                 g = _gradh_launch(w, OUT, True)                                             # sum_b w conj(out)
                 gr = g.movedim(-1, 0) if rp.dim() == 2 else g.sum(dim=-1)
-        return gl, gU, gr, (gR if ctx.needs_input_grad[3] else None)
+        return gl, None, gU, gr, (gR if need_R else None)
 
 
-class _SolveDUD2(torch.autograd.Function):
-    """OUT = (I - diag(l . l2) U diag(r))^-1 (l2 . R0) per bin: the loop of a feedback delay network with the feedforward
-    path's diagonal l2 (no gradient) applied where the kernels load l and the right-hand side (fl_solve_dud2_*).
-    l, r: per-bin (M, N) or None; l2: per-bin (M, N)."""
+def solve_dud(l: Optional[torch.Tensor], U: torch.Tensor, r: Optional[torch.Tensor], R: torch.Tensor) -> torch.Tensor:
+    """Per bin f: (I - diag(l[f]) U diag(r[f]))^-1 R[:, f] -- the closed loop of a feedback delay
+    network, with the loop matrix kept in factored form (never materialised)."""
+    cd = R.dtype
+    conv = lambda t: None if t is None else (t if t.dtype == cd else t.to(cd))  # noqa: E731
+    return _SolveDUD.apply(conv(l), None, conv(U), conv(r), R)
 
-    @staticmethod
-    def forward(ctx, l, l2, U, r, R0):
-        _require_gpu(l2, U, R0)
-        Rp = to_planar(R0.resolve_conj())
-        Uc = U.resolve_conj().contiguous()
-        pl = lambda t: None if t is None else _h_planar(t.resolve_conj(), True)  # noqa: E731
-        lp, l2p, rp = pl(l), pl(l2), pl(r)
-        OUT = _solve_dud2_launch(lp, l2p, True, Uc, rp, False, Rp)
-        ctx.have = (l is not None, r is not None)
-        ctx.save_for_backward(*([t for t in (lp, rp) if t is not None] + [l2p, Uc, OUT]))
-        return OUT
 
-    @staticmethod
-    def backward(ctx, gOUT):
-        saved = list(ctx.saved_tensors)
-        lp = saved.pop(0) if ctx.have[0] else None
-        rp = saved.pop(0) if ctx.have[1] else None
-        l2p, Uc, OUT = saved
-        gR = _solve_dud2_launch(lp, l2p, False, Uc, rp, True, to_planar(gOUT.resolve_conj()))     # A^-H g
-        need_l, need_U, need_r, need_R = (ctx.needs_input_grad[0] and lp is not None, ctx.needs_input_grad[2],
-                                          ctx.needs_input_grad[3] and rp is not None, ctx.needs_input_grad[4])
-        real = _rdtype(OUT)
-        B, M, N, K, s_b, s_n, s_k = _bnk(OUT)
-        dev = OUT.device
-        L = _lib.lib()
-        gl = _empty_rows((N,), M, OUT.dtype, dev) if need_l else None
-        gr = _empty_rows((N,), M, OUT.dtype, dev) if need_r else None
-        gR0 = _empty_planar(OUT.shape, OUT.dtype, dev) if need_R else None
-        part = gU = None
-        if need_U:
-            part = torch.empty((L.fl_solve_dud_grads_blocks(M, N), N, N), dtype=OUT.dtype, device=dev)
-            gU = torch.empty((N, N), dtype=OUT.dtype, device=dev)
-        if need_l or need_U or need_r or need_R:
-            lptr, l_sn, l_sf = _diag_args(lp)
-            l2ptr, l2_sn, l2_sf = _diag_args(l2p)
-            rptr, r_sn, r_sf = _diag_args(rp)
-            fn = L.fl_solve_dud2_grads_c64 if real == torch.float32 else L.fl_solve_dud2_grads_c128
-            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-            with kernel_timer.span("solve_dud_grads"):
-                _lib.check(fn(lptr, l_sn, l_sf, l2ptr, l2_sn, l2_sf, Uc.data_ptr(), rptr, r_sn, r_sf, gR.data_ptr(), OUT.data_ptr(),
-                              s_b, s_n, s_k, B, M, N, K, ptr(gl), _pitch(M), ptr(gr), _pitch(M), ptr(part), ptr(gU), ptr(gR0),
-                              None, 0, None, 0, None, _stream()), "solve_dud2_grads")
-        return (None if gl is None else gl.movedim(-1, 0)), None, gU, (None if gr is None else gr.movedim(-1, 0)), gR0
+def solve_dud2(l: Optional[torch.Tensor], l2: torch.Tensor, U: torch.Tensor, r: Optional[torch.Tensor], R0: torch.Tensor) -> torch.Tensor:
+    """Per bin f: (I - diag(l[f] . l2[f]) U diag(r[f]))^-1 (l2[f] . R0[:, f]); l, r: per-bin (M, N) or None, l2: per-bin
+    (M, N) without gradient (the diagonal of the feedforward path, which also scales the right-hand side).
+    Replaces system.py:417-424 (Recursion.forward: A = I - fF(fB(I)), solve(A, fF(X))) for the FDN structure of
+    reverb.py:117-199 / e8_fdn.py:60-100, where fF is the delay line alone."""
+    if l2.requires_grad:
+        raise ValueError("solve_dud2: the feedforward diagonal must not require a gradient (use solve_dud)")
+    cd = R0.dtype
+    conv = lambda t: None if t is None else (t if t.dtype == cd else t.to(cd))  # noqa: E731
+    return _SolveDUD.apply(conv(l), conv(l2), conv(U), conv(r), R0)
 
 
 def _apply_const(W, transpose, X):
@@ -1690,67 +1706,70 @@ FDN_ADJOINT_IN_FORWARD = True
 FDN_ADJOINT_IN_FORWARD_F64 = True      # (float64: the forward kernel with w runs at one wavefront per SIMD -- still ahead of a second solve)
 
 
-def _solve_fdn_launch(l, l2, U, r, adjoint, gain, sig, cw, keep=False, wadj=False):
-    """OUT = A^-1 (l2 . (gain sig)) [forward] or A^-H (conj(gain) sig) [adjoint]; with cw (forward) also z = cw . OUT.
-    gain, cw: contiguous N-vectors, real or complex; sig: planar one-channel signal (B, M, 1).  -> (OUT, z | None), or with
-    keep (forward): (OUT, z, (LU, piv, tile)) -- the factors for _solve_fdn_kept_adjoint_launch."""
-    real = _rdtype(sig)
+def _fdn_route(real, N, needs_grad) -> str:
+    """How ops.fdn_core reaches the solve kernels, chosen once in the forward pass:
+    "wadj"     fl_solve_fdn_wadj_*: the forward launch also leaves w = A^-H c^H; the backward pass runs no solve
+    "keep"     fl_solve_fdn_keep_*: the forward launch keeps its factors; the adjoint is fl_solve_kept_adjoint_rank1_*
+    "in_solve" fl_solve_fdn_* forward and adjoint: the gains inside the kernels, a second elimination for the adjoint
+    "layered"  fl_solve_dud2_* between separate launches for b x, c OUT and c^H gy"""
+    if not _fdn_in_solve(real, N):
+        return "layered"
+    L = _lib.lib()
+    if needs_grad and FDN_ADJOINT_IN_FORWARD and (real == torch.float32 or FDN_ADJOINT_IN_FORWARD_F64) and \
+            L.fl_solve_fdn_wadj_supported(N):
+        return "wadj"
+    if needs_grad and KEEP_LU_FDN and L.fl_solve_fdn_keep_tile(N, int(real == torch.float64)) > 0:
+        return "keep"
+    return "in_solve"
+
+
+def _solve_fdn_call(name, span, head, gain, sig, N, cw=None, contracts=True, post=()):
+    """(OUT (B, M, N), z (B, M, 1) | None) from an entry ``name``_c64 / _c128 that builds its right-hand side gain . sig in the
+    kernel.  gain, cw: contiguous N-vectors, real or complex; sig: planar one-channel signal (B, M, 1); z = cw . OUT.
+    fn(*head, gain, sig, [cw, z -- the entries that can contract], OUT and its strides, B, M, N, *post, stream)."""
     B, M, _, K, ss_b, _, _ = _bnk(sig)
     assert K == 1
-    N = U.shape[0]
     OUT = _empty_planar((B, M, N), sig.dtype, sig.device)
     _, _, _, _, os_b, os_n, os_k = _bnk(OUT)
     z = _empty_planar((B, M, 1), sig.dtype, sig.device) if cw is not None else None
-    zs_b = _bnk(z)[4] if z is not None else 0
-    L = _lib.lib()
-    lp, l_sn, l_sf = _diag_args(l)
-    l2p, l2_sn, l2_sf = _diag_args(l2)
-    rp, r_sn, r_sf = _diag_args(r)
-    if wadj:        # forward: (OUT, z, W) with W (1, M, N) planar = A^-H cw^H
-        assert not adjoint and cw is not None
-        W = _empty_planar((1, M, N), sig.dtype, sig.device)
-        _, _, _, _, _, ws_n, _ = _bnk(W)
-        fnw = L.fl_solve_fdn_wadj_c64 if real == torch.float32 else L.fl_solve_fdn_wadj_c128
-        with kernel_timer.span("solve_dud"):
-            _lib.check(fnw(lp, l_sn, l_sf, l2p, l2_sn, l2_sf, U.data_ptr(), rp, r_sn, r_sf, gain.data_ptr(),
-                           int(not gain.is_complex()), sig.data_ptr(), ss_b, cw.data_ptr(), int(not cw.is_complex()),
-                           z.data_ptr(), zs_b, OUT.data_ptr(), os_b, os_n, os_k, B, M, N, W.data_ptr(), ws_n,
-                           _stream()), "solve_fdn_wadj")
-        return OUT, z, W
-    if keep:
-        assert not adjoint
-        tile = L.fl_solve_fdn_keep_tile(N, int(real == torch.float64))
-        nt = (M + tile - 1) // tile
-        LU = torch.empty(nt * tile * N * N, dtype=sig.dtype, device=sig.device)
-        piv = torch.empty(nt * tile * N, dtype=torch.int32, device=sig.device)
-        fn = L.fl_solve_fdn_keep_c64 if real == torch.float32 else L.fl_solve_fdn_keep_c128
-        with kernel_timer.span("solve_dud"):
-            _lib.check(fn(lp, l_sn, l_sf, l2p, l2_sn, l2_sf, U.data_ptr(), rp, r_sn, r_sf, gain.data_ptr(),
-                          int(not gain.is_complex()), sig.data_ptr(), ss_b, None if cw is None else cw.data_ptr(),
-                          int(cw is not None and not cw.is_complex()), None if z is None else z.data_ptr(), zs_b, OUT.data_ptr(), os_b,
-                          os_n, os_k, B, M, N, LU.data_ptr(), piv.data_ptr(), _stream()), "solve_fdn_keep")
-        return OUT, z, (LU, piv, tile)
-    fn = L.fl_solve_fdn_c64 if real == torch.float32 else L.fl_solve_fdn_c128
-    with kernel_timer.span("solve_dud_adj" if adjoint else "solve_dud"):
-        _lib.check(fn(lp, l_sn, l_sf, l2p, l2_sn, l2_sf, U.data_ptr(), rp, r_sn, r_sf, int(adjoint), gain.data_ptr(),
-                      int(not gain.is_complex()), sig.data_ptr(), ss_b, None if cw is None else cw.data_ptr(),
-                      int(cw is not None and not cw.is_complex()), None if z is None else z.data_ptr(), zs_b, OUT.data_ptr(), os_b,
-                      os_n, os_k, B, M, N, _stream()), "solve_fdn")
+    contract = ()
+    if contracts:
+        contract = ((None, 0, None, 0) if cw is None else (cw.data_ptr(), int(not cw.is_complex()), z.data_ptr(), _bnk(z)[4]))
+    fn = _solve_entry(name, _rdtype(sig))
+    with kernel_timer.span(span):
+        _lib.check(fn(*head, gain.data_ptr(), int(not gain.is_complex()), sig.data_ptr(), ss_b, *contract, OUT.data_ptr(), os_b,
+                      os_n, os_k, B, M, N, *post, _stream()), name[3:])
     return OUT, z
 
 
-def _solve_fdn_kept_adjoint_launch(LU, piv, tile, gain, sig, N):
+def _solve_fdn_launch(l, l2, U, r, adjoint, gain, sig, cw, route="in_solve"):
+    """OUT = A^-1 (l2 . (gain sig)) [forward] or A^-H (conj(gain) sig) [adjoint]; with cw (forward) also z = cw . OUT.
+    -> (OUT, z | None, extra): what the route's forward launch leaves for the backward pass -- "wadj": (W,) with W (1, M, N)
+    planar = A^-H cw^H; "keep": (LU, piv), the factors for _solve_fdn_kept_adjoint_launch; else ()."""
+    N, M, f64 = U.shape[0], sig.shape[1], int(_rdtype(sig) == torch.float64)
+    loop = _loop_args(l, l2, U, r)
+    if route == "wadj":
+        assert not adjoint and cw is not None
+        W = _empty_planar((1, M, N), sig.dtype, sig.device)
+        OUT, z = _solve_fdn_call("fl_solve_fdn_wadj", "solve_dud", loop, gain, sig, N, cw, post=(W.data_ptr(), _bnk(W)[5]))
+        return OUT, z, (W,)
+    if route == "keep":
+        assert not adjoint
+        tile = _lib.lib().fl_solve_fdn_keep_tile(N, f64)
+        nt = (M + tile - 1) // tile
+        LU = torch.empty(nt * tile * N * N, dtype=sig.dtype, device=sig.device)
+        piv = torch.empty(nt * tile * N, dtype=torch.int32, device=sig.device)
+        OUT, z = _solve_fdn_call("fl_solve_fdn_keep", "solve_dud", loop, gain, sig, N, cw, post=(LU.data_ptr(), piv.data_ptr()))
+        return OUT, z, (LU, piv)
+    OUT, z = _solve_fdn_call("fl_solve_fdn", "solve_dud_adj" if adjoint else "solve_dud", (*loop, int(adjoint)), gain, sig, N, cw)
+    return OUT, z, ()
+
+
+def _solve_fdn_kept_adjoint_launch(LU, piv, gain, sig, N):
     """A^-H (conj(gain) sig) from the factors the forward solve kept"""
-    real = _rdtype(sig)
-    B, M, _, K, ss_b, _, _ = _bnk(sig)
-    OUT = _empty_planar((B, M, N), sig.dtype, sig.device)
-    _, _, _, _, os_b, os_n, os_k = _bnk(OUT)
-    L = _lib.lib()
-    fn = L.fl_solve_kept_adjoint_rank1_c64 if real == torch.float32 else L.fl_solve_kept_adjoint_rank1_c128
-    with kernel_timer.span("solve_dud_adj"):
-        _lib.check(fn(LU.data_ptr(), piv.data_ptr(), int(tile), gain.data_ptr(), int(not gain.is_complex()), sig.data_ptr(), ss_b,
-                      OUT.data_ptr(), os_b, os_n, os_k, B, M, N, _stream()), "solve_kept_adjoint_rank1")
-    return OUT
+    tile = _lib.lib().fl_solve_fdn_keep_tile(N, int(_rdtype(sig) == torch.float64))
+    return _solve_fdn_call("fl_solve_kept_adjoint_rank1", "solve_dud_adj", (LU.data_ptr(), piv.data_ptr(), int(tile)), gain, sig, N,
+                           contracts=False)[0]
 
 
 class _FdnCore(torch.autograd.Function):
@@ -1768,102 +1787,39 @@ class _FdnCore(torch.autograd.Function):
             raise ValueError("fdn_core: expected b (N, 1), c (1, N) and a one-channel spectrum X (B, M, 1)")
         Xp = to_planar(X.resolve_conj())
         Uc = U.resolve_conj().contiguous()
-        pl = lambda t: None if t is None else _h_planar(t.resolve_conj(), True)  # noqa: E731
-        lp, l2p, rp = pl(l), pl(l2), pl(r)
+        lp, l2p, rp = _diag_factor(l), _diag_factor(l2), _diag_factor(r)
         bc, cc = b.resolve_conj().contiguous(), c.resolve_conj().contiguous()
-        ctx.in_solve = _fdn_in_solve(_rdtype(Xp), N)
-        kept = None
-        Wadj = None
-        if ctx.in_solve and FDN_ADJOINT_IN_FORWARD and any(ctx.needs_input_grad) and \
-                (_rdtype(Xp) == torch.float32 or FDN_ADJOINT_IN_FORWARD_F64) and _lib.lib().fl_solve_fdn_wadj_supported(N):
-            OUT, y, Wadj = _solve_fdn_launch(lp, l2p, Uc, rp, False, bc, Xp, cc, wadj=True)
-        elif ctx.in_solve and KEEP_LU_FDN and any(ctx.needs_input_grad) and \
-                _lib.lib().fl_solve_fdn_keep_tile(N, int(_rdtype(Xp) == torch.float64)) > 0:
-            OUT, y, kept = _solve_fdn_launch(lp, l2p, Uc, rp, False, bc, Xp, cc, keep=True)
-        elif ctx.in_solve:
-            OUT, y = _solve_fdn_launch(lp, l2p, Uc, rp, False, bc, Xp, cc)
-        else:
+        route = ctx.route = _fdn_route(_rdtype(Xp), N, any(ctx.needs_input_grad))
+        if route == "layered":
             R0 = _apply_const(bc, False, Xp)
-            OUT = _solve_dud2_launch(lp, l2p, True, Uc, rp, False, R0)
-            y = _apply_const(cc, False, OUT)
-        ctx.have = (l is not None, r is not None)
-        ctx.kept_tile = kept[2] if kept is not None else 0
-        ctx.has_wadj = Wadj is not None
-        ctx.save_for_backward(*([t for t in (lp, rp) if t is not None] + [l2p, Uc, OUT, Xp, bc, cc] +
-                                (list(kept[:2]) if kept is not None else []) + ([Wadj] if Wadj is not None else [])))
+            OUT = _solve_dud_launch(lp, l2p, Uc, rp, False, R0)
+            y, extra = _apply_const(cc, False, OUT), ()
+        else:
+            OUT, y, extra = _solve_fdn_launch(lp, l2p, Uc, rp, False, bc, Xp, cc, route=route)
+        ctx.save_for_backward(lp, l2p, Uc, rp, OUT, Xp, bc, cc, *extra)     # extra: (W,) on "wadj", (LU, piv) on "keep"
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        saved = list(ctx.saved_tensors)
-        lp = saved.pop(0) if ctx.have[0] else None
-        rp = saved.pop(0) if ctx.have[1] else None
-        l2p, Uc, OUT, Xp, bc, cc, *kept = saved
+        lp, l2p, Uc, rp, OUT, Xp, bc, cc, *extra = ctx.saved_tensors
         gyp = to_planar(gy.resolve_conj())
-        Wadj = kept[-1] if ctx.has_wadj else None
-        if Wadj is not None:   # A^-H c^H gy = w gy with w from the forward launch: formed inside the gradient kernel, no solve, no tensor
-            gR = None
-        elif kept:        # A^-H c^H gy from the forward solve's factors: a substitution, no second elimination
-            gR = _solve_fdn_kept_adjoint_launch(kept[0], kept[1], ctx.kept_tile, cc, gyp, Uc.shape[0])
-        elif ctx.in_solve:
-            gR, _ = _solve_fdn_launch(lp, l2p, Uc, rp, True, cc, gyp, None)                           # A^-H c^H gy
+        route = ctx.route
+        gR = Wadj = None
+        if route == "wadj":   # A^-H c^H gy = w gy with w from the forward launch: formed inside the gradient kernel, no solve, no tensor
+            Wadj, = extra
+        elif route == "keep":        # A^-H c^H gy from the forward solve's factors: a substitution, no second elimination
+            gR = _solve_fdn_kept_adjoint_launch(*extra, cc, gyp, Uc.shape[0])
+        elif route == "in_solve":
+            gR, _, _ = _solve_fdn_launch(lp, l2p, Uc, rp, True, cc, gyp, None)                        # A^-H c^H gy
         else:
-            gR = _solve_dud2_launch(lp, l2p, False, Uc, rp, True, _apply_const(cc, True, gyp))
+            gR = _solve_dud_launch(lp, l2p, Uc, rp, True, _apply_const(cc, True, gyp))
         need_b, need_c, need_l, need_U, need_r, need_X = (ctx.needs_input_grad[0], ctx.needs_input_grad[1],
                                                           ctx.needs_input_grad[2] and lp is not None, ctx.needs_input_grad[4],
                                                           ctx.needs_input_grad[5] and rp is not None, ctx.needs_input_grad[6])
-        real = _rdtype(OUT)
-        B, M, N, K, s_b, s_n, s_k = _bnk(OUT)
-        dev = OUT.device
-        L = _lib.lib()
-        gl = _empty_rows((N,), M, OUT.dtype, dev) if need_l else None
-        gr = _empty_rows((N,), M, OUT.dtype, dev) if need_r else None
-        gR0 = _empty_planar(OUT.shape, OUT.dtype, dev) if need_X else None
-        side = need_b or need_c
-        real_gains = not bc.is_complex() and not cc.is_complex()
-        part = gUS = side_real = None
-        if need_U or side:
-            cnt = N * N + (2 * N if side else 0)
-            part = torch.empty((L.fl_solve_dud_grads_blocks(M, N), cnt), dtype=OUT.dtype, device=dev)
-            gUS = torch.empty((cnt,), dtype=OUT.dtype, device=dev)
-            if side and real_gains:
-                side_real = torch.empty((2 * N,), dtype=real, device=dev)
-        g_b = g_c = gU = gX = None
-        if need_l or need_U or need_r or need_X or side:
-            lptr, l_sn, l_sf = _diag_args(lp)
-            l2ptr, l2_sn, l2_sf = _diag_args(l2p)
-            rptr, r_sn, r_sf = _diag_args(rp)
-            _, _, _, _, xs_b, _, _ = _bnk(Xp)
-            _, _, _, _, gs_b, _, _ = _bnk(gyp)
-            fn = L.fl_solve_dud2_grads_c64 if real == torch.float32 else L.fl_solve_dud2_grads_c128
-            ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-            with kernel_timer.span("solve_dud_grads"):
-                if Wadj is not None:
-                    _, _, _, _, _, w_sn, _ = _bnk(Wadj)
-                    fnw = L.fl_solve_dud2_grads_w_c64 if real == torch.float32 else L.fl_solve_dud2_grads_w_c128
-                    _lib.check(fnw(lptr, l_sn, l_sf, l2ptr, l2_sn, l2_sf, Uc.data_ptr(), rptr, r_sn, r_sf,
-                                   Wadj.data_ptr(), w_sn, gyp.data_ptr(), gs_b, OUT.data_ptr(), s_b, s_n, s_k, B, M, N,
-                                   ptr(gl), _pitch(M), ptr(gr), _pitch(M), ptr(part), ptr(gUS), ptr(gR0),
-                                   Xp.data_ptr() if side else None, xs_b, gyp.data_ptr() if side else None, gs_b,
-                                   ptr(side_real), _stream()), "solve_dud2_grads_w")
-                else:
-                    _lib.check(fn(lptr, l_sn, l_sf, l2ptr, l2_sn, l2_sf, Uc.data_ptr(), rptr, r_sn, r_sf, gR.data_ptr(), OUT.data_ptr(),
-                                  s_b, s_n, s_k, B, M, N, K, ptr(gl), _pitch(M), ptr(gr), _pitch(M), ptr(part), ptr(gUS), ptr(gR0),
-                                  Xp.data_ptr() if side else None, xs_b, gyp.data_ptr() if side else None, gs_b, ptr(side_real),
-                                  _stream()), "solve_dud2_grads")
-            if need_U:
-                gU = gUS[:N * N].view(N, N)
-            if side:
-                tail = side_real if side_real is not None else gUS[N * N:]
-                gb_full, gc_full = tail[:N].view(N, 1), tail[N:].view(1, N)
-                if side_real is None:        # mixed real / complex gains: the real one takes the real part
-                    gb_full = gb_full if bc.is_complex() else gb_full.real
-                    gc_full = gc_full if cc.is_complex() else gc_full.real
-                g_b = gb_full if need_b else None
-                g_c = gc_full if need_c else None
-            if need_X:
-                gX = _apply_const(bc, True, gR0)
-        return (g_b, g_c, (None if gl is None else gl.movedim(-1, 0)), None, gU, (None if gr is None else gr.movedim(-1, 0)), gX)
+        gl, gU, gr, gR0, g_b, g_c = _dud_grads(lp, l2p, Uc, rp, OUT, need_l, need_U, need_r, gR=gR, Wadj=Wadj, gyp=gyp,
+                                               need_R0=need_X, Xp=Xp, gains=(bc, cc), need_gains=(need_b, need_c))
+        gX = _apply_const(bc, True, gR0) if need_X else None
+        return g_b, g_c, gl, None, gU, gr, gX
 
 
 def fdn_core(b, c, l, l2, U, r, X):
@@ -1879,47 +1835,6 @@ def fdn_core(b, c, l, l2, U, r, X):
     return _FdnCore.apply(gain(b), gain(c), conv(l), conv(l2), conv(U), conv(r), X)
 
 
-def _solve_dud2_launch(l, l2, rhs_l2, U, r, adjoint, R):
-    real = _rdtype(R)
-    B, M, N, K, rs_b, rs_n, rs_k = _bnk(R)
-    OUT = _empty_planar(R.shape, R.dtype, R.device)
-    _, _, _, _, os_b, os_n, os_k = _bnk(OUT)
-    L = _lib.lib()
-    fn = L.fl_solve_dud2_c64 if real == torch.float32 else L.fl_solve_dud2_c128
-    lp, l_sn, l_sf = _diag_args(l)
-    l2p, l2_sn, l2_sf = _diag_args(l2)
-    rp, r_sn, r_sf = _diag_args(r)
-    with kernel_timer.span("solve_dud_adj" if adjoint else "solve_dud"):
-        _lib.check(fn(lp, l_sn, l_sf, l2p, l2_sn, l2_sf, int(rhs_l2), U.data_ptr(), rp, r_sn, r_sf, int(adjoint), R.data_ptr(),
-                      rs_b, rs_n, rs_k, OUT.data_ptr(), os_b, os_n, os_k, B, M, N, K, _stream()), "solve_dud2")
-    return OUT
-
-
-def solve_dud2(l: Optional[torch.Tensor], l2: torch.Tensor, U: torch.Tensor, r: Optional[torch.Tensor], R0: torch.Tensor) -> torch.Tensor:
-    """Per bin f: (I - diag(l[f] . l2[f]) U diag(r[f]))^-1 (l2[f] . R0[:, f]); l, r: per-bin (M, N) or None, l2: per-bin
-    (M, N) without gradient (the diagonal of the feedforward path, which also scales the right-hand side).
-    Replaces system.py:417-424 (Recursion.forward: A = I - fF(fB(I)), solve(A, fF(X))) for the FDN structure of
-    reverb.py:117-199 / e8_fdn.py:60-100, where fF is the delay line alone."""
-    if l2.requires_grad:
-        raise ValueError("solve_dud2: the feedforward diagonal must not require a gradient (use solve_dud)")
-    cd = R0.dtype
-    conv = lambda t: None if t is None else (t if t.dtype == cd else t.to(cd))  # noqa: E731
-    return _SolveDUD2.apply(conv(l), conv(l2), conv(U), conv(r), R0)
-
-
-def _solve_scaled_launch(DU, g, adjoint, R):
-    real = _rdtype(R)
-    B, M, N, K, rs_b, rs_n, rs_k = _bnk(R)
-    OUT = _empty_planar(R.shape, R.dtype, R.device)
-    _, _, _, _, os_b, os_n, os_k = _bnk(OUT)
-    L = _lib.lib()
-    fn = L.fl_solve_scaled_c64 if real == torch.float32 else L.fl_solve_scaled_c128
-    with kernel_timer.span("solve_adj" if adjoint else "solve"):
-        _lib.check(fn(DU.data_ptr(), _lead_pitch(DU.movedim(0, -1)), g.data_ptr(), g.stride(0), int(adjoint), R.data_ptr(), rs_b,
-                      rs_n, rs_k, OUT.data_ptr(), os_b, os_n, os_k, B, M, N, K, _stream()), "solve_scaled")
-    return OUT
-
-
 # The scaled loop's forward solve keeps its LU factors for the backward pass's adjoint system when the elimination dominates the
 # solve (N > KEEP_LU_MIN_N) and the factors fit the budget: 8 N^2 bytes per bin in HBM (1.6 GB at the 32 x 32 chain of nfft =
 # 384000) against a second (2/3) N^3 elimination per bin.  False / a smaller budget: the adjoint system is factored again.
@@ -1928,33 +1843,22 @@ KEEP_LU_MIN_N = 16
 KEEP_LU_MAX_BYTES = 16 << 30
 
 
-def _solve_scaled_keep_launch(DU, g, R):
-    real = _rdtype(R)
-    B, M, N, K, rs_b, rs_n, rs_k = _bnk(R)
-    OUT = _empty_planar(R.shape, R.dtype, R.device)
-    _, _, _, _, os_b, os_n, os_k = _bnk(OUT)
+def _solve_scaled_launch(DU, g, adjoint, R, keep=False):
+    """(I - diag(g) DU)^-1 R, its adjoint system, or with keep (forward) -> (OUT, LU, piv): the factors for
+    _solve_kept_adjoint_launch"""
+    scaled = (DU.data_ptr(), _lead_pitch(DU.movedim(0, -1)), g.data_ptr(), g.stride(0))
+    if not keep:
+        return _solve_call("fl_solve_scaled", "solve_adj" if adjoint else "solve", R, *scaled, int(adjoint))
+    assert not adjoint
     L = _lib.lib()
-    f64 = int(real == torch.float64)
+    M, N, f64 = R.shape[1], R.shape[2], int(_rdtype(R) == torch.float64)
     LU = torch.empty(L.fl_solve_kept_lu_elems(N, M, f64), dtype=R.dtype, device=R.device)
     piv = torch.empty(L.fl_solve_kept_piv_elems(N, M, f64), dtype=torch.int32, device=R.device)
-    fn = L.fl_solve_scaled_keep_c64 if real == torch.float32 else L.fl_solve_scaled_keep_c128
-    with kernel_timer.span("solve"):
-        _lib.check(fn(DU.data_ptr(), _lead_pitch(DU.movedim(0, -1)), g.data_ptr(), g.stride(0), R.data_ptr(), rs_b, rs_n, rs_k,
-                      OUT.data_ptr(), os_b, os_n, os_k, B, M, N, K, LU.data_ptr(), piv.data_ptr(), _stream()), "solve_scaled_keep")
-    return OUT, LU, piv
+    return _solve_call("fl_solve_scaled_keep", "solve", R, *scaled, post=(LU.data_ptr(), piv.data_ptr())), LU, piv
 
 
 def _solve_kept_adjoint_launch(LU, piv, R):
-    real = _rdtype(R)
-    B, M, N, K, rs_b, rs_n, rs_k = _bnk(R)
-    OUT = _empty_planar(R.shape, R.dtype, R.device)
-    _, _, _, _, os_b, os_n, os_k = _bnk(OUT)
-    L = _lib.lib()
-    fn = L.fl_solve_kept_adjoint_c64 if real == torch.float32 else L.fl_solve_kept_adjoint_c128
-    with kernel_timer.span("solve_adj"):
-        _lib.check(fn(LU.data_ptr(), piv.data_ptr(), R.data_ptr(), rs_b, rs_n, rs_k, OUT.data_ptr(), os_b,
-                      os_n, os_k, B, M, N, K, _stream()), "solve_kept_adjoint")
-    return OUT
+    return _solve_call("fl_solve_kept_adjoint", "solve_adj", R, LU.data_ptr(), piv.data_ptr())
 
 
 class _SolveScaledLoop(torch.autograd.Function):
@@ -1980,7 +1884,7 @@ class _SolveScaledLoop(torch.autograd.Function):
         keep = (KEEP_LU and any(ctx.needs_input_grad) and KEEP_LU_MIN_N < N <= (64 if _rdtype(Rp) == torch.float32 else 32)
                 and N * N * (M + 64) * Rp.element_size() <= KEEP_LU_MAX_BYTES)
         if keep:
-            OUT, LU, piv = _solve_scaled_keep_launch(DU, gc, Rp)
+            OUT, LU, piv = _solve_scaled_launch(DU, gc, False, Rp, keep=True)
             ctx.save_for_backward(gc, Dp, Uc, DU, OUT, LU, piv)
         else:
             OUT = _solve_scaled_launch(DU, gc, False, Rp)
@@ -2014,14 +1918,6 @@ def solve_scaled_loop(g: torch.Tensor, D: torch.Tensor, U: torch.Tensor, R: torc
     cd = R.dtype
     conv = lambda t: t if t.dtype == cd else t.to(cd)  # noqa: E731
     return _SolveScaledLoop.apply(conv(g), conv(D), conv(U), R)
-
-
-def solve_dud(l: Optional[torch.Tensor], U: torch.Tensor, r: Optional[torch.Tensor], R: torch.Tensor) -> torch.Tensor:
-    """Per bin f: (I - diag(l[f]) U diag(r[f]))^-1 R[:, f] -- the closed loop of a feedback delay
-    network, with the loop matrix kept in factored form (never materialised)."""
-    cd = R.dtype
-    conv = lambda t: None if t is None else (t if t.dtype == cd else t.to(cd))  # noqa: E731
-    return _SolveDUD.apply(conv(l), conv(U), conv(r), R)
 
 
 # ----------------------------------------------------------------------------- responses
