@@ -60,29 +60,22 @@ _SIGNATURES = {
     "fl_spec_walk_partition": (_i, [_i, _i, _i, C.POINTER(_i)]),
     "fl_spec_mid_walk_f32": (_i, [_vp, _vp, _vp, _vp, _l, _l, _i, _vp, _i, _i, _i, _i, _d, _i, _i, _vp, _vp]),
     "fl_spec_gradh_slices": (_i, [_i, _i]),
-    "fl_spec_gradh_walk_f32": (_i, [_vp, _vp, _vp, _l, _l, _l, _i, _vp, _i, _i, _i, _i, _d, _i, _vp]),
+    "fl_spec_gradh_walk_f32": (_i, [_vp, _vp, _vp, _l, _l, _l, _i, _vp, _i, _i, _i, _i, _d, _i, _vp, _vp]),
     "fl_sum_parts_c64": (_i, [_vp, _l, _i, _vp, _l, _vp]),
     "fl_debug_set_walk": (_i, [_i, _i, _i, _vp]),
     "fl_debug_set_walk_stamps": (_i, [_vp]),
     "fl_wall_clock_khz": (_i, []),
-    "fl_spec_cols_inv_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _d, _d, _vp]),
-    "fl_spec_cols_inv_sumsq_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _d, _d, _vp, _vp]),
-    "fl_spec_cols_inv_sumsq_f64": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _d, _d, _vp, _vp]),
+    "fl_spec_cols_inv_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _d, _d, _vp, _vp, _vp, _vp]),
     "fl_spec_cols_blocks_f32": (_i, [_i, _i, _i]),
     "fl_spec_cols_blocks_f64": (_i, [_i, _i, _i]),
     "fl_spec_cols_inv_inplace_ok_f32": (_i, [_i, _i]),
     "fl_spec_cols_inv_inplace_ok_f64": (_i, [_i, _i]),
     "fl_spec_cols_inv_grad_supported_f32": (_i, [_i, _i]),
     "fl_spec_cols_inv_grad_supported_f64": (_i, [_i, _i]),
-    "fl_spec_cols_inv_sumsq_grad_f32": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _d, _vp, _vp]),
-    "fl_spec_cols_inv_sumsq_grad_f64": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _d, _vp, _vp]),
-    "fl_spec_cols_inv_scaled_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _d, _vp, _d, _vp]),
-    "fl_spec_cols_inv_scaled_f64": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _d, _vp, _d, _vp]),
-    "fl_spec_gradh_walk_scaled_f32": (_i, [_vp, _vp, _vp, _l, _l, _l, _i, _vp, _i, _i, _i, _i, _d, _i, _vp, _vp]),
     "fl_mean_square_final_f32": (_i, [_vp, _i, _d, _vp, _vp]),
     "fl_mean_square_final_f64": (_i, [_vp, _i, _d, _vp, _vp]),
     "fl_pack_toggle": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
-    "fl_spec_cols_inv_f64": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _d, _d, _vp]),
+    "fl_spec_cols_inv_f64": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _d, _d, _vp, _vp, _vp, _vp]),
     "fl_permute_bins_c64": (_i, [_vp, _l, _vp, _l, _i, _i, _i, _vp]),
     "fl_permute_bins_c128": (_i, [_vp, _l, _vp, _l, _i, _i, _i, _vp]),
     "fl_mimo_c64": (_i, [_vp, _l, _l, _l, _i, _vp, _l, _l, _l, _vp, _l, _l, _l, _i, _i, _i, _i, _i, _vp]),

@@ -1379,8 +1379,6 @@ int FL_SPEC_FN(fl_spec_cols_fwd)(const void* x, int Bn, int t_len, int G, void* 
     return cols_launch(false, a, Bn, (hipStream_t)stream);
 }
 
-static int cols_inv_impl(const void* S2, void* y, int Bn, int t_len, int t_out, int G, const void* W, int nfft, double scale,
-                         double env_log2, double* sumsq, void* stream, const real_t* dev_scale = nullptr, void* Sg = nullptr);
 // the fused gradient pass (spec_cols_inv<..., FUSE>) exists where one thread takes one second-stage item of the tile (first radix
 // of the column plan x tile width <= 256: every plan but the 441- and 800-point columns and the 32-wide tile of 16-point radices)
 static int cols_first_radix(int l1) {      // A of launch_cols<A, B> (cols_launch)
@@ -1397,15 +1395,6 @@ static bool cols_inv_grad_ok(int nfft, int G) {
     const int a_len = cols_first_radix(l1);
     return a_len && a_len * cols_vt(G, l1) <= 256;      // (cols_vt: the tile width cols_launch takes)
 }
-int FL_SPEC_FN(fl_spec_cols_inv)(const void* S2, void* y, int Bn, int t_len, int t_out, int G, const void* W, int nfft, double scale,
-                         double env_log2, void* stream) {
-    return cols_inv_impl(S2, y, Bn, t_len, t_out, G, W, nfft, scale, env_log2, nullptr, stream);
-}
-int FL_SPEC_FN(fl_spec_cols_inv_sumsq)(const void* S2, void* y, int Bn, int t_len, int t_out, int G, const void* W, int nfft, double scale,
-                               double env_log2, void* sumsq_parts, void* stream) {
-    FL_REQUIRE(sumsq_parts, "spec_cols_inv_sumsq: null pointer");
-    return cols_inv_impl(S2, y, Bn, t_len, t_out, G, W, nfft, scale, env_log2, (double*)sumsq_parts, stream);
-}
 /* 1: the inverse column pass may write y over its own input (y = S2's storage read as real (Bn, nfft, G)): a workgroup's tile of
  * samples occupies the bytes of the tile of column values it has read in full before its first store -- when one tile carries
  * all G channels (G <= the tile width) and every sample is stored (t_len = t_out = nfft) */
@@ -1415,17 +1404,6 @@ int FL_SPEC_FN(fl_spec_cols_inv_inplace_ok)(int nfft, int G) {
     return G <= cols_vt(G, l1) ? 1 : 0;
 }
 int FL_SPEC_FN(fl_spec_cols_inv_grad_supported)(int nfft, int G) { return cols_inv_grad_ok(nfft, G) ? 1 : 0; }
-int FL_SPEC_FN(fl_spec_cols_inv_sumsq_grad)(const void* S2, void* y, void* Sg, int Bn, int G, const void* W, int nfft, double scale,
-                                    void* sumsq_parts, void* stream) {
-    FL_REQUIRE(sumsq_parts && Sg, "spec_cols_inv_sumsq_grad: null pointer");
-    FL_REQUIRE(cols_inv_grad_ok(nfft, G), "spec_cols_inv_sumsq_grad: shape not taken (fl_spec_cols_inv_grad_supported)");
-    return cols_inv_impl(S2, y, Bn, nfft, nfft, G, W, nfft, scale, 0.0, (double*)sumsq_parts, stream, nullptr, Sg);
-}
-int FL_SPEC_FN(fl_spec_cols_inv_scaled)(const void* S2, void* y, int Bn, int t_len, int t_out, int G, const void* W, int nfft, double scale,
-                                const void* dev_scale, double env_log2, void* stream) {
-    FL_REQUIRE(dev_scale, "spec_cols_inv_scaled: null pointer");
-    return cols_inv_impl(S2, y, Bn, t_len, t_out, G, W, nfft, scale, env_log2, nullptr, stream, (const real_t*)dev_scale);
-}
 int FL_SPEC_FN(fl_spec_cols_blocks)(int nfft, int Bn, int G) {      // workgroups of a column pass = entries of sumsq_parts
     ColsArgs a = {};
     static const real_t dummy = 0;
@@ -1433,10 +1411,16 @@ int FL_SPEC_FN(fl_spec_cols_blocks)(int nfft, int Bn, int G) {      // workgroup
     if (cols_setup(a, nfft, Bn, 0, 0, G, &dummy, cols_vt_of(nfft, G))) return -1;
     return Bn * a.nct * a.ngt;
 }
-}  // extern "C"
-static int cols_inv_impl(const void* S2, void* y, int Bn, int t_len, int t_out, int G, const void* W, int nfft, double scale,
-                         double env_log2, double* sumsq, void* stream, const real_t* dev_scale, void* Sg) {
+/* sumsq_parts (double, fl_spec_cols_blocks entries: the workgroups' partial sums of y^2), dev_scale (a device scalar of the real
+ * type multiplied into `scale`) and Sg (the column pass of y's own forward transform, formed from the tiles: needs sumsq_parts,
+ * every sample stored, no envelope and a shape of fl_spec_cols_inv_grad_supported) are optional: null = absent */
+int FL_SPEC_FN(fl_spec_cols_inv)(const void* S2, void* y, int Bn, int t_len, int t_out, int G, const void* W, int nfft, double scale,
+                         double env_log2, void* sumsq_parts, const void* dev_scale, void* Sg, void* stream) {
     FL_REQUIRE(S2 && y, "spec_cols_inv: null pointer");
+    if (Sg) {
+        FL_REQUIRE(sumsq_parts && t_len == nfft && t_out == nfft && env_log2 == 0.0, "spec_cols_inv: Sg needs sumsq_parts, t_len = t_out = nfft and no envelope");
+        FL_REQUIRE(cols_inv_grad_ok(nfft, G), "spec_cols_inv: Sg at a shape not taken (fl_spec_cols_inv_grad_supported)");
+    }
     FL_REQUIRE(reinterpret_cast<uintptr_t>(y) % (2 * RSZ) == 0, "spec_cols_inv: y must be aligned to two samples");
     FL_REQUIRE(t_out >= 0 && t_out <= t_len, "spec_cols_inv: t_out must be in [0, t_len]");
     if (Bn == 0) return FL_OK;
@@ -1447,14 +1431,13 @@ static int cols_inv_impl(const void* S2, void* y, int Bn, int t_len, int t_out, 
     a.S = (cf*)S2;
     a.scale = (real_t)scale;
     a.env_log2 = env_log2;
-    a.sumsq = sumsq;
-    a.dev_scale = dev_scale;
+    a.sumsq = (double*)sumsq_parts;
+    a.dev_scale = (const real_t*)dev_scale;
     a.Sg = (cf*)Sg;
     a.pol = ((stream_policy() >> 2) & 3u) | ((stream_policy() & POL_INV_SG_NT) ? 4u : 0u);      // POL_INV_LD_NT, POL_INV_ST_NT, POL_INV_SG_NT
     a.stamp = walk_successor_stamp();
     return cols_launch(true, a, Bn, (hipStream_t)stream);
 }
-extern "C" {
 
 int FL_SPEC_FN(fl_spec_mid)(const void* S, void* S2, void* Xs, long xs_b, long xs_n, const void* H, long hs_m, long hs_n, int conj_h,
                     const void* W, int nfft, int Bn, int NI, int NO, double spec_scale, int spec_interior2, int pre_half,

@@ -980,19 +980,9 @@ int fl_spec_gradh_slices(int nfft, int Bn) {
     return ns < Bn ? ns : Bn;
 }
 
-static int gradh_walk_impl(const void* Sg, const void* Xp, void* dH_parts, long ds_s, long ds_m, long ds_n, int n_slices, const void* W,
-                           int nfft, int Bn, int NI, int NO, double scale_g, int interior2_g, const float* out_scale, void* stream);
+// out_scale: optional float device scalar multiplied in on the way out (null: absent)
 int fl_spec_gradh_walk_f32(const void* Sg, const void* Xp, void* dH_parts, long ds_s, long ds_m, long ds_n, int n_slices, const void* W,
-                           int nfft, int Bn, int NI, int NO, double scale_g, int interior2_g, void* stream) {
-    return gradh_walk_impl(Sg, Xp, dH_parts, ds_s, ds_m, ds_n, n_slices, W, nfft, Bn, NI, NO, scale_g, interior2_g, nullptr, stream);
-}
-int fl_spec_gradh_walk_scaled_f32(const void* Sg, const void* Xp, void* dH_parts, long ds_s, long ds_m, long ds_n, int n_slices, const void* W,
-                                  int nfft, int Bn, int NI, int NO, double scale_g, int interior2_g, const void* out_scale, void* stream) {
-    return gradh_walk_impl(Sg, Xp, dH_parts, ds_s, ds_m, ds_n, n_slices, W, nfft, Bn, NI, NO, scale_g, interior2_g, (const float*)out_scale, stream);
-}
-}  // extern "C"
-static int gradh_walk_impl(const void* Sg, const void* Xp, void* dH_parts, long ds_s, long ds_m, long ds_n, int n_slices, const void* W,
-                           int nfft, int Bn, int NI, int NO, double scale_g, int interior2_g, const float* out_scale, void* stream) {
+                           int nfft, int Bn, int NI, int NO, double scale_g, int interior2_g, const void* out_scale, void* stream) {
     FL_REQUIRE(Sg && Xp && dH_parts && W, "spec_gradh_walk: null pointer");
     FL_REQUIRE(n_slices >= 1 && n_slices <= (Bn > 0 ? Bn : 1), "spec_gradh_walk: slices must be in [1, batch]");
     FL_REQUIRE(reinterpret_cast<uintptr_t>(Sg) % 16 == 0 && reinterpret_cast<uintptr_t>(Xp) % 16 == 0, "spec_gradh_walk: scratch arrays must be 16-byte aligned");
@@ -1002,7 +992,7 @@ static int gradh_walk_impl(const void* Sg, const void* Xp, void* dH_parts, long 
     if (rc) return rc;
     a.Sg = (const cf*)Sg; a.Xp = (const cf*)Xp; a.dH = (cf*)dH_parts; a.ds_s = ds_s; a.ds_m = ds_m; a.ds_n = ds_n;
     a.W = (const cf*)W; a.n = nfft; a.L = nfft / 2; a.Bn = Bn; a.NS = n_slices;
-    a.scale_g = (float)scale_g; a.interior2_g = interior2_g; a.dbg_times = g_walk_times; a.out_scale = out_scale;
+    a.scale_g = (float)scale_g; a.interior2_g = interior2_g; a.dbg_times = g_walk_times; a.out_scale = (const float*)out_scale;
     a.pol = stream_policy();
     FL_REQUIRE((size_t)NO * (size_t)ds_m * 8ull < (1ull << 32), "spec_gradh_walk: a partial plane set exceeds 32-bit offsets");
     const int P = a.L1 / 2 + 1;
@@ -1057,7 +1047,6 @@ static int gradh_walk_impl(const void* Sg, const void* Xp, void* dH_parts, long 
     FL_CHECK_LAUNCH("spec_gradh_walk");
     return FL_OK;
 }
-extern "C" {
 
 int fl_sum_parts_c64(const void* parts, long part_stride, int n_parts, void* out, long n, void* stream) {
     FL_REQUIRE(parts && out && n_parts >= 1 && n >= 0, "sum_parts: bad arguments");

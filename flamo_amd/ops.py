@@ -12,6 +12,7 @@ pass over (B, M, ...) data is one of the HIP kernels.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import threading
 from collections import namedtuple
@@ -75,6 +76,19 @@ def _sfx(real: torch.dtype, cplx: bool) -> str:
     return "f32" if real == torch.float32 else "f64"
 
 
+def _fn(name: str, real: torch.dtype, cplx: bool = False):
+    """The library's entry ``name`` for this precision (fl_x_f32 / _f64, or _c64 / _c128 with ``cplx``), fetched through
+    _lib.lib() when it is asked for -- where a launch recorded in an open pair goes out first (paired_launch)."""
+    return getattr(_lib.lib(), f"{name}_{_sfx(real, cplx)}")
+
+
+_spec_fn = _fn      # (the name the fused pipeline's tests ask the library's shape queries by)
+
+
+def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    return None if t is None else t.data_ptr()
+
+
 def _prod(xs) -> int:
     p = 1
     for v in xs:
@@ -100,11 +114,11 @@ def twiddles(nfft: int, real: torch.dtype, device: torch.device) -> torch.Tensor
                 # tables of the fused pipeline's lengths carry its contiguous copies behind the nfft entries
                 aux = int(L.fl_spec_aux_elems(int(nfft)))
                 W = torch.empty(nfft + aux, dtype=_cdtype(real), device=device)
-                fn = L.fl_twiddle_fill_f32 if real == torch.float32 else L.fl_twiddle_fill_f64
+                fn = _fn("fl_twiddle_fill", real)
                 cur = torch.cuda.current_stream(device)
                 _lib.check(fn(W.data_ptr(), nfft, cur.cuda_stream), "twiddle_fill")
                 if aux:
-                    fill = L.fl_spec_aux_fill_f32 if real == torch.float32 else L.fl_spec_aux_fill_f64
+                    fill = _fn("fl_spec_aux_fill", real)
                     _lib.check(fill(W.data_ptr(), nfft, cur.cuda_stream), "spec_aux_fill")
                 ev = torch.cuda.Event()
                 ev.record(cur)
@@ -500,7 +514,7 @@ def _rfft_launch(xp: torch.Tensor, t_in: int, nfft: int, scale: float, env_log2:
     f64 = int(real == torch.float64)
     n_scr = L.fl_fft_scratch_elems(nfft, f64, nsig)
     scratch = torch.empty(max(n_scr, 1), dtype=_cdtype(real), device=dev)
-    fn = L.fl_rfft_f64 if f64 else L.fl_rfft_f32
+    fn = _fn("fl_rfft", real)
     _lib.check(fn(xp.data_ptr(), x_pitch, t_in, X.data_ptr(), _pitch(M),
                   scratch.data_ptr(), twiddles(nfft, real, dev).data_ptr(), nsig, nfft, scale, env_log2, interior_x2,
                   _stream()), "rfft")
@@ -528,7 +542,7 @@ def _rfft_launch_ci(x: torch.Tensor, nfft: int, scale: float, env_log2: float, i
     f64 = int(real == torch.float64)
     n_scr = L.fl_fft_scratch_elems(nfft, f64, nsig)
     scratch = torch.empty(max(n_scr, 1), dtype=_cdtype(real), device=dev)
-    fn = L.fl_rfft_ci_f64 if f64 else L.fl_rfft_ci_f32
+    fn = _fn("fl_rfft_ci", real)
     _lib.check(fn(x.data_ptr(), C_, T, X.data_ptr(), _pitch(M), scratch.data_ptr(),
                   twiddles(nfft, real, dev).data_ptr(), nsig, nfft, scale, env_log2, interior_x2, _stream()), "rfft_ci")
     return X.movedim(-1, 1)
@@ -558,7 +572,7 @@ def _irfft_launch(Xp: torch.Tensor, nfft: int, t_out: int, t_alloc: int, scale: 
     f64 = int(real == torch.float64)
     n_scr = L.fl_fft_scratch_elems(nfft, f64, nsig)
     scratch = torch.empty(max(n_scr, 1), dtype=_cdtype(real), device=dev)
-    fn = L.fl_irfft_f64 if f64 else L.fl_irfft_f32
+    fn = _fn("fl_irfft", real)
     _lib.check(fn(Xp.data_ptr(), X_pitch, y.data_ptr(), t_alloc, t_out, scratch.data_ptr(),
                   twiddles(nfft, real, dev).data_ptr(), nsig, nfft, scale, env_log2, interior_half, _stream()), "irfft")
     return y.movedim(-1, 1)
@@ -748,14 +762,13 @@ def irfft(X: torch.Tensor, nfft: int, norm: str = "backward", alias_decay_db: Op
 # boundary (the spectrum kept for the backward pass, H, dL/dH) is bin-planar in ROW-MAJOR BIN ORDER
 # (bin k = k1 + L1 k2 at element k1 L2 + k2).  float32 and float64 (the same kernels compiled for double, one workgroup per
 # (row pair, batch item) and equal channel counts only); everything else takes the layered operators above.
+# ---- one layer over the fl_spec_* entries, each called from ONE place (_spec_cols_fwd, _spec_mid, _spec_mid_walk, _spec_cols_inv,
+# ---- _spec_gradh_loop, _spec_gradh_walk); the route is named once each way: _spec_route (forward, kept in _SpecCfg.route) and
+# ---- _spec_backward_route
 def spectral_supported(nfft: int, n_in: int, n_out: int, real: torch.dtype = torch.float32) -> bool:
     L = _lib.lib()
     fn = L.fl_spec_supports if real == torch.float32 else L.fl_spec_supports_f64
     return bool(fn(int(nfft), int(n_in), int(n_out)))
-
-
-def _spec_fn(name: str, real: torch.dtype):
-    return getattr(_lib.lib(), name + ("_f32" if real == torch.float32 else "_f64"))
 
 
 class _PermuteBins(torch.autograd.Function):
@@ -772,9 +785,8 @@ class _PermuteBins(torch.autograd.Function):
         Hp = _h_planar(H.resolve_conj(), True)
         rest = tuple(H.shape[1:])
         out = _empty_rows(rest, M, H.dtype, H.device)
-        fn = _lib.lib().fl_permute_bins_c64 if H.dtype == torch.complex64 else _lib.lib().fl_permute_bins_c128
-        _lib.check(fn(Hp.data_ptr(), _lead_pitch(Hp.movedim(0, -1)), out.data_ptr(), _pitch(M),
-                      max(_prod(rest), 1), nfft, int(inverse), _stream()), "permute_bins")
+        _lib.check(_fn("fl_permute_bins", _rdtype(H), True)(Hp.data_ptr(), _lead_pitch(Hp.movedim(0, -1)), out.data_ptr(), _pitch(M),
+                                                             max(_prod(rest), 1), nfft, int(inverse), _stream()), "permute_bins")
         ctx.cfg = (nfft, inverse)
         return out.movedim(-1, 0)
 
@@ -890,7 +902,7 @@ def _spec_cols_fwd(x, nfft, env_log2, site=0):
     try:
         with kernel_timer.span("spec_cols_fwd+response" if (not site and kernel_timer.enabled and L.fl_launch_pair_pending())
                                else "spec_cols_fwd"):
-            fn = L.fl_spec_cols_fwd_f32 if x.dtype == torch.float32 else L.fl_spec_cols_fwd_f64
+            fn = getattr(L, "fl_spec_cols_fwd_" + _sfx(x.dtype, False))      # (from L: _fn's handle would issue the recorded launch)
             _lib.check(fn(x.data_ptr(), B, T, G, S.data_ptr(), W.data_ptr(), nfft, env_log2, _stream()), "spec_cols_fwd")
     finally:
         if site:
@@ -898,6 +910,14 @@ def _spec_cols_fwd(x, nfft, env_log2, site=0):
         elif getattr(_lib._pair, "keep", None):
             _pair_issued()      # this launch carried the recorded one
     return S
+
+
+def _h_strides(Hrm, conj_t):
+    """(hs_m, hs_n): element strides between the output and the input channels of a bin-planar response view (M, NO_h, NI_h);
+    conj_t: of its transpose"""
+    hp = _lead_pitch(Hrm.movedim(0, -1))
+    hs_m, hs_n = Hrm.shape[2] * hp, hp
+    return (hs_n, hs_m) if conj_t else (hs_m, hs_n)
 
 
 def _spec_mid(S, B, NI, NO, nfft, Hrm, conj_t, want_spec, want_inverse, spec_scale, interior2, pre_half):
@@ -909,20 +929,13 @@ def _spec_mid(S, B, NI, NO, nfft, Hrm, conj_t, want_spec, want_inverse, spec_sca
     S2 = None
     if want_inverse:
         S2 = S if NI == NO else torch.empty(B * (nfft // 2) * NO, dtype=S.dtype, device=dev)   # row pairs are private: in place
-    hp = hs_m = hs_n = 0
-    if Hrm is not None:
-        hp = _lead_pitch(Hrm.movedim(0, -1))
-        hs_m, hs_n = Hrm.shape[2] * hp, hp
-        if conj_t:
-            hs_m, hs_n = hs_n, hs_m
+    hs_m, hs_n = _h_strides(Hrm, conj_t) if Hrm is not None else (0, 0)
     P = _pitch(M)
     tag = f"spec_mid[{NI}->{NO}" + (",H" if Hrm is not None else "") + (",inv" if want_inverse else "") + (",spec" if want_spec else "") + "]"
     with kernel_timer.span(tag):
-        _lib.check(_spec_fn("fl_spec_mid", real)(S.data_ptr(), None if S2 is None else S2.data_ptr(),
-                                                 None if Xs is None else Xs.data_ptr(), NI * P, P,
-                                                 None if Hrm is None else Hrm.data_ptr(), hs_m, hs_n, int(bool(conj_t)),
-                                                 twiddles(nfft, real, dev).data_ptr(), nfft, B, NI, NO, spec_scale,
-                                                 int(interior2), int(pre_half), _stream()), "spec_mid")
+        _lib.check(_fn("fl_spec_mid", real)(S.data_ptr(), _ptr(S2), _ptr(Xs), NI * P, P, _ptr(Hrm), hs_m, hs_n, int(bool(conj_t)),
+                                            twiddles(nfft, real, dev).data_ptr(), nfft, B, NI, NO, spec_scale,
+                                            int(interior2), int(pre_half), _stream()), "spec_mid")
     return S2, Xs
 
 
@@ -932,47 +945,34 @@ def _spec_cols_inv(S2, B, t_len, t_out, G, nfft, scale, env_log2, want_sumsq=Fal
     shape): also Sg = _spec_cols_fwd(y), formed by the same launch from its tiles (-> y, parts, Sg)"""
     alloc = torch.zeros if t_len > t_out else torch.empty
     real = _rdtype(S2)
+    dev = S2.device
     if INVERSE_IN_PLACE and t_len == t_out == nfft and S2.numel() == B * (nfft // 2) * G and S2.is_contiguous() and \
-            _spec_fn("fl_spec_cols_inv_inplace_ok", real)(nfft, G):
+            _fn("fl_spec_cols_inv_inplace_ok", real)(nfft, G):
         # y over the scratch it is transformed from (a workgroup's tile of samples is the bytes of the tile of column values it
         # has read before its first store): one streaming array less in the step -- the arrays' total, not only the passes'
         # bytes, is what the memory-side cache sees
         # (a tensor of its own over the same storage, not a view of S2: the caller hands it out as a Function's output)
-        y = torch.empty(0, dtype=real, device=S2.device).set_(S2.untyped_storage(), 2 * S2.storage_offset(), (B, t_len, G))
+        y = torch.empty(0, dtype=real, device=dev).set_(S2.untyped_storage(), 2 * S2.storage_offset(), (B, t_len, G))
     else:
-        y = alloc((B, t_len, G), dtype=real, device=S2.device)
-    parts = None
+        y = alloc((B, t_len, G), dtype=real, device=dev)
+    if dev_scale is not None and (dev_scale.dtype != real or not dev_scale.is_cuda or dev_scale.numel() != 1):
+        raise ValueError("spec_cols_inv: dev_scale must be one device scalar of the signal's dtype")
+    parts = Sg = None
+    if want_sumsq:
+        nblk = int(_fn("fl_spec_cols_blocks", real)(nfft, B, G))
+        parts = torch.empty(max(nblk, 1), dtype=torch.float64, device=dev)
     if grad_cols:
         assert want_sumsq and t_len == t_out == nfft and env_log2 == 0.0
-        nblk = int(_spec_fn("fl_spec_cols_blocks", real)(nfft, B, G))
-        parts = torch.empty(max(nblk, 1), dtype=torch.float64, device=S2.device)
         # (sg_buf: a dead scratch array of the same size -- the forward transform's column pass, consumed by the row kernel --
         # so that the step's streaming arrays stay four, as without the fused pass)
         n_sg = B * (nfft // 2) * G
         Sg = sg_buf if sg_buf is not None and sg_buf.numel() == n_sg and sg_buf.dtype == S2.dtype and sg_buf.data_ptr() != S2.data_ptr() \
-            else torch.empty(n_sg, dtype=S2.dtype, device=S2.device)
-        with kernel_timer.span("spec_cols_inv+grad_cols"):
-            _lib.check(_spec_fn("fl_spec_cols_inv_sumsq_grad", real)(S2.data_ptr(), y.data_ptr(), Sg.data_ptr(), B, G,
-                                                                     twiddles(nfft, real, S2.device).data_ptr(), nfft, scale,
-                                                                     parts.data_ptr(), _stream()), "spec_cols_inv_sumsq_grad")
+            else torch.empty(n_sg, dtype=S2.dtype, device=dev)
+    with kernel_timer.span("spec_cols_inv+grad_cols" if grad_cols else "spec_cols_inv"):
+        _lib.check(_fn("fl_spec_cols_inv", real)(S2.data_ptr(), y.data_ptr(), B, t_len, t_out, G, twiddles(nfft, real, dev).data_ptr(),
+                                                 nfft, scale, env_log2, _ptr(parts), _ptr(dev_scale), _ptr(Sg), _stream()), "spec_cols_inv")
+    if grad_cols:
         return y, parts, Sg
-    with kernel_timer.span("spec_cols_inv"):
-        if want_sumsq:
-            nblk = int(_spec_fn("fl_spec_cols_blocks", real)(nfft, B, G))
-            parts = torch.empty(max(nblk, 1), dtype=torch.float64, device=S2.device)
-            _lib.check(_spec_fn("fl_spec_cols_inv_sumsq", real)(S2.data_ptr(), y.data_ptr(), B, t_len, t_out, G,
-                                                                twiddles(nfft, real, S2.device).data_ptr(), nfft, scale, env_log2,
-                                                                parts.data_ptr(), _stream()), "spec_cols_inv_sumsq")
-        elif dev_scale is not None:
-            if dev_scale.dtype != real or not dev_scale.is_cuda or dev_scale.numel() != 1:
-                raise ValueError("spec_cols_inv: dev_scale must be one device scalar of the signal's dtype")
-            _lib.check(_spec_fn("fl_spec_cols_inv_scaled", real)(S2.data_ptr(), y.data_ptr(), B, t_len, t_out, G,
-                                                                 twiddles(nfft, real, S2.device).data_ptr(), nfft, scale,
-                                                                 dev_scale.data_ptr(), env_log2, _stream()), "spec_cols_inv_scaled")
-        else:
-            _lib.check(_spec_fn("fl_spec_cols_inv", real)(S2.data_ptr(), y.data_ptr(), B, t_len, t_out, G,
-                                                          twiddles(nfft, real, S2.device).data_ptr(), nfft, scale, env_log2,
-                                                          _stream()), "spec_cols_inv")
     return (y, parts) if want_sumsq else y
 
 
@@ -996,7 +996,6 @@ def _walk_partition(nfft: int, B: int, dev: torch.device) -> torch.Tensor:
     key = (int(nfft), int(B), n_wg, dev.index if dev.index is not None else torch.cuda.current_device())
     t = _walk_bounds.get(key)
     if t is None:
-        import ctypes
         host = (ctypes.c_int * (n_wg + 1))()
         _lib.check(L.fl_spec_walk_partition(nfft, B, n_wg, host), "spec_walk_partition")
         if torch.cuda.is_current_stream_capturing():
@@ -1014,16 +1013,12 @@ def _spec_mid_walk(S, B, NI, NO, nfft, Hrm, conj_t, want_spec, spec_scale, inter
     bounds = _walk_partition(nfft, B, dev)
     S2 = torch.empty(B * (nfft // 2) * NO, dtype=torch.complex64, device=dev)
     Xp = torch.empty(int(L.fl_spec_walk_spectrum_elems(nfft, B, NI)), dtype=torch.complex64, device=dev) if want_spec else None
-    hp = _lead_pitch(Hrm.movedim(0, -1))
-    hs_m, hs_n = Hrm.shape[2] * hp, hp
-    if conj_t:
-        hs_m, hs_n = hs_n, hs_m
+    hs_m, hs_n = _h_strides(Hrm, conj_t)
     tag = f"spec_mid_walk[{NI}->{NO}" + (",spec" if want_spec else "") + "]"
     with kernel_timer.span(tag):
-        _lib.check(L.fl_spec_mid_walk_f32(S.data_ptr(), S2.data_ptr(), None if Xp is None else Xp.data_ptr(), Hrm.data_ptr(), hs_m, hs_n,
+        _lib.check(L.fl_spec_mid_walk_f32(S.data_ptr(), S2.data_ptr(), _ptr(Xp), Hrm.data_ptr(), hs_m, hs_n,
                                           int(bool(conj_t)), twiddles(nfft, torch.float32, dev).data_ptr(), nfft, B, NI, NO, spec_scale,
-                                          int(interior2), int(pre_half), None if bounds is None else bounds.data_ptr(), _stream()),
-                   "spec_mid_walk")
+                                          int(interior2), int(pre_half), _ptr(bounds), _stream()), "spec_mid_walk")
     return S2, Xp
 
 
@@ -1037,7 +1032,7 @@ GRADH_LOOP = True      # False: the layered backward (spec_mid without a respons
 GRADH_LOOP_MAX_BATCH = 4
 
 
-def _spec_gradh_loop(Sg, Xs, B, NI, NO, nfft, scale_g, host_factor, out_scale):
+def _spec_gradh_loop(Sg, Xs, B, NI, NO, nfft, scale_g, host_factor=1.0, out_scale=None):
     """dL/dH (M, NO, NI) view in row-major bin order from the gradient's column pass Sg and the kept spectrum Xs (B, NI, P)"""
     dev = Sg.device
     M = nfft // 2 + 1
@@ -1045,10 +1040,9 @@ def _spec_gradh_loop(Sg, Xs, B, NI, NO, nfft, scale_g, host_factor, out_scale):
     P = _pitch(M)
     dH = _empty_rows((NO, NI), M, Sg.dtype, dev)
     with kernel_timer.span("spec_gradh_loop"):
-        _lib.check(_spec_fn("fl_spec_gradh_loop", real)(Sg.data_ptr(), Xs.data_ptr(), NI * P, P, dH.data_ptr(), NI * P, P,
-                                                        twiddles(nfft, real, dev).data_ptr(), nfft, B, NI, NO, float(scale_g), 1,
-                                                        float(host_factor), None if out_scale is None else out_scale.data_ptr(),
-                                                        _stream()), "spec_gradh_loop")
+        _lib.check(_fn("fl_spec_gradh_loop", real)(Sg.data_ptr(), Xs.data_ptr(), NI * P, P, dH.data_ptr(), NI * P, P,
+                                                   twiddles(nfft, real, dev).data_ptr(), nfft, B, NI, NO, float(scale_g), 1,
+                                                   float(host_factor), _ptr(out_scale), _stream()), "spec_gradh_loop")
     return dH.movedim(-1, 0)
 
 
@@ -1062,10 +1056,9 @@ def _spec_gradh_walk(Sg, Xp, B, NI, NO, nfft, scale_g, out_scale=None):
     ns = int(L.fl_spec_gradh_slices(nfft, B))
     parts = torch.empty((ns, NO, NI, P), dtype=torch.complex64, device=dev)
     with kernel_timer.span("spec_gradh_walk"):
-        _lib.check(L.fl_spec_gradh_walk_scaled_f32(Sg.data_ptr(), Xp.data_ptr(), parts.data_ptr(), NO * NI * P, NI * P, P, ns,
-                                                   twiddles(nfft, torch.float32, dev).data_ptr(), nfft, B, NI, NO, scale_g, 1,
-                                                   None if out_scale is None else out_scale.data_ptr(), _stream()),
-                   "spec_gradh_walk")
+        _lib.check(L.fl_spec_gradh_walk_f32(Sg.data_ptr(), Xp.data_ptr(), parts.data_ptr(), NO * NI * P, NI * P, P, ns,
+                                            twiddles(nfft, torch.float32, dev).data_ptr(), nfft, B, NI, NO, scale_g, 1,
+                                            _ptr(out_scale), _stream()), "spec_gradh_walk")
     if ns == 1:
         out = parts[0]
     else:
@@ -1073,6 +1066,41 @@ def _spec_gradh_walk(Sg, Xp, B, NI, NO, nfft, scale_g, out_scale=None):
         with kernel_timer.span("sum_parts"):
             _lib.check(L.fl_sum_parts_c64(parts.data_ptr(), NO * NI * P, ns, out.data_ptr(), NO * NI * P, _stream()), "sum_parts")
     return out[..., :M].movedim(-1, 0)
+
+
+class _SpecCfg(NamedTuple):
+    """What one evaluation of the pipeline fixed: the autograd node keeps it, the tag on its output carries it (_SpectralTag)"""
+    nfft: int
+    scale_f: float
+    env_f: float
+    scale_i: float
+    env_i: float
+    T: int
+    NI: int
+    NO: int
+    route: str       # of the forward pass: "walk" | "rows" (_spec_route)
+
+
+def _spec_route(real, nfft, B, NI, NO) -> str:
+    """The forward pass's row kernel: "walk" (spec_mid_walk: float32, from _WALK_MIN_BATCH items on, 2 / 4 / 8 channels) or
+    "rows" (spec_mid)"""
+    return "walk" if real == torch.float32 and _walk_applies(nfft, B, NI, NO) else "rows"
+
+
+def _spec_backward_route(cfg, real, B, need_x, need_h) -> str:
+    """How dL/dH is formed: "walk" (spec_gradh_walk from the pair-major spectrum the walking forward kept), "loop" (the response's
+    gradient alone -- the training step: the data tensor takes no gradient, trainer.py:172-191 -- in one launch that walks the
+    batch, the gradient's spectrum is never written and read back: fl_spec_gradh_loop_*) or "layered" (spec_mid + mimo_gradh)"""
+    if cfg.route == "walk":
+        return "walk"
+    if need_h and not need_x and GRADH_LOOP and B <= GRADH_LOOP_MAX_BATCH and _fn("fl_spec_gradh_loop_supports", real)(cfg.nfft, cfg.NI, cfg.NO):
+        return "loop"
+    return "layered"
+
+
+# Rides on the tensor _SpectralApply returns (attribute ``_flamo_sa``): the inputs and kept arrays of that evaluation (Xs, Sg: or
+# None), its _SpecCfg, the partial sums of y^2 and y's version -- for an objective computed from y alone (mean_square)
+_SpectralTag = namedtuple("_SpectralTag", "x Hrm Hp Xs cfg parts version Sg")
 
 
 class _SpectralApply(torch.autograd.Function):
@@ -1093,95 +1121,77 @@ class _SpectralApply(torch.autograd.Function):
         Hp = _h_planar(Hrm.resolve_conj(), True)
         B, T = xc.shape[0], xc.shape[1]
         S = _spec_cols_fwd(xc, nfft, env_f)
-        walk = x.dtype == torch.float32 and _walk_applies(nfft, B, NI, NO)
-        if walk:
+        cfg = _SpecCfg(nfft, scale_f, env_f, scale_i, env_i, T, NI, NO, _spec_route(x.dtype, nfft, B, NI, NO))
+        if cfg.route == "walk":
             S2, Xs = _spec_mid_walk(S, B, NI, NO, nfft, Hp, False, ctx.needs_input_grad[1], scale_f, 0, 0)
         else:
             S2, Xs = _spec_mid(S, B, NI, NO, nfft, Hp, False, ctx.needs_input_grad[1], True, scale_f, 0, 0)
         # (the gradient's first pass rides in the inverse pass when this operator's output went into mean_square the last time
         # it ran with this shape -- _grad_cols_key / GRAD_COLS_IN_FORWARD)
         key = _grad_cols_key(x, nfft, NI, NO)
-        Sg = None
-        if GRAD_COLS_IN_FORWARD and key in _GRAD_COLS_SEEN and env_i == 0.0 and any(ctx.needs_input_grad[:2]) and \
-                _spec_fn("fl_spec_cols_inv_grad_supported", x.dtype)(nfft, NO):
-            y, parts, Sg = _spec_cols_inv(S2, B, nfft, nfft, NO, nfft, scale_i, env_i, want_sumsq=True, grad_cols=True, sg_buf=S)
-        else:
-            y, parts = _spec_cols_inv(S2, B, nfft, nfft, NO, nfft, scale_i, env_i, want_sumsq=True)
-        ctx.save_for_backward(Hp, *([Xs] if Xs is not None else []))
-        ctx.cfg = (nfft, scale_f, env_f, scale_i, env_i, T, NI, NO, walk)
-        ctx.speculated = key if Sg is not None else None
+        ahead = bool(GRAD_COLS_IN_FORWARD and key in _GRAD_COLS_SEEN and env_i == 0.0 and any(ctx.needs_input_grad[:2]) and
+                     _fn("fl_spec_cols_inv_grad_supported", x.dtype)(nfft, NO))
+        y, parts, *sg = _spec_cols_inv(S2, B, nfft, nfft, NO, nfft, scale_i, env_i, want_sumsq=True, grad_cols=ahead, sg_buf=S)
+        ctx.save_for_backward(Hp, Xs)        # (no spectrum kept: saved as None, no tensor is held for it)
+        ctx.cfg = cfg
+        ctx.speculated = key if ahead else None
         # what an objective computed from y alone can reuse (mean_square): the partial sums the inverse pass left behind, and
         # everything the backward pass needs -- see _SpectralMeanSquare (not on an inference tensor: it has no version counter,
         # and nothing differentiates it)
         if not y.is_inference():
-            y._flamo_sa = _SpectralTag(x, Hrm, Hp, Xs, ctx.cfg, parts, y._version, Sg, key)
+            y._flamo_sa = _SpectralTag(x, Hrm, Hp, Xs, cfg, parts, y._version, sg[0] if ahead else None)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        Hp, *kept = ctx.saved_tensors
+        Hp, Xs = ctx.saved_tensors
         if ctx.speculated is not None:
             _GRAD_COLS_SEEN.discard(ctx.speculated)      # another criterion came: this shape stops forming the column pass ahead
-        return _SpectralApply._backward(ctx.cfg, Hp, kept[0] if kept else None, ctx.needs_input_grad[0], ctx.needs_input_grad[1], gy, None) \
-            + (None, None, None, None, None)
+        return _SpectralApply._backward(ctx.cfg, Hp, Xs, ctx.needs_input_grad[0], ctx.needs_input_grad[1], gy) + (None, None, None, None, None)
 
     @staticmethod
-    def _backward(cfg, Hp, Xkept, need_x, need_h, gy, out_scale, host_factor=1.0, Sg=None):
+    def _backward(cfg, Hp, Xkept, need_x, need_h, gy, out_scale=None, host_factor=1.0, Sg=None):
         """Gradients (gx, gH) for the output gradient gy -- or, with out_scale (a device scalar c of gy's dtype) and host_factor
         (a Python float f), for (c f) * gy without forming it: the pipeline is linear, so the factor is applied where the
-        results are small (f rides in the walking kernel's transform scale, c in its epilogue: no launch of its own)."""
-        kept = [Xkept]
-        nfft, scale_f, env_f, scale_i, env_i, T, NI, NO, walk = cfg
+        results are small (f rides in a host-side scale of the launch that forms each result, c is multiplied in by its kernel:
+        no launch of its own)."""
+        nfft, NI, NO = cfg.nfft, cfg.NI, cfg.NO
         g = gy.contiguous()
         if g.data_ptr() % (2 * g.element_size()):
             g = g.clone()
         B = g.shape[0]
         # irfft' : g_Y[k] = w_k scale_i sum_t g_y[t] e_i(t) exp(-j w_k t) -- a forward transform with doubled interior bins
         # (Sg given: its column pass was formed by the forward pass's inverse launch from the tiles of y -- _SpectralMeanSquare)
-        kept_sg = Sg is not None      # (a tensor the autograd node keeps: spec_mid works in place when NI == NO -- it gets a copy)
+        kept_sg = Sg is not None
         if Sg is None:
-            Sg = _spec_cols_fwd(g, nfft, env_i, site=1)
-        gx = gH = None
-        if walk:
-            if need_h:
-                gH = _spec_gradh_walk(Sg, kept[0], B, NI, NO, nfft, scale_i * host_factor, out_scale)      # (walking kernels: float32)
-            if need_x:
-                # rfft' : g_x[t] = scale_f e_f(t) Re sum_k g_X[k] exp(+j w_k t), g_X = H^H g_Y
-                if _walk_applies(nfft, B, NO, NI):
-                    S3, _ = _spec_mid_walk(Sg, B, NO, NI, nfft, Hp, True, False, scale_i, 1, 1)
-                else:
-                    S3, _ = _spec_mid(Sg.clone() if kept_sg else Sg, B, NO, NI, nfft, Hp, True, False, True, scale_i, 1, 1)
-                # (the objective's factor: its host part in the pass's scale, its device part multiplied in by the kernel)
-                gx = _spec_cols_inv(S3, B, T, min(T, nfft), NI, nfft, scale_f * (host_factor if out_scale is not None else 1.0), env_f,
-                                    dev_scale=out_scale)
-            return gx, gH
-        if need_h and not need_x and GRADH_LOOP and B <= GRADH_LOOP_MAX_BATCH and _spec_fn("fl_spec_gradh_loop_supports", _rdtype(Sg))(nfft, NI, NO):
-            # the response's gradient alone (the training step: the data tensor takes no gradient, trainer.py:172-191): one launch
-            # that walks the batch -- the gradient's spectrum is never written and read back (fl_spec_gradh_loop_*)
-            return None, _spec_gradh_loop(Sg, kept[0], B, NI, NO, nfft, scale_i, host_factor if out_scale is not None else 1.0, out_scale)
+            Sg = _spec_cols_fwd(g, nfft, cfg.env_i, site=1)
+
+        def rows_in():      # spec_mid's input: a tensor the autograd node keeps gets a copy (spec_mid works in place when NI == NO)
+            return Sg.clone() if kept_sg and need_x else Sg
+
+        route = _spec_backward_route(cfg, _rdtype(Sg), B, need_x, need_h)
+        gx = gH = S3 = gYs = None
         # rfft' : g_x[t] = scale_f e_f(t) Re sum_k g_X[k] exp(+j w_k t), g_X = H^H g_Y -- an inverse transform with halved interior bins
-        S3, gYs = _spec_mid(Sg.clone() if kept_sg and need_x else Sg, B, NO, NI if need_x else NO, nfft, Hp if need_x else None, True, need_h,
-                            need_x, scale_i, 1, 1)
+        if route == "walk":
+            if need_h:
+                gH = _spec_gradh_walk(Sg, Xkept, B, NI, NO, nfft, cfg.scale_i * host_factor, out_scale)      # (walking kernels: float32)
+            if need_x and _walk_applies(nfft, B, NO, NI):
+                S3, _ = _spec_mid_walk(Sg, B, NO, NI, nfft, Hp, True, False, cfg.scale_i, 1, 1)
+            elif need_x:
+                S3, _ = _spec_mid(rows_in(), B, NO, NI, nfft, Hp, True, False, True, cfg.scale_i, 1, 1)
+        elif route == "loop":
+            gH = _spec_gradh_loop(Sg, Xkept, B, NI, NO, nfft, cfg.scale_i, host_factor, out_scale)
+        else:
+            S3, gYs = _spec_mid(rows_in(), B, NO, NI if need_x else NO, nfft, Hp if need_x else None, True, need_h, need_x, cfg.scale_i, 1, 1)
         if need_x:
-            gx = _spec_cols_inv(S3, B, T, min(T, nfft), NI, nfft, scale_f * (host_factor if out_scale is not None else 1.0), env_f,
-                                dev_scale=out_scale)
-        if need_h:
-            Xs = kept[0]
-            gH = _gradh_launch(gYs.movedim(-1, 1), Xs.movedim(-1, 1), False, host_factor if out_scale is not None else 1.0,
-                               out_scale).movedim(-1, 0)
+            # (the objective's factor: its host part in the pass's scale, its device part multiplied in by the kernel)
+            gx = _spec_cols_inv(S3, B, cfg.T, min(cfg.T, nfft), NI, nfft, cfg.scale_f * host_factor, cfg.env_f, dev_scale=out_scale)
+        if gYs is not None:      # (layered: behind the input gradient's column pass, the order the launches have always had)
+            gH = _gradh_launch(gYs.movedim(-1, 1), Xkept.movedim(-1, 1), False, host_factor, out_scale).movedim(-1, 0)
         return gx, gH
 
 
-class _SpectralTag:
-    """Rides on the tensor _SpectralApply returns (attribute ``_flamo_sa``): the inputs and kept arrays of that evaluation."""
-    __slots__ = ("x", "Hrm", "Hp", "Xs", "cfg", "parts", "version", "Sg", "key")
-
-    def __init__(self, x, Hrm, Hp, Xs, cfg, parts, version, Sg=None, key=None):
-        self.x, self.Hrm, self.Hp, self.Xs, self.cfg, self.parts, self.version = x, Hrm, Hp, Xs, cfg, parts, version
-        self.Sg, self.key = Sg, key
-
-
-# The first pass of the gradient's transform inside the forward pass's inverse launch (fl_spec_cols_inv_sumsq_grad_*): worth a
+# The first pass of the gradient's transform inside the forward pass's inverse launch (fl_spec_cols_inv_* with Sg): worth a
 # 98 MB store at BASELINE configs[1] only when the backward pass of mean_square(y) follows -- which the operator cannot know when
 # it runs.  It goes by what happened the last time: a shape whose output went into mean_square AND was differentiated is
 # remembered (_SpectralMeanSquare.backward) and takes the fused launch from then on; a miss costs that store, never a result,
@@ -1203,24 +1213,16 @@ class _SpectralMeanSquare(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, Hrm, y, tag):
-        real = y.dtype
-        loss = torch.empty((), dtype=real, device=y.device)
-        fn = _lib.lib().fl_mean_square_final_f32 if real == torch.float32 else _lib.lib().fl_mean_square_final_f64
-        with kernel_timer.span("mean_square_final"):
-            _lib.check(fn(tag.parts.data_ptr(), tag.parts.numel(), 1.0 / y.numel(), loss.data_ptr(), _stream()), "mean_square_final")
-        ctx.has_xs, ctx.has_sg = tag.Xs is not None, tag.Sg is not None
-        ctx.save_for_backward(y, tag.Hp, *([tag.Xs] if ctx.has_xs else []), *([tag.Sg] if ctx.has_sg else []))
+        loss = _mean_square_final(tag.parts, y.numel(), y.dtype, y.device)
+        ctx.save_for_backward(y, tag.Hp, tag.Xs, tag.Sg)        # (absent ones are saved as None: no tensor is held for them)
         ctx.cfg = tag.cfg
-        ctx.key = tag.key
+        ctx.key = _grad_cols_key(tag.x, tag.cfg.nfft, tag.cfg.NI, tag.cfg.NO)
         return loss
 
     @staticmethod
     def backward(ctx, gloss):
-        y, Hp, *kept = ctx.saved_tensors
-        Xs = kept.pop(0) if ctx.has_xs else None
-        Sg = kept.pop(0) if ctx.has_sg else None
-        if ctx.key is not None:
-            _GRAD_COLS_SEEN.add(ctx.key)           # the next forward pass of this shape forms the gradient's column pass itself
+        y, Hp, Xs, Sg = ctx.saved_tensors
+        _GRAD_COLS_SEEN.add(ctx.key)               # the next forward pass of this shape forms the gradient's column pass itself
         c = gloss.to(y.dtype).reshape(())          # device scalar in the pipeline's precision (no launch when it already is)
         gx, gH = _SpectralApply._backward(ctx.cfg, Hp, Xs, ctx.needs_input_grad[0], ctx.needs_input_grad[1], y, c,
                                           2.0 / y.numel(), Sg=Sg)
@@ -1257,14 +1259,13 @@ def _mimo_launch(H, per_bin, diag, conj_t, X):
     """Y = op(H) X.  conj_t: use H^H (swap m/n, conjugate)."""
     real = _rdtype(X)
     B, M, Nx, K, xs_b, xs_n, xs_k = _bnk(X)
-    L = _lib.lib()
     hp = _lead_pitch(H.movedim(0, -1)) if per_bin else 0   # pitch of the per-bin response rows
     if diag:
         N = H.shape[-1]
         hs_f, hs_n = (1, hp) if per_bin else (0, H.stride(-1))
         Y = _empty_planar(X.shape, X.dtype, X.device)
         _, _, _, _, ys_b, ys_n, ys_k = _bnk(Y)
-        fn = L.fl_mimo_diag_c64 if real == torch.float32 else L.fl_mimo_diag_c128
+        fn = _fn("fl_mimo_diag", real, True)
         _lib.check(fn(H.data_ptr(), hs_f, hs_n, int(conj_t), X.data_ptr(), xs_b, xs_n, xs_k, Y.data_ptr(), ys_b, ys_n,
                       ys_k, B, M, N, K, _stream()), "mimo_diag")
         return Y
@@ -1279,7 +1280,7 @@ def _mimo_launch(H, per_bin, diag, conj_t, X):
         No, Ni = No_h, Ni_h
     Y = _empty_planar((B, M, No, *X.shape[3:]), X.dtype, X.device)
     _, _, _, _, ys_b, ys_m, ys_k = _bnk(Y)
-    fn = L.fl_mimo_c64 if real == torch.float32 else L.fl_mimo_c128
+    fn = _fn("fl_mimo", real, True)
     tag = ("mimo_bin" if per_bin else "mimo_const") + ("_adj" if conj_t else "_fwd") + f"[cols={B * K},{No}x{Ni}]"
     with kernel_timer.span(tag):
         _lib.check(fn(H.data_ptr(), hs_f, hs_m, hs_n, int(conj_t), X.data_ptr(), xs_b, xs_n, xs_k, Y.data_ptr(), ys_b,
@@ -1293,21 +1294,20 @@ def _gradh_launch(G, X, diag, scale=1.0, dev_scale=None):
     real = _rdtype(X)
     B, M, Ni, K, xs_b, xs_n, xs_k = _bnk(X)
     _, _, No, _, gs_b, gs_m, gs_k = _bnk(G)
-    L = _lib.lib()
     P = _pitch(M)
     if diag:
         dh = _empty_rows((Ni,), M, X.dtype, X.device)
-        fn = L.fl_mimo_gradh_diag_c64 if real == torch.float32 else L.fl_mimo_gradh_diag_c128
+        fn = _fn("fl_mimo_gradh_diag", real, True)
         _lib.check(fn(G.data_ptr(), gs_b, gs_m, gs_k, X.data_ptr(), xs_b, xs_n, xs_k, dh.data_ptr(), P, B, M, Ni, K,
                       _stream()), "mimo_gradh_diag")
         return dh if scale == 1.0 else dh * scale
     dH = _empty_rows((No, Ni), M, X.dtype, X.device)
-    fn = L.fl_mimo_gradh_c64 if real == torch.float32 else L.fl_mimo_gradh_c128
+    fn = _fn("fl_mimo_gradh", real, True)
     with kernel_timer.span(f"mimo_gradh[cols={B * K},{No}x{Ni}]"):
         if dev_scale is not None:
             if dev_scale.dtype != real or not dev_scale.is_cuda or dev_scale.numel() != 1:
                 raise ValueError("mimo_gradh: dev_scale must be one device scalar of the signal's real dtype")
-            fn = L.fl_mimo_gradh_scaled_c64 if real == torch.float32 else L.fl_mimo_gradh_scaled_c128
+            fn = _fn("fl_mimo_gradh_scaled", real, True)
             _lib.check(fn(G.data_ptr(), gs_b, gs_m, gs_k, X.data_ptr(), xs_b, xs_n, xs_k, dH.data_ptr(), P, float(scale),
                           dev_scale.data_ptr(), B, M, No, Ni, K, _stream()), "mimo_gradh_scaled")
         else:
@@ -1326,7 +1326,7 @@ def _gradw_launch(G, X):
     nblk = L.fl_mimo_gradw_blocks(M)
     part = torch.empty((nblk, No, Ni), dtype=X.dtype, device=X.device)
     dW = torch.empty((No, Ni), dtype=X.dtype, device=X.device)
-    fn = L.fl_mimo_gradw_c64 if real == torch.float32 else L.fl_mimo_gradw_c128
+    fn = _fn("fl_mimo_gradw", real, True)
     with kernel_timer.span(f"mimo_gradw[cols={B * K},{No}x{Ni}]"):
         _lib.check(fn(G.data_ptr(), gs_b, gs_m, gs_k, X.data_ptr(), xs_b, xs_n, xs_k, part.data_ptr(), dW.data_ptr(), B, M, No, Ni,
                       K, _stream()), "mimo_gradw")
@@ -1389,8 +1389,7 @@ def _mimo_real_launch(W, conj_t, X):
         raise ValueError(f"response expects {Ni} input channels, signal has {Nx}")
     Y = _empty_planar((B, M, No, *X.shape[3:]), X.dtype, X.device)
     _, _, _, _, ys_b, ys_m, ys_k = _bnk(Y)
-    L = _lib.lib()
-    fn = L.fl_mimo_c64 if real == torch.float32 else L.fl_mimo_c128
+    fn = _fn("fl_mimo", real, True)
     with kernel_timer.span("mimo_const_real" + ("_adj" if conj_t else "_fwd") + f"[cols={B * K},{No}x{Ni}]"):
         _lib.check(fn(W.data_ptr(), 0, hs_m, hs_n, 2, X.data_ptr(), xs_b, xs_n, xs_k, Y.data_ptr(), ys_b, ys_m, ys_k, B, M, No, Ni,
                       K, _stream()), "mimo")
@@ -1419,7 +1418,7 @@ class _MimoRealConst(torch.autograd.Function):
             L = _lib.lib()
             part = torch.empty((L.fl_mimo_gradw_blocks(M), No, Ni), dtype=Xp.dtype, device=Xp.device)
             gW = torch.empty((No, Ni), dtype=real, device=Xp.device)
-            fn = L.fl_mimo_gradw_re_c64 if real == torch.float32 else L.fl_mimo_gradw_re_c128
+            fn = _fn("fl_mimo_gradw_re", real, True)
             with kernel_timer.span(f"mimo_gradw[cols={B * K},{No}x{Ni}]"):
                 _lib.check(fn(gY.data_ptr(), gs_b, gs_m, gs_k, Xp.data_ptr(), xs_b, xs_n, xs_k, part.data_ptr(), gW.data_ptr(), B, M,
                               No, Ni, K, _stream()), "mimo_gradw")
@@ -1454,17 +1453,13 @@ def mimo(H: torch.Tensor, X: torch.Tensor, diag: bool = False) -> torch.Tensor:
 # ----------------------------------------------------------------------------- closed-loop solve
 # ---- one layer over the fl_solve_* entries, each called from ONE place: _solve_call (right-hand side in, solution out),
 # ---- _solve_fdn_call (the FDN form: the right-hand side is built in the kernel) and _dud_grads (the one-pass gradient kernel)
-def _solve_entry(name: str, real: torch.dtype):
-    return getattr(_lib.lib(), name + ("_c64" if real == torch.float32 else "_c128"))
-
-
 def _solve_call(name, span, R, *head, post=()):
     """The solution OUT for the planar right-hand side R (B, M, N, K...), allocated like R, from the entry ``name``_c64 / _c128:
     fn(*head, R and its strides, OUT and its strides, B, M, N, K, *post, stream)."""
     B, M, N, K, rs_b, rs_n, rs_k = _bnk(R)
     OUT = _empty_planar(R.shape, R.dtype, R.device)
     _, _, _, _, os_b, os_n, os_k = _bnk(OUT)
-    fn = _solve_entry(name, _rdtype(R))
+    fn = _fn(name, _rdtype(R), True)
     with kernel_timer.span(span):
         _lib.check(fn(*head, R.data_ptr(), rs_b, rs_n, rs_k, OUT.data_ptr(), os_b, os_n, os_k, B, M, N, K, *post, _stream()),
                    name[3:])
@@ -1593,7 +1588,7 @@ def _dud_grads(l, l2, U, r, OUT, need_l, need_U, need_r, gR=None, Wadj=None, gyp
         name, adj, sizes = "fl_solve_dud2_grads_w", (Wadj.data_ptr(), _bnk(Wadj)[5], gyp.data_ptr(), gs_b), (B, M, N)
     else:
         name, adj, sizes = ("fl_solve_dud_grads" if l2 is None else "fl_solve_dud2_grads"), (gR.data_ptr(),), (B, M, N, K)
-    fn = _solve_entry(name, real)
+    fn = _fn(name, real, True)
     with kernel_timer.span("solve_dud_grads"):
         _lib.check(fn(*_loop_args(l, l2, U, r), *adj, OUT.data_ptr(), s_b, s_n, s_k, *sizes, *outs, _stream()), name[3:])
     g_b = g_c = None
@@ -1735,7 +1730,7 @@ def _solve_fdn_call(name, span, head, gain, sig, N, cw=None, contracts=True, pos
     contract = ()
     if contracts:
         contract = ((None, 0, None, 0) if cw is None else (cw.data_ptr(), int(not cw.is_complex()), z.data_ptr(), _bnk(z)[4]))
-    fn = _solve_entry(name, _rdtype(sig))
+    fn = _fn(name, _rdtype(sig), True)
     with kernel_timer.span(span):
         _lib.check(fn(*head, gain.data_ptr(), int(not gain.is_complex()), sig.data_ptr(), ss_b, *contract, OUT.data_ptr(), os_b,
                       os_n, os_k, B, M, N, *post, _stream()), name[3:])
@@ -1932,8 +1927,7 @@ def delay_response(m_int: torch.Tensor, amp: torch.Tensor, nfft: int) -> torch.T
     m32 = m_int.to(torch.int32).contiguous()
     amp = amp.contiguous()
     H = _empty_rows(shape, m_local, _cdtype(real), dev)
-    L = _lib.lib()
-    fn = L.fl_delay_response_c64 if real == torch.float32 else L.fl_delay_response_c128
+    fn = _fn("fl_delay_response", real, True)
     _lib.check(fn(m32.data_ptr(), amp.data_ptr(), C_, twiddles(nfft, real, dev).data_ptr(), nfft, bin0, m_local,
                   H.data_ptr(), _pitch(m_local), _stream()), "delay_response")
     return H.movedim(-1, 0)
@@ -1991,8 +1985,7 @@ def _sos_forward_launch(bc, ac, gamma, nfft, real, float_eval=False, geq=None):
             _lib.check(L.fl_geq_response_c64(xc.data_ptr(), kind, cfg.S, consts.data_ptr(), bc.data_ptr(), ac.data_ptr(), *tail,
                                              int(float_eval), _stream()), "geq_response")
         else:
-            fn = L.fl_sos_response_c128 if real == torch.float64 else \
-                (L.fl_sos_response_f32eval_c64 if float_eval else L.fl_sos_response_c64)
+            fn = _fn("fl_sos_response_f32eval" if float_eval and real == torch.float32 else "fl_sos_response", real, True)
             _lib.check(fn(bc.data_ptr(), ac.data_ptr(), cfg.S, *tail, _stream()), "sos_response")
     return H, cfg
 
@@ -2006,7 +1999,7 @@ def _sos_backward_launch(gH, Hf, bc, ac, cfg):
     L = _lib.lib()
     nblk = L.fl_sos_bwd_blocks(cfg.m_local, cfg.C, cfg.S, int(cfg.real == torch.float32 and Hf is not None))
     part = torch.empty((nblk, 2, 3, cfg.S, cfg.C), dtype=torch.float64, device=bc.device)   # every entry is written
-    fn = L.fl_sos_response_bwd_c64 if cfg.real == torch.float32 else L.fl_sos_response_bwd_c128
+    fn = _fn("fl_sos_response_bwd", cfg.real, True)
     Wd = twiddles(cfg.nfft, torch.float64, bc.device)
     with kernel_timer.span("sos_response_bwd"):
         _lib.check(fn(g.data_ptr(), g_pitch, None if Hf is None else Hf.data_ptr(), _pitch(cfg.m_local), bc.data_ptr(),
@@ -2319,13 +2312,12 @@ def _cascade_rc_forward(b, a, Wr, gamma, nfft, real, float_eval, geq=None):
     if cfg.m_local == 0 and geq is None:      # nothing to evaluate (a designing launch still has b, a to write)
         return H.movedim(-1, 0), G, cfg
     with kernel_timer.span("sos_response_rc"):
-        L = _lib.lib()
         if geq is not None:
             xc, kind, consts = geq
-            fn, name = (L.fl_geq_response_rc_c128 if f64 else L.fl_geq_response_rc_c64), "geq_response_rc"
+            fn, name = _fn("fl_geq_response_rc", real, True), "geq_response_rc"
             args = (xc.data_ptr(), kind, S, consts.data_ptr(), b.data_ptr(), a.data_ptr())
         else:
-            fn, name = (L.fl_sos_response_rc_c128 if f64 else L.fl_sos_response_rc_c64), "sos_response_rc"
+            fn, name = _fn("fl_sos_response_rc", real, True), "sos_response_rc"
             args = (b.data_ptr(), a.data_ptr(), S)
         args += (No, Nmid, Ni, Wc.data_ptr(), cfg.gamma, Wd.data_ptr(), nfft, cfg.bin0, cfg.m_local, G.data_ptr(), P, H.data_ptr(), P)
         if not f64:      # the all-double entry points have no float evaluation to choose
@@ -2352,7 +2344,7 @@ def _cascade_rc_backward(gH, G, b, a, Wr, cfg):
     part = torch.empty((nblk, 2, 3, cfg.S, cfg.C), dtype=torch.float64, device=b.device)
     partW = torch.empty((nblk, No, Nmid, Ni), dtype=real, device=b.device)
     Wc = Wr.contiguous()
-    fn = L.fl_sos_response_bwd_rc_c128 if real == torch.float64 else L.fl_sos_response_bwd_rc_c64
+    fn = _fn("fl_sos_response_bwd_rc", real, True)
     with kernel_timer.span("sos_response_bwd_rc"):
         _lib.check(fn(g.data_ptr(), _lead_pitch(g.movedim(0, -1)), G.data_ptr(), _pitch(cfg.m_local),
                       b.data_ptr(), a.data_ptr(), cfg.S, No, Nmid, Ni, Wc.data_ptr(), cfg.gamma,
@@ -2393,7 +2385,7 @@ def _geq_backward_lanes(mode, gH, G, b, a, Wr, cfg, No, Nmid, Ni, nbx, xc, const
     partW = torch.empty((Nmid * Ni, wrows), dtype=real, device=dev) if mode == 1 else None
     Wc = Wr.to(real).contiguous() if mode == 1 else None
     with kernel_timer.span("sos_response_bwd_rc" if mode == 1 else "sos_response_bwd"):
-        _lib.check((L.fl_geq_response_bwd_lanes_c128 if f64 else L.fl_geq_response_bwd_lanes_c64)(
+        _lib.check(_fn("fl_geq_response_bwd_lanes", real, True)(
             mode, g.data_ptr(), _lead_pitch(g.movedim(0, -1)), G.data_ptr(), _pitch(m_local), b.data_ptr(), a.data_ptr(), S, No, Nmid, Ni,
             None if Wc is None else Wc.data_ptr(), gamma, twiddles(nfft, torch.float64, dev).data_ptr(), nfft, bin0, m_local,
             psum.data_ptr(), pq.data_ptr(), None if partW is None else partW.data_ptr(), _stream()), "geq_response_bwd_lanes")
@@ -2508,8 +2500,7 @@ class _MeanSquare(torch.autograd.Function):
             raise ValueError("mean_square of an empty tensor")
         ym, rows, cols, pitch = _rows_of(y)
         loss = torch.empty((), dtype=y.dtype, device=dev)
-        L = _lib.lib()
-        fn = L.fl_mean_square_f32 if y.dtype == torch.float32 else L.fl_mean_square_f64
+        fn = _fn("fl_mean_square", y.dtype)
         with kernel_timer.span("mean_square"):
             _lib.check(fn(ym.data_ptr(), rows, cols, pitch, loss.data_ptr(), _ms_scratch_for(dev).data_ptr(), _stream()),
                        "mean_square")
@@ -2523,11 +2514,19 @@ class _MeanSquare(torch.autograd.Function):
         rows, cols, pitch = ctx.layout
         gy = torch.empty_strided(ym.shape, ym.stride(), dtype=ym.dtype, device=ym.device)
         g = gloss.to(ym.dtype).contiguous()
-        L = _lib.lib()
-        fn = L.fl_mean_square_bwd_f32 if ym.dtype == torch.float32 else L.fl_mean_square_bwd_f64
+        fn = _fn("fl_mean_square_bwd", ym.dtype)
         with kernel_timer.span("mean_square_bwd"):
             _lib.check(fn(ym.data_ptr(), g.data_ptr(), gy.data_ptr(), rows, cols, pitch, _stream()), "mean_square_bwd")
         return gy
+
+
+def _mean_square_final(parts, n, real, dev):
+    """mean of n squares from the partial sums an inverse column pass left behind (fixed order: fl_mean_square_final_*)"""
+    loss = torch.empty((), dtype=real, device=dev)
+    fn = _fn("fl_mean_square_final", real)
+    with kernel_timer.span("mean_square_final"):
+        _lib.check(fn(parts.data_ptr(), parts.numel(), 1.0 / n, loss.data_ptr(), _stream()), "mean_square_final")
+    return loss
 
 
 def _is_pipeline_output(y: torch.Tensor) -> bool:
@@ -2555,8 +2554,7 @@ class _CAbs(torch.autograd.Function):
         else:
             mem = zm.movedim(1, -1)
             out = torch.empty_strided(mem.shape, mem.stride(), dtype=real, device=dev).movedim(-1, 1)
-        L = _lib.lib()
-        fn = L.fl_cabs_c64 if real == torch.float32 else L.fl_cabs_c128
+        fn = _fn("fl_cabs", real, True)
         _lib.check(fn(zm.data_ptr(), out.data_ptr(), rows, cols, pitch, pitch, _stream()), "cabs")
         ctx.save_for_backward(zm)
         ctx.layout = (rows, cols, pitch)
@@ -2580,8 +2578,7 @@ class _CAbs(torch.autograd.Function):
                 gm.copy_(g)
             gpitch = pitch
         gz = torch.empty_strided(zm.shape, zm.stride(), dtype=zm.dtype, device=zm.device)
-        L = _lib.lib()
-        fn = L.fl_cabs_bwd_c64 if zm.dtype == torch.complex64 else L.fl_cabs_bwd_c128
+        fn = _fn("fl_cabs_bwd", _rdtype(zm), True)
         _lib.check(fn(zm.data_ptr(), gm.data_ptr(), gz.data_ptr(), rows, cols, pitch, gpitch, _stream()), "cabs_bwd")
         return gz
 
@@ -2603,8 +2600,7 @@ class _Sparsity(torch.autograd.Function):
         Ac = A.contiguous()
         C, N = (1 if Ac.dim() == 2 else Ac.shape[0]), Ac.shape[-1]
         loss = torch.empty((), dtype=A.dtype, device=dev)
-        L = _lib.lib()
-        fn = L.fl_sparsity_f32 if A.dtype == torch.float32 else L.fl_sparsity_f64
+        fn = _fn("fl_sparsity", A.dtype)
         _lib.check(fn(Ac.data_ptr(), C, N, loss.data_ptr(), _stream()), "sparsity")
         ctx.save_for_backward(Ac)
         ctx.cn = (C, N)
@@ -2616,8 +2612,7 @@ class _Sparsity(torch.autograd.Function):
         C, N = ctx.cn
         gA = torch.empty_like(Ac)
         g = gloss.to(Ac.dtype).contiguous()
-        L = _lib.lib()
-        fn = L.fl_sparsity_bwd_f32 if Ac.dtype == torch.float32 else L.fl_sparsity_bwd_f64
+        fn = _fn("fl_sparsity_bwd", Ac.dtype)
         _lib.check(fn(Ac.data_ptr(), g.data_ptr(), C, N, gA.data_ptr(), _stream()), "sparsity_bwd")
         return gA
 
@@ -2639,8 +2634,7 @@ class _MSE(torch.autograd.Function):
         yc, tc = y.contiguous(), t.contiguous()
         rows = yc.numel() // ncols
         loss = torch.empty((), dtype=y.dtype, device=dev)
-        L = _lib.lib()
-        fn = L.fl_mse_f32 if y.dtype == torch.float32 else L.fl_mse_f64
+        fn = _fn("fl_mse", y.dtype)
         with kernel_timer.span("mse"):
             _lib.check(fn(yc.data_ptr(), tc.data_ptr(), rows, ncols, loss.data_ptr(), _ms_scratch_for(dev).data_ptr(), _stream()), "mse")
         ctx.save_for_backward(yc, tc)
@@ -2653,8 +2647,7 @@ class _MSE(torch.autograd.Function):
         rows, ncols, shape = ctx.cfg
         gy = torch.empty_like(yc)
         g = gloss.to(yc.dtype).contiguous()
-        L = _lib.lib()
-        fn = L.fl_mse_bwd_f32 if yc.dtype == torch.float32 else L.fl_mse_bwd_f64
+        fn = _fn("fl_mse_bwd", yc.dtype)
         with kernel_timer.span("mse_bwd"):
             _lib.check(fn(yc.data_ptr(), tc.data_ptr(), g.data_ptr(), gy.data_ptr(), rows, ncols, _stream()), "mse_bwd")
         return gy.view(shape), None, None
@@ -2698,11 +2691,7 @@ def mean_square(y: torch.Tensor) -> torch.Tensor:
                 return _SpectralMeanSquare.apply(tag.x, tag.Hrm, y.detach(), tag)
         elif not (torch.is_grad_enabled() and y.requires_grad):
             # nothing to differentiate (evaluation under no_grad, validation steps): the value alone, from the partial sums
-            loss = torch.empty((), dtype=y.dtype, device=y.device)
-            fn = _lib.lib().fl_mean_square_final_f32 if y.dtype == torch.float32 else _lib.lib().fl_mean_square_final_f64
-            with kernel_timer.span("mean_square_final"):
-                _lib.check(fn(tag.parts.data_ptr(), tag.parts.numel(), 1.0 / y.numel(), loss.data_ptr(), _stream()), "mean_square_final")
-            return loss
+            return _mean_square_final(tag.parts, y.numel(), y.dtype, y.device)
     return _MeanSquare.apply(y)
 
 
@@ -2729,9 +2718,9 @@ class _MatrixExp(torch.autograd.Function):
         E = torch.empty((N, N), dtype=_cdtype(X.dtype) if cplx else X.dtype, device=dev)
         stash = torch.empty(L.fl_matrix_exp_stash_elems(N), dtype=torch.float64, device=dev)
         if cplx:
-            fn = L.fl_matrix_exp_cplx_f32 if X.dtype == torch.float32 else L.fl_matrix_exp_cplx_f64
+            fn = _fn("fl_matrix_exp_cplx", X.dtype)
         else:
-            fn = L.fl_matrix_exp_f32 if X.dtype == torch.float32 else L.fl_matrix_exp_f64
+            fn = _fn("fl_matrix_exp", X.dtype)
         _lib.check(fn(Xc.data_ptr(), N, int(skew), E.data_ptr(), stash.data_ptr(), _stream()), "matrix_exp")
         ctx.save_for_backward(stash)
         ctx.cfg = (N, int(skew), X.dtype, bool(cplx))
@@ -2741,13 +2730,12 @@ class _MatrixExp(torch.autograd.Function):
     def backward(ctx, gE):
         (stash,) = ctx.saved_tensors
         N, skew, dt, cplx = ctx.cfg
-        L = _lib.lib()
         if cplx:      # the kernel takes the real part of the complex gradient
             g = gE.resolve_conj().to(_cdtype(dt)).contiguous()
-            fn = L.fl_matrix_exp_bwd_cplx_f32 if dt == torch.float32 else L.fl_matrix_exp_bwd_cplx_f64
+            fn = _fn("fl_matrix_exp_bwd_cplx", dt)
         else:
             g = gE.to(dt).contiguous()
-            fn = L.fl_matrix_exp_bwd_f32 if dt == torch.float32 else L.fl_matrix_exp_bwd_f64
+            fn = _fn("fl_matrix_exp_bwd", dt)
         gX = torch.empty((N, N), dtype=dt, device=g.device)
         _lib.check(fn(g.data_ptr(), N, skew, stash.data_ptr(), gX.data_ptr(), _stream()), "matrix_exp_bwd")
         return gX, None, None
@@ -2769,7 +2757,7 @@ class _MatrixExpBoth(torch.autograd.Function):
         E = torch.empty((N, N), dtype=X.dtype, device=dev)
         Ec = torch.empty((N, N), dtype=_cdtype(X.dtype), device=dev)
         stash = torch.empty(L.fl_matrix_exp_stash_elems(N), dtype=torch.float64, device=dev)
-        fn = L.fl_matrix_exp_both_f32 if X.dtype == torch.float32 else L.fl_matrix_exp_both_f64
+        fn = _fn("fl_matrix_exp_both", X.dtype)
         _lib.check(fn(Xc.data_ptr(), N, int(skew), E.data_ptr(), Ec.data_ptr(), stash.data_ptr(), _stream()), "matrix_exp")
         ctx.save_for_backward(stash)
         ctx.cfg = (N, int(skew), X.dtype)
@@ -2780,13 +2768,12 @@ class _MatrixExpBoth(torch.autograd.Function):
     def backward(ctx, gE, gEc):
         (stash,) = ctx.saved_tensors
         N, skew, dt = ctx.cfg
-        L = _lib.lib()
         if gE is None and gEc is None:
             return None, None
         g = None if gE is None else gE.to(dt).contiguous()
         gc = None if gEc is None else gEc.resolve_conj().to(_cdtype(dt)).contiguous()
         gX = torch.empty((N, N), dtype=dt, device=stash.device)
-        fn = L.fl_matrix_exp_bwd_both_f32 if dt == torch.float32 else L.fl_matrix_exp_bwd_both_f64
+        fn = _fn("fl_matrix_exp_bwd_both", dt)
         _lib.check(fn(None if g is None else g.data_ptr(), None if gc is None else gc.data_ptr(), N, skew, stash.data_ptr(),
                       gX.data_ptr(), _stream()), "matrix_exp_bwd")
         return gX, None
@@ -2835,8 +2822,7 @@ class _Eigvals(torch.autograd.Function):
         lam = _empty_rows((N,), Mt, A.dtype, dev)
         Vv = _empty_rows((N, N), Mt, A.dtype, dev) if need_v else None
         info = torch.empty(Mt, dtype=torch.int32, device=dev)
-        L = _lib.lib()
-        fn = L.fl_eig_c64 if A.dtype == torch.complex64 else L.fl_eig_c128
+        fn = _fn("fl_eig", _rdtype(A), True)
         _lib.check(fn(Ap.data_ptr(), a_pitch, N, Mt, lam.data_ptr(), _pitch(Mt), None if Vv is None else Vv.data_ptr(),
                       _pitch(Mt), info.data_ptr(), _stream()), "eig")
         _eig_state["info"] = info

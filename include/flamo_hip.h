@@ -169,13 +169,10 @@ int fl_spec_mid_walk_f32(const void* S, void* S2, void* Xp, const void* H, long 
  *   written; fl_sum_parts_c64 or the consumer adds the sets -- fixed order, no atomics).
  *   fl_spec_gradh_slices: the slice count that fills the device (1 <= . <= Bn). */
 int fl_spec_gradh_slices(int nfft, int Bn);
+/* out_scale (optional, null = absent): dH multiplied by the device scalar out_scale[0] (float) on its way out -- the factor
+ * 2 g / N of an objective mean(y^2) whose gradient g_y = (2 g / N) y is never materialised: K1 runs on y itself (ops.mean_square) */
 int fl_spec_gradh_walk_f32(const void* Sg, const void* Xp, void* dH_parts, long ds_s, long ds_m, long ds_n, int n_slices, const void* W,
-                           int nfft, int Bn, int NI, int NO, double scale_g, int interior2_g, void* stream);
-/* the same with dH multiplied by the device scalar out_scale[0] (float) on its way out: the factor 2 g / N of an objective
- * mean(y^2) whose gradient g_y = (2 g / N) y is never materialised -- K1 runs on y itself (ops.mean_square) */
-int fl_spec_gradh_walk_scaled_f32(const void* Sg, const void* Xp, void* dH_parts, long ds_s, long ds_m, long ds_n, int n_slices,
-                                  const void* W, int nfft, int Bn, int NI, int NO, double scale_g, int interior2_g,
-                                  const void* out_scale, void* stream);
+                           int nfft, int Bn, int NI, int NO, double scale_g, int interior2_g, const void* out_scale, void* stream);
 /* out[j] = sum_{s < n_parts} parts[s*part_stride + j], j < n complex values (16-byte aligned, n and part_stride even) */
 int fl_sum_parts_c64(const void* parts, long part_stride, int n_parts, void* out, long n, void* stream);
 /* tuning hook: mode 0 switches the walking kernels off (fl_spec_walk_supports -> 0); wgs / slices override the forward
@@ -188,33 +185,28 @@ int fl_debug_set_walk(int mode, int wgs, int slices, void* times);
  * events cannot be recorded; max(end) - min(start) its active time.  NULL: off. */
 int fl_debug_set_walk_stamps(void* buf);
 int fl_wall_clock_khz(void);
-/* K3: y[b][t][g] = scale * e(t) * (unnormalised inverse transform of S2), t < t_out <= t_len; y: real (Bn, t_len, G) */
+/* K3: y[b][t][g] = scale * e(t) * (unnormalised inverse transform of S2), t < t_out <= t_len; y: real (Bn, t_len, G).  Three
+ * optional pointers, null = absent:
+ *   sumsq_parts[w] = sum of the squares of the samples workgroup w stored (double; fl_spec_cols_blocks entries, every one
+ *     written): the reduction of an objective mean(y^2) -- trainer.py:177-190 with a squared-error criterion -- rides in the
+ *     pass that produces y; fl_mean_square_final_* combines the partials in a fixed order;
+ *   dev_scale: a DEVICE scalar (float; double in the _f64 form) multiplied into `scale` -- the gradient of the input under an
+ *     objective whose factor lives on the device (trainer.py:177-190: loss.backward() hands 2 g / N down as a tensor), a
+ *     multiplication pass over the (Bn, t_len, G) result otherwise;
+ *   Sg (with sumsq_parts, plain shape: t_len = t_out = nfft, env_log2 = 0) = what fl_spec_cols_fwd of the y it stores would
+ *     leave -- the first pass of the GRADIENT's transform when the objective's g_y is a multiple of y (loss.backward() starts
+ *     with rfft(g_y), dsp.py:114 under autograd) -- formed from the tile in registers: the backward pass does not re-read y.
+ *     fl_spec_cols_inv_grad_supported_*: 1 where that form exists (every column plan whose first radix times the tile width is
+ *     at most 256 -- all but the 441- and 800-point columns and 16 channels on 16-point radices -- both precisions), else the
+ *     caller runs fl_spec_cols_fwd on y. */
 int fl_spec_cols_inv_f32(const void* S2, void* y, int Bn, int t_len, int t_out, int G, const void* W, int nfft, double scale,
-                         double env_log2, void* stream);
-/* K3 that also leaves sumsq_parts[w] = sum of the squares of the samples workgroup w stored (double; fl_spec_cols_blocks
- * entries, every one written): the reduction of an objective mean(y^2) -- trainer.py:177-190 with a squared-error criterion --
- * rides in the pass that produces y; fl_mean_square_final_* combines the partials in a fixed order */
-int fl_spec_cols_inv_sumsq_f32(const void* S2, void* y, int Bn, int t_len, int t_out, int G, const void* W, int nfft, double scale,
-                               double env_log2, void* sumsq_parts, void* stream);
+                         double env_log2, void* sumsq_parts, const void* dev_scale, void* Sg, void* stream);
 int fl_spec_cols_blocks_f32(int nfft, int Bn, int G);
-/* K3 (plain shape: every sample stored, no envelope) that also leaves Sg = what fl_spec_cols_fwd_f32 of the y it stores would
- * leave -- the first pass of the GRADIENT's transform when the objective's g_y is a multiple of y (trainer.py:177-190 with a
- * squared-error criterion: loss.backward() starts with rfft(g_y), dsp.py:114 under autograd) -- formed from the tile in
- * registers: the backward pass does not re-read y.  fl_spec_cols_inv_grad_supported_*: 1 where the fused form exists
- * (every column plan whose first radix times the tile width is at most 256 -- all but the 441- and 800-point columns and 16
- * channels on 16-point radices -- both precisions), else the caller runs fl_spec_cols_fwd on y. */
 int fl_spec_cols_inv_grad_supported_f32(int nfft, int G);
 /* 1: fl_spec_cols_inv_* may be given y = S2 (the real (Bn, nfft, G) output over the scratch it is transformed from; t_len = t_out
  * = nfft): a workgroup reads its whole tile before its first store and the two tiles are the same bytes when one tile carries all
  * G channels */
 int fl_spec_cols_inv_inplace_ok_f32(int nfft, int G);
-int fl_spec_cols_inv_sumsq_grad_f32(const void* S2, void* y, void* Sg, int Bn, int G, const void* W, int nfft, double scale,
-                                    void* sumsq_parts, void* stream);
-/* K3 with a DEVICE scalar (float; double in the _f64 form) multiplied into `scale`: the gradient of the input under an
- * objective whose factor lives on the device (trainer.py:177-190: loss.backward() hands 2 g / N down as a tensor) -- a
- * multiplication pass over the (Bn, t_len, G) result otherwise */
-int fl_spec_cols_inv_scaled_f32(const void* S2, void* y, int Bn, int t_len, int t_out, int G, const void* W, int nfft, double scale,
-                                const void* dev_scale, double env_log2, void* stream);
 /* per plane: dst[i] = src[k(i)] (inverse = 0, natural -> row-major bin order) or dst[k(i)] = src[i] (inverse = 1) */
 int fl_permute_bins_c64(const void* src, long src_pitch, void* dst, long dst_pitch, int nplanes, int nfft, int inverse,
                         void* stream);
@@ -246,16 +238,10 @@ int fl_spec_mid_f64(const void* S, void* S2, void* Xs, long xs_b, long xs_n, con
                     const void* W, int nfft, int Bn, int NI, int NO, double spec_scale, int spec_interior2, int pre_half,
                     void* stream);
 int fl_spec_cols_inv_f64(const void* S2, void* y, int Bn, int t_len, int t_out, int G, const void* W, int nfft, double scale,
-                         double env_log2, void* stream);
-int fl_spec_cols_inv_sumsq_f64(const void* S2, void* y, int Bn, int t_len, int t_out, int G, const void* W, int nfft, double scale,
-                               double env_log2, void* sumsq_parts, void* stream);
+                         double env_log2, void* sumsq_parts, const void* dev_scale, void* Sg, void* stream);
 int fl_spec_cols_blocks_f64(int nfft, int Bn, int G);
-int fl_spec_cols_inv_scaled_f64(const void* S2, void* y, int Bn, int t_len, int t_out, int G, const void* W, int nfft, double scale,
-                                const void* dev_scale, double env_log2, void* stream);
 int fl_spec_cols_inv_grad_supported_f64(int nfft, int G);
 int fl_spec_cols_inv_inplace_ok_f64(int nfft, int G);
-int fl_spec_cols_inv_sumsq_grad_f64(const void* S2, void* y, void* Sg, int Bn, int G, const void* W, int nfft, double scale,
-                                    void* sumsq_parts, void* stream);
 int fl_permute_bins_c128(const void* src, long src_pitch, void* dst, long dst_pitch, int nplanes, int nfft, int inverse,
                          void* stream);
 

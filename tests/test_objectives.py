@@ -168,7 +168,7 @@ def test_fused_mean_square_only_for_the_pipelines_own_output(gpu):
                                                 (4096, 2, 3, True, torch.float32), (65536, 8, 5, False, torch.float32),
                                                 (32000, 4, 2, True, torch.float64), (88200, 4, 2, False, torch.float32)])
 def test_gradient_column_pass_inside_the_forward_pass(gpu, nfft, N, B, with_x, dt):
-    """fl_spec_cols_inv_sumsq_grad_f32: once the output of an operator of some shape has gone into ops.mean_square and been
+    """fl_spec_cols_inv_* given Sg: once the output of an operator of some shape has gone into ops.mean_square and been
     differentiated, the next forward pass of that shape leaves the gradient's first column pass (fl_spec_cols_fwd of y) from the
     tiles of its inverse column pass -- y is not read back.  Same operations on the same values: output, loss and gradients EQUAL
     the two-pass form's in float32 (1e-13 in float64), the backward pass runs no column pass of its own (only the input gradient's inverse one), a second

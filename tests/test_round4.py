@@ -186,7 +186,7 @@ def test_walking_kernels_beyond_the_benchmark_shape(gpu, nfft, NI, NO, B):
 
 @pytest.mark.parametrize("nfft,G,B,t_out", [(96000, 8, 3, 96000), (96000, 16, 2, 50000), (32000, 4, 2, 32000), (4096, 2, 5, 4096), (384000, 8, 1, 384000)])
 def test_inverse_column_pass_leaves_the_sum_of_squares(gpu, dt, nfft, G, B, t_out):
-    """fl_spec_cols_inv_sumsq_*: the same y as fl_spec_cols_inv_* (bit for bit) plus per-workgroup partial sums whose total is
+    """fl_spec_cols_inv_* with sumsq_parts: the same y as without (bit for bit) plus per-workgroup partial sums whose total is
     sum(y^2) over the samples it stored (truncated output, envelope and scale included); fl_mean_square_final_* reduces them."""
     from flamo_amd import _lib, ops
     if not ops.spectral_supported(nfft, G, G, dt):

@@ -779,3 +779,154 @@ def test_launch_pair_response_beside_column_pass(gpu, kind, N, db):
     assert L.fl_debug_launch_pair_count() == n1
     for a, b in zip(paired, plain):
         assert torch.equal(a, b), kind
+
+
+def _route_case(name, dt, nfft, NI, NO, B, needs, fwd, bwd, objective="cotangent", knobs=None, T=None, db=None, offset=0):
+    return pytest.param(dict(dt=dt, nfft=nfft, NI=NI, NO=NO, B=B, needs=needs, fwd=fwd, bwd=bwd, objective=objective,
+                             knobs=knobs or {}, T=T, db=db, offset=offset), id=name)
+
+
+_F32, _F64 = torch.float32, torch.float64
+ROUTE_CASES = [
+    _route_case("loop-f32", _F32, 96000, 8, 8, 2, "h", "rows", "loop"),
+    _route_case("loop-f64", _F64, 96000, 4, 4, 4, "h", "rows", "loop"),
+    _route_case("layered-xh-f32-4096", _F32, 4096, 4, 4, 3, "xh", "rows", "layered"),
+    _route_case("layered-h-f64-batch5", _F64, 96000, 8, 8, 5, "h", "rows", "layered"),
+    _route_case("layered-h-f32-loop-off", _F32, 96000, 8, 8, 2, "h", "rows", "layered", knobs=dict(GRADH_LOOP=False)),
+    _route_case("layered-x-f32-4096", _F32, 4096, 2, 2, 2, "x", "rows", "layered"),
+    _route_case("walk-h", _F32, 96000, 8, 8, 5, "h", "walk", "walk"),
+    _route_case("walk-xh", _F32, 96000, 2, 2, 7, "xh", "walk", "walk"),
+    _route_case("walk-xh-4to8", _F32, 96000, 4, 8, 4, "xh", "walk", "walk"),
+    _route_case("walk-xh-8to2", _F32, 96000, 8, 2, 5, "xh", "walk", "walk"),
+    _route_case("objective-walk-f32", _F32, 96000, 8, 8, 5, "h", "walk", "walk", objective="mean_square"),
+    _route_case("objective-loop-f64", _F64, 96000, 8, 8, 3, "h", "rows", "loop", objective="mean_square"),
+    _route_case("objective-layered-f32-4096", _F32, 4096, 4, 4, 3, "xh", "rows", "layered", objective="mean_square"),
+    _route_case("objective-no-grad", _F32, 96000, 8, 8, 5, "", "walk", None, objective="mean_square"),
+    _route_case("not-in-place-16ch", _F32, 192000, 16, 16, 2, "xh", "rows", "layered"),
+    _route_case("not-in-place-knob", _F32, 96000, 8, 8, 2, "xh", "rows", "layered", knobs=dict(INVERSE_IN_PLACE=False)),
+    _route_case("short-input-envelopes", _F32, 4096, 4, 4, 3, "xh", "rows", "layered", T=3000, db=30.0),
+    _route_case("long-input-envelopes", _F32, 96000, 2, 2, 7, "xh", "walk", "walk", T=96100, db=30.0),
+    _route_case("input-offset-one-sample", _F32, 96000, 8, 8, 2, "h", "rows", "loop", offset=1),
+]
+
+
+@pytest.mark.parametrize("case", ROUTE_CASES)
+def test_spectral_routes_and_launches(gpu, case):
+    """Which launches one forward + backward pass of the fused pipeline makes, per route: the exact span names ops.kernel_timer
+    records and how many of each, and that no launch pair is issued outside ops.paired_launch.  Names and counts only -- the
+    values belong to the tests above and to test_round4 / test_objectives.  Forward: "rows" (spec_mid) or "walk"
+    (spec_mid_walk, float32 from _WALK_MIN_BATCH items on); backward: "walk" (spec_gradh_walk, + sum_parts with more than one
+    batch slice), "loop" (spec_gradh_loop: the response's gradient alone, up to GRADH_LOOP_MAX_BATCH items) or "layered" (spec_mid
+    + mimo_gradh); the input's gradient always ends in an inverse column pass.  With mean_square(y) as the objective the first
+    step adds mean_square_final and nothing else; once the shape is remembered the forward pass's inverse launch forms the
+    gradient's column pass (spec_cols_inv+grad_cols) and the backward pass runs none; a gradient that then arrives through the
+    operator's own node makes the shape forget."""
+    from collections import Counter
+
+    from flamo_amd import _lib, ops
+    c = case
+    dt, nfft, NI, NO, B = c["dt"], c["nfft"], c["NI"], c["NO"], c["B"]
+    need_x, need_h = "x" in c["needs"], "h" in c["needs"]
+    cdt = torch.complex64 if dt == torch.float32 else torch.complex128
+    T = c["T"] or nfft
+    M = nfft // 2 + 1
+    torch.manual_seed(nfft % 977 + NI + 3 * NO + B)
+    H0 = ops.permute_bins(torch.randn(M, NO, NI, device=gpu, dtype=cdt) / NI ** 0.5, nfft)
+    x0 = torch.randn(B * T * NI + c["offset"], device=gpu, dtype=dt)[c["offset"]:].view(B, T, NI)
+    assert (x0.data_ptr() % (2 * x0.element_size()) != 0) == bool(c["offset"])       # (one sample off: the operator works on a copy)
+    cot = torch.randn(B, nfft, NO, device=gpu, dtype=dt)
+    L = _lib.lib()
+    sfx = "_f32" if dt == torch.float32 else "_f64"
+
+    assert (dt == torch.float32 and ops._walk_applies(nfft, B, NI, NO)) == (c["fwd"] == "walk")
+    swapped_walks = c["fwd"] == "walk" and ops._walk_applies(nfft, B, NO, NI)
+    slices = int(L.fl_spec_gradh_slices(nfft, B)) if c["bwd"] == "walk" else 0
+    grad_cols_taken = c["db"] is None and bool(getattr(L, "fl_spec_cols_inv_grad_supported" + sfx)(nfft, NO))
+    if c["bwd"] == "loop":
+        assert getattr(L, "fl_spec_gradh_loop_supports" + sfx)(nfft, NI, NO) and B <= ops.GRADH_LOOP_MAX_BATCH
+
+    def expected(backward, grad_cols=False, kept_sg=False, final=False):
+        e = Counter({"spec_cols_fwd": 1})
+        spec = ",spec" if need_h else ""
+        e[f"spec_mid_walk[{NI}->{NO}{spec}]" if c["fwd"] == "walk" else f"spec_mid[{NI}->{NO},H,inv{spec}]"] += 1
+        e["spec_cols_inv+grad_cols" if grad_cols else "spec_cols_inv"] += 1
+        if final:
+            e["mean_square_final"] += 1
+        if not backward:
+            return dict(e)
+        if not kept_sg:
+            e["spec_cols_fwd"] += 1
+        if c["bwd"] == "loop":
+            e["spec_gradh_loop"] += 1
+        elif c["bwd"] == "walk":
+            if need_h:
+                e["spec_gradh_walk"] += 1
+                if slices > 1:
+                    e["sum_parts"] += 1
+            if need_x:
+                e[f"spec_mid_walk[{NO}->{NI}]" if swapped_walks else f"spec_mid[{NO}->{NI},H,inv]"] += 1
+        else:
+            e[f"spec_mid[{NO}->{NI},H,inv{spec}]" if need_x else f"spec_mid[{NO}->{NO},spec]"] += 1
+            if need_h:
+                e[f"mimo_gradh[cols={B},{NO}x{NI}]"] += 1
+        if need_x:
+            e["spec_cols_inv"] += 1
+        return dict(e)
+
+    def step(objective):
+        """one forward + backward pass -> (spans recorded, launch pairs issued)"""
+        H = H0.clone().requires_grad_(need_h)
+        x = x0.detach().requires_grad_(need_x)       # (same storage, same offset)
+        n0 = L.fl_debug_launch_pair_count()
+        ops.kernel_timer.reset(True)
+        try:
+            y = ops.spectral_apply(x, H, nfft, "backward", "backward", c["db"], c["db"])
+            assert y.shape == (B, nfft, NO)
+            loss = ops.mean_square(y) if objective == "mean_square" else (y * cot).sum()
+            g = torch.autograd.grad(loss, ([x] if need_x else []) + ([H] if need_h else []))
+            assert len(g) == len(c["needs"]) and (not need_x or g[0].shape == x.shape)
+            torch.cuda.synchronize()
+            return {k: len(v) for k, v in ops.kernel_timer.records.items()}, L.fl_debug_launch_pair_count() - n0
+        finally:
+            ops.kernel_timer.reset(False)
+
+    keep = {k: getattr(ops, k) for k in c["knobs"]}
+    seen = set(ops._GRAD_COLS_SEEN)
+    ops._GRAD_COLS_SEEN.clear()
+    try:
+        for k, v in c["knobs"].items():
+            setattr(ops, k, v)
+        if c["bwd"] is None:            # evaluation: the value from the partial sums, no pass over y
+            n0 = L.fl_debug_launch_pair_count()
+            ops.kernel_timer.reset(True)
+            with torch.no_grad():
+                ops.mean_square(ops.spectral_apply(x0, H0, nfft))
+            torch.cuda.synchronize()
+            used = {k: len(v) for k, v in ops.kernel_timer.records.items()}
+            assert used == expected(False, final=True) and L.fl_debug_launch_pair_count() == n0, used
+            return
+        if c["objective"] == "cotangent":
+            used, pairs = step("cotangent")
+            assert used == expected(True) and pairs == 0, (used, expected(True))
+            assert not ops._GRAD_COLS_SEEN
+            return
+        key = ops._grad_cols_key(x0, nfft, NI, NO)
+        used, pairs = step("mean_square")                 # first step: the shape is not remembered yet
+        assert used == expected(True, final=True) and pairs == 0, (used, expected(True, final=True))
+        assert ops._GRAD_COLS_SEEN == {key}
+        used, pairs = step("mean_square")                 # second step: the inverse launch forms the gradient's column pass
+        want = expected(True, grad_cols=grad_cols_taken, kept_sg=grad_cols_taken, final=True)
+        assert used == want and pairs == 0, (used, want)
+        used, pairs = step("cotangent")                   # another criterion: through the operator's own node; the shape forgets
+        want = expected(True, grad_cols=grad_cols_taken)
+        assert used == want and pairs == 0, (used, want)
+        assert (key in ops._GRAD_COLS_SEEN) == (not grad_cols_taken)
+        ops._GRAD_COLS_SEEN.discard(key)
+        used, pairs = step("cotangent")
+        assert used == expected(True) and pairs == 0, (used, expected(True))
+    finally:
+        for k, v in keep.items():
+            setattr(ops, k, v)
+        ops.kernel_timer.reset(False)
+        ops._GRAD_COLS_SEEN.clear()
+        ops._GRAD_COLS_SEEN.update(seen)

@@ -146,7 +146,7 @@ for ns in [int(v) for v in args.slices.split(",")]:
 
     def run():
         _lib.check(L.fl_spec_gradh_walk_f32(Sg.data_ptr(), Xp.data_ptr(), parts.data_ptr(), N * N * P, N * P, P, nsl, W.data_ptr(), nfft, B, N, N,
-                                            1.0 / nfft, 1, ops._stream()), "gradh_walk")
+                                            1.0 / nfft, 1, None, ops._stream()), "gradh_walk")
 
     def run_sum():
         _lib.check(L.fl_sum_parts_c64(parts.data_ptr(), N * N * P, nsl, out.data_ptr(), N * N * P, ops._stream()), "sum_parts")
@@ -174,7 +174,7 @@ gmode = int(os.environ.get("WALK_GRADH_MODE", "1"))       # 15: all output chann
 L.fl_debug_set_walk(gmode, 0, 0, bufg.data_ptr())
 nsl = L.fl_spec_gradh_slices(nfft, B)
 parts = torch.empty((nsl, N, N, P), dtype=torch.complex64, device=dev)
-_lib.check(L.fl_spec_gradh_walk_f32(Sg.data_ptr(), Xp.data_ptr(), parts.data_ptr(), N * N * P, N * P, P, nsl, W.data_ptr(), nfft, B, N, N, 1.0 / nfft, 1, ops._stream()), "gradh_walk")
+_lib.check(L.fl_spec_gradh_walk_f32(Sg.data_ptr(), Xp.data_ptr(), parts.data_ptr(), N * N * P, N * P, P, nsl, W.data_ptr(), nfft, B, N, N, 1.0 / nfft, 1, None, ops._stream()), "gradh_walk")
 torch.cuda.synchronize()
 L.fl_debug_set_walk(1, 0, 0, None)
 tg = bufg.view(-1, 8).cpu().double()
