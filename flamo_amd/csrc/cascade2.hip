@@ -588,16 +588,24 @@ __global__ void __launch_bounds__(256) sos_response_rc_ba_kernel(RcBaArgs A) {
     if (dbg && threadIdx.x == 0) dbg[5] = (long long)__builtin_amdgcn_s_memrealtime();
 }
 
+static void pin_kernel_order() {      // the code object's kernel order, kept as it has always been (see response.hip)
+    (void)&sos_response_rc_ba_kernel<2>, (void)&sos_response_rc_ba_kernel<4>, (void)&sos_response_rc_ba_kernel<8>,
+        (void)&sos_response_rc_ba_kernel<16>, (void)&sos_bwd_lanes_kernel<float, 0, 1, 2, false>,
+        (void)&sos_bwd_lanes_kernel<float, 8, 8, 2, false>, (void)&sos_bwd_lanes_kernel<float, 4, 4, 2, false>,
+        (void)&sos_bwd_lanes_kernel<float, 2, 2, 2, false>, (void)&sos_bwd_lanes_kernel<float, 16, 16, 2, false>,
+        (void)&sos_bwd_lanes_kernel<double, 0, 1, 2, false>, (void)&sos_bwd_lanes_kernel<double, 8, 8, 2, false>,
+        (void)&sos_bwd_lanes_kernel<double, 4, 4, 2, false>, (void)&sos_bwd_lanes_kernel<double, 2, 2, 2, false>,
+        (void)&sos_bwd_lanes_kernel<double, 16, 16, 2, false>, (void)&geq_bwd_lanes_kernel<float>, (void)&geq_bwd_lanes_kernel<double>;
+}
+
 // host side of the kernel above (called by response.hip: rc_impl); returns FL_ERR_UNSUPPORTED (no error text) when the shape is
 // not taken, so that the caller falls back to the first generation
 int rc_ba_launch_now(const PendingRc& p0, hipStream_t st) {
     PendingRc p = p0;
     p.args.dbg = pair_dbg() && p.gx <= 4096 ? pair_dbg() + 4 * 8192 : nullptr;
-    const dim3 grid(p.gx, p.gy);
-    if (p.niw == 2) hipLaunchKernelGGL((sos_response_rc_ba_kernel<2>), grid, dim3(256), p.lds, st, p.args);
-    else if (p.niw == 4) hipLaunchKernelGGL((sos_response_rc_ba_kernel<4>), grid, dim3(256), p.lds, st, p.args);
-    else if (p.niw == 8) hipLaunchKernelGGL((sos_response_rc_ba_kernel<8>), grid, dim3(256), p.lds, st, p.args);
-    else hipLaunchKernelGGL((sos_response_rc_ba_kernel<16>), grid, dim3(256), p.lds, st, p.args);
+    dispatch<2, 4, 8, 16>(p.niw, [&](auto NIW) {      // (rc_ba_launch records these four only)
+        hipLaunchKernelGGL((sos_response_rc_ba_kernel<decltype(NIW)::value>), dim3(p.gx, p.gy), dim3(256), p.lds, st, p.args);
+    });
     FL_CHECK_LAUNCH("sos_response_rc_ba");
     return FL_OK;
 }
@@ -609,8 +617,7 @@ int rc_ba_launch(const void* b, const void* a, int S, int No, int Nmid, int Ni, 
     PendingRc p;
     p.lds = (size_t)Nmid * 2 * Seff * 32 + (size_t)((Nmid * Ni + 3) & ~3) * 4 + (size_t)Nmid * S * 6 * 8;
     if (p.lds > 64 * 1024) return FL_ERR_UNSUPPORTED;
-    const int npairs = bin0 >= 0 ? cdiv_i(m_local, 2) : (((nfft / 2 / (-bin0)) + 1) / 2) * (-bin0) + 1;
-    p.gx = cdiv_i(npairs, 256);
+    p.gx = cdiv_i(rc_npairs(nfft, bin0, m_local), 256);
     p.gy = No;
     p.niw = Ni;
     p.args = RcBaArgs{(const double*)b, (const double*)a, S, No * Nmid, Nmid, (const float*)Wr, gamma, (const cx<double>*)Wd, nfft, bin0,
@@ -639,29 +646,9 @@ static int g_lanes_tb = 0;     // > 0: forced tile length
 static long long* g_lanes_stamps = nullptr;
 static int g_lanes_skip = 0;
 
-static size_t lanes_lds_limit() {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || v <= 0) v = 64 * 1024;
-    return (size_t)v;
-}
-// more dynamic LDS than the default 64 KB: the attribute is per function AND per device, set (and checked) once per pair
-static int lanes_ensure_lds(const void* kern, size_t lds, bool* done /* [64] */) {
-    if (lds <= 64 * 1024) return FL_OK;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (done[dev]) return FL_OK;
-    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lanes_lds_limit());
-    if (e != hipSuccess) {
-        set_error("lanes cascade backward: %zu bytes of LDS per workgroup are not available on device %d (%s)", lds, dev, hipGetErrorString(e));
-        return FL_ERR_UNSUPPORTED;
-    }
-    done[dev] = true;
-    return FL_OK;
-}
-static int lanes_cus() {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) return v;
-    return 256;
+// more dynamic LDS than the default 64 KB: nothing to set at or below it; beyond, the attribute is raised to the device's limit
+static int lanes_ensure_lds(const void* kern, size_t lds, bool* done /* [kMaxDevices] */) {
+    return lds <= 64 * 1024 ? FL_OK : ensure_dynamic_lds(kern, lds, true, done, "lanes cascade backward");
 }
 
 // mode: 0 plain (ppr = 1), 1 constant factor (ppr = N_mid, niw columns), 2 outer (ppr = N_in)
@@ -699,7 +686,7 @@ static LanesPlan lanes_plan(int m_local, int C, int S, int nfft, int bin0, int p
     // config 2 against 131 for the lane-per-bin kernel; built for three per SIMD it spills 53 registers: 213 us)
     if (esz == 8) bpc = 1;
     if (bpc < 1) bpc = 1;
-    const int slots = lanes_cus() * bpc;
+    const int slots = device_cus() * bpc;
     int nbx_target = slots / P.ng;
     if (nbx_target < 1) nbx_target = 1;
     if (bin0 < 0) {
@@ -745,7 +732,7 @@ static LanesPlan lanes_plan(int m_local, int C, int S, int nfft, int bin0, int p
         const size_t need = items * (mode == 1 ? jpt * (niw > 1 ? niw : 1) : jpt) * 4 * sc;      // (the epilogue's reductions reuse the buffers)
         if (2 * P.lds1 < need) P.lds1 = (need + 63) / 64 * 32;
     }
-    if (2 * P.lds1 > lanes_lds_limit()) return P;
+    if (2 * P.lds1 > device_lds_limit()) return P;
     if ((size_t)C * (size_t)m_local * 8 * sc >= (1ull << 32)) return P;      // (32-bit byte offsets into the response / cotangent planes)
     P.ok = 1;
     return P;
@@ -758,53 +745,43 @@ static void lanes_fill(LanesArgs<T>& A, const LanesPlan& P) {
     A.lds1 = (int)P.lds1;
 }
 
+// psum / pq as left by the kernel above (nbx = fl_geq_bwd_lanes_blocks), b / a the designed taps -> ggain in the
+// parameter's dtype (in_kind); wn > 0: gW[e] = sum_r partW[r * wn + e], r < wrows
+template <typename T>
+static int lanes_sections_bwd_impl(const void* gain, int in_kind, const void* psum, const void* pq, int nbx, const void* b, const void* a,
+                                   double gamma, int nb, int C, const void* consts, void* ggain, const void* partW, int wrows, int wn,
+                                   void* gW, void* stream) {
+    FL_REQUIRE(gain && psum && pq && b && a && consts && ggain, "geq_sections_bwd_lanes: null pointer");
+    FL_REQUIRE(in_kind >= 0 && in_kind <= 4 && nb >= 4 && C > 0 && nbx > 0, "geq_sections_bwd_lanes: bad sizes");
+    FL_REQUIRE(wn == 0 || (partW && gW && wrows > 0), "geq_sections_bwd_lanes: bad constant-factor partials");
+    const int epb = nbx > 512 ? 1 : nbx > 256 ? 2 : 4;      // entries per workgroup: 4 / 2 / 1 wavefronts per entry
+    const int main_blocks = cdiv_i((long)nb * C, epb);
+    hipLaunchKernelGGL(geq_bwd_lanes_kernel<T>, dim3(main_blocks + cdiv_i(wn, 4)), dim3(256), 0, (hipStream_t)stream, gain, in_kind,
+                       (const T*)psum, (const T*)pq, nbx, (const double*)b, (const double*)a, gamma, nb, C,
+                       (const double*)consts, ggain, main_blocks, epb, (const T*)partW, wrows, wn, (T*)gW);
+    FL_CHECK_LAUNCH("geq_sections_bwd_lanes");
+    return FL_OK;
+}
+
 }  // namespace fl
 
 using namespace fl;
 
-extern "C" {
-int fl_debug_set_cascade_lanes(int on, int blocks_per_cu, int tile_bins) {
-    const int prev = g_lanes | ((g_lanes && !g_lanes_fwd) ? 2 : 0);      // (the previous `on`, the forward split included)
-    if (on >= 0) {
-        g_lanes = on & 1;
-        g_lanes_fwd = (on & 1) && !(on & 2);      // (on = 3: second-generation backward, first-generation forward)
-    }
-    if (blocks_per_cu >= 0) g_lanes_bpc = blocks_per_cu;
-    if (tile_bins >= 0) g_lanes_tb = tile_bins;
-    return prev;
-}
-
-int fl_debug_set_cascade_stamps(void* device_buffer, int skip) {
-    g_lanes_stamps = (long long*)device_buffer;
-    g_lanes_skip = skip;
-    return 0;
-}
-
-// rows of partW: one (Nmid, Ni) matrix per workgroup
-int fl_geq_bwd_lanes_wrows(int m_local, int C, int S, int nfft, int bin0, int ppr, int niw) {
-    const LanesPlan P = lanes_plan(m_local, C, S, nfft, bin0, ppr, niw, 1);
-    return P.ok ? P.nbx * P.ng : 0;
-}
-int fl_geq_bwd_lanes_wrows_f64(int m_local, int C, int S, int nfft, int bin0, int ppr, int niw) {
-    const LanesPlan P = lanes_plan(m_local, C, S, nfft, bin0, ppr, niw, 1, 8);
-    return P.ok ? P.nbx * P.ng : 0;
-}
-
-int fl_geq_bwd_lanes_blocks(int m_local, int C, int S, int nfft, int bin0, int ppr, int niw, int mode) {
+// ================================================================ the exported entries (C linkage), in the order of include/flamo_hip.h
+extern "C" int fl_geq_bwd_lanes_blocks(int m_local, int C, int S, int nfft, int bin0, int ppr, int niw, int mode) {
     const LanesPlan P = lanes_plan(m_local, C, S, nfft, bin0, ppr, niw, mode);
     return P.ok ? P.nbx : 0;
 }
-int fl_geq_bwd_lanes_blocks_f64(int m_local, int C, int S, int nfft, int bin0, int ppr, int niw, int mode) {
-    const LanesPlan P = lanes_plan(m_local, C, S, nfft, bin0, ppr, niw, mode, 8);
-    return P.ok ? P.nbx : 0;
+// rows of partW: one (Nmid, Ni) matrix per workgroup
+extern "C" int fl_geq_bwd_lanes_wrows(int m_local, int C, int S, int nfft, int bin0, int ppr, int niw) {
+    const LanesPlan P = lanes_plan(m_local, C, S, nfft, bin0, ppr, niw, 1);
+    return P.ok ? P.nbx * P.ng : 0;
 }
-}  // extern "C"
-
 // mode 0: gH planes c (C = channel pairs); mode 1: gH planes (m * Ni + n), G planes (m * Nmid + j), Wr (Nmid, Ni), partW out
-template <typename T>
-static int lanes_bwd_impl(int mode, const void* gH, long g_pitch, const void* G, long h_pitch, const void* b, const void* a, int S, int No,
-                          int Nmid, int Ni, const void* Wr, double gamma, const void* Wd, int nfft, int bin0, int m_local, void* psum,
-                          void* pq, void* partW, void* stream) {
+FL_ENTRY_C64_C128(fl_geq_response_bwd_lanes, (int mode, const void* gH, long g_pitch, const void* G, long h_pitch, const void* b, const void* a,
+                                              int S, int No, int Nmid, int Ni, const void* Wr, double gamma, const void* Wd, int nfft,
+                                              int bin0, int m_local, void* psum, void* pq, void* partW, void* stream),
+                  (mode, gH, g_pitch, G, h_pitch, b, a, S, No, Nmid, Ni, Wr, gamma, Wd, nfft, bin0, m_local, psum, pq, partW, stream)) {
     FL_REQUIRE(mode == 0 || mode == 1, "geq_response_bwd_lanes: mode 0 (plain) or 1 (constant factor)");
     FL_REQUIRE(gH && G && b && a && Wd && psum && pq, "geq_response_bwd_lanes: null pointer");
     FL_REQUIRE(mode == 0 || (Wr && partW), "geq_response_bwd_lanes: the constant-factor mode needs Wr and partW");
@@ -826,61 +803,48 @@ static int lanes_bwd_impl(int mode, const void* gH, long g_pitch, const void* G,
     lanes_fill(A, P);
     const dim3 grid(P.nbx, P.ng), block(P.threads);
     const size_t lds = 2 * P.lds1;
-#define FL_LANES(NIW_, PPR_)                                                                                                     \
-    {                                                                                                                            \
-        static bool done[64] = {};                                                                                               \
-        auto kern = sos_bwd_lanes_kernel<T, NIW_, PPR_, 2, false>;                                                               \
-        const int rc_ = lanes_ensure_lds(reinterpret_cast<const void*>(kern), lds, done);                                        \
-        if (rc_) return rc_;                                                                                                     \
-        hipLaunchKernelGGL(kern, grid, block, lds, (hipStream_t)stream, A);                                                      \
-    }
-    if (mode == 0) FL_LANES(0, 1)
-    else if (Ni == 8) FL_LANES(8, 8)
-    else if (Ni == 4) FL_LANES(4, 4)
-    else if (Ni == 2) FL_LANES(2, 2)
-    else FL_LANES(16, 16)
-#undef FL_LANES
+    int rc = FL_OK;
+    dispatch<0, 8, 4, 2, 16>(mode == 0 ? 0 : Ni, [&](auto NIW) {      // (mode 1: the plan took one of these four)
+        constexpr int niw = decltype(NIW)::value;
+        static bool done[kMaxDevices] = {};
+        auto kern = sos_bwd_lanes_kernel<T, niw, niw ? niw : 1, 2, false>;
+        rc = lanes_ensure_lds(reinterpret_cast<const void*>(kern), lds, done);
+        if (rc == FL_OK) hipLaunchKernelGGL(kern, grid, block, lds, (hipStream_t)stream, A);
+    });
+    if (rc) return rc;
     FL_CHECK_LAUNCH("geq_response_bwd_lanes");
     return FL_OK;
 }
-
-// psum / pq as left by the kernel above (nbx = fl_geq_bwd_lanes_blocks), b / a the designed taps -> ggain in the
-// parameter's dtype (in_kind); wn > 0: gW[e] = sum_r partW[r * wn + e], r < wrows
-template <typename T>
-static int lanes_sections_bwd_impl(const void* gain, int in_kind, const void* psum, const void* pq, int nbx, const void* b, const void* a,
-                                   double gamma, int nb, int C, const void* consts, void* ggain, const void* partW, int wrows, int wn,
-                                   void* gW, void* stream) {
-    FL_REQUIRE(gain && psum && pq && b && a && consts && ggain, "geq_sections_bwd_lanes: null pointer");
-    FL_REQUIRE(in_kind >= 0 && in_kind <= 4 && nb >= 4 && C > 0 && nbx > 0, "geq_sections_bwd_lanes: bad sizes");
-    FL_REQUIRE(wn == 0 || (partW && gW && wrows > 0), "geq_sections_bwd_lanes: bad constant-factor partials");
-    const int epb = nbx > 512 ? 1 : nbx > 256 ? 2 : 4;      // entries per workgroup: 4 / 2 / 1 wavefronts per entry
-    const int main_blocks = cdiv_i((long)nb * C, epb);
-    hipLaunchKernelGGL(geq_bwd_lanes_kernel<T>, dim3(main_blocks + cdiv_i(wn, 4)), dim3(256), 0, (hipStream_t)stream, gain, in_kind,
-                       (const T*)psum, (const T*)pq, nbx, (const double*)b, (const double*)a, gamma, nb, C,
-                       (const double*)consts, ggain, main_blocks, epb, (const T*)partW, wrows, wn, (T*)gW);
-    FL_CHECK_LAUNCH("geq_sections_bwd_lanes");
-    return FL_OK;
-}
-
-extern "C" {
-int fl_geq_response_bwd_lanes_c64(int mode, const void* gH, long g_pitch, const void* G, long h_pitch, const void* b, const void* a,
-                                  int S, int No, int Nmid, int Ni, const void* Wr, double gamma, const void* Wd, int nfft,
-                                  int bin0, int m_local, void* psum, void* pq, void* partW, void* stream) {
-    return lanes_bwd_impl<float>(mode, gH, g_pitch, G, h_pitch, b, a, S, No, Nmid, Ni, Wr, gamma, Wd, nfft, bin0, m_local, psum, pq, partW, stream);
-}
-int fl_geq_response_bwd_lanes_c128(int mode, const void* gH, long g_pitch, const void* G, long h_pitch, const void* b, const void* a,
-                                   int S, int No, int Nmid, int Ni, const void* Wr, double gamma, const void* Wd, int nfft,
-                                   int bin0, int m_local, void* psum, void* pq, void* partW, void* stream) {
-    return lanes_bwd_impl<double>(mode, gH, g_pitch, G, h_pitch, b, a, S, No, Nmid, Ni, Wr, gamma, Wd, nfft, bin0, m_local, psum, pq, partW, stream);
-}
-int fl_geq_sections_bwd_lanes(const void* gain, int in_kind, const void* psum, const void* pq, int nbx, const void* b, const void* a,
-                              double gamma, int nb, int C, const void* consts, void* ggain, const void* partW, int wrows, int wn,
-                              void* gW, void* stream) {
+extern "C" int fl_geq_sections_bwd_lanes(const void* gain, int in_kind, const void* psum, const void* pq, int nbx, const void* b, const void* a,
+                                         double gamma, int nb, int C, const void* consts, void* ggain, const void* partW, int wrows, int wn,
+                                         void* gW, void* stream) {
     return lanes_sections_bwd_impl<float>(gain, in_kind, psum, pq, nbx, b, a, gamma, nb, C, consts, ggain, partW, wrows, wn, gW, stream);
 }
-int fl_geq_sections_bwd_lanes_f64(const void* gain, int in_kind, const void* psum, const void* pq, int nbx, const void* b, const void* a,
-                                  double gamma, int nb, int C, const void* consts, void* ggain, const void* partW, int wrows, int wn,
-                                  void* gW, void* stream) {
+extern "C" int fl_geq_bwd_lanes_blocks_f64(int m_local, int C, int S, int nfft, int bin0, int ppr, int niw, int mode) {
+    const LanesPlan P = lanes_plan(m_local, C, S, nfft, bin0, ppr, niw, mode, 8);
+    return P.ok ? P.nbx : 0;
+}
+extern "C" int fl_geq_bwd_lanes_wrows_f64(int m_local, int C, int S, int nfft, int bin0, int ppr, int niw) {
+    const LanesPlan P = lanes_plan(m_local, C, S, nfft, bin0, ppr, niw, 1, 8);
+    return P.ok ? P.nbx * P.ng : 0;
+}
+extern "C" int fl_geq_sections_bwd_lanes_f64(const void* gain, int in_kind, const void* psum, const void* pq, int nbx, const void* b, const void* a,
+                                             double gamma, int nb, int C, const void* consts, void* ggain, const void* partW, int wrows,
+                                             int wn, void* gW, void* stream) {
     return lanes_sections_bwd_impl<double>(gain, in_kind, psum, pq, nbx, b, a, gamma, nb, C, consts, ggain, partW, wrows, wn, gW, stream);
 }
-}  // extern "C"
+extern "C" int fl_debug_set_cascade_lanes(int on, int blocks_per_cu, int tile_bins) {
+    const int prev = g_lanes | ((g_lanes && !g_lanes_fwd) ? 2 : 0);      // (the previous `on`, the forward split included)
+    if (on >= 0) {
+        g_lanes = on & 1;
+        g_lanes_fwd = (on & 1) && !(on & 2);      // (on = 3: second-generation backward, first-generation forward)
+    }
+    if (blocks_per_cu >= 0) g_lanes_bpc = blocks_per_cu;
+    if (tile_bins >= 0) g_lanes_tb = tile_bins;
+    return prev;
+}
+extern "C" int fl_debug_set_cascade_stamps(void* device_buffer, int skip) {
+    g_lanes_stamps = (long long*)device_buffer;
+    g_lanes_skip = skip;
+    return 0;
+}

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/flamo_hip.h"
 
 namespace fl {
@@ -242,6 +244,54 @@ int check_hip(hipError_t e, const char* what);
     } while (0)
 
 static inline int cdiv_i(long a, long b) { return (int)((a + b - 1) / b); }
+
+// ---------------------------------------------------------------- host helpers the sources share
+// A run-time integer becomes a template argument: dispatch<2, 4, 8>(v, f) calls f(std::integral_constant<int, V>{}) for the V
+// that equals v and returns false when none does (the caller's "no kernel for ..." error).  Two-level choices nest two calls.
+template <int... Vs, class F>
+static inline bool dispatch(int v, F&& f) {
+    return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+
+// compute units of the CURRENT device (asked per call: a few hundred nanoseconds beside a launch); 256 with no device to ask
+static inline int device_cus() {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+    return v;
+}
+// LDS a workgroup of the current device may ask for; the default 64 KB with no device to ask
+static inline size_t device_lds_limit() {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || v <= 0) v = 64 * 1024;
+    return (size_t)v;
+}
+// More dynamic LDS than the default 64 KB: the attribute is per function AND per device, so it is set once per (kernel, device)
+// -- a second GPU used by the same process gets its own -- and its result is checked (a part with less LDS per workgroup fails
+// here with a message that starts with `who`, not at the launch).  done: the kernel's own flags, one per device; to_limit: raise
+// the attribute to the device's limit rather than to this request.
+constexpr int kMaxDevices = 64;
+static inline int ensure_dynamic_lds(const void* kern, size_t lds, bool to_limit, bool* done /* [kMaxDevices] */, const char* who) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = 0;
+    if (done[dev]) return FL_OK;
+    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(to_limit ? device_lds_limit() : lds));
+    if (e != hipSuccess) {
+        set_error("%s: %zu bytes of LDS per workgroup are not available on device %d (%s)", who, lds, dev, hipGetErrorString(e));
+        return FL_ERR_UNSUPPORTED;
+    }
+    done[dev] = true;
+    return FL_OK;
+}
+
+// An entry that exists in both precisions, written ONCE: FL_ENTRY_C64_C128(name, (parameters), (arguments)) { body } makes the
+// body template <class T> static int name_entry(parameters), and the exported symbols name_c64 / name_c128 (declared in
+// include/flamo_hip.h: a parameter list that differs from the declaration does not compile) one-line forwards to
+// name_entry<float> / name_entry<double>.
+#define FL_ENTRY_C64_C128(NAME, PARAMS, ARGS)                                             \
+    template <class T> static int NAME##_entry PARAMS;                                    \
+    extern "C" int NAME##_c64 PARAMS { return NAME##_entry<float> ARGS; }                 \
+    extern "C" int NAME##_c128 PARAMS { return NAME##_entry<double> ARGS; }               \
+    template <class T> static int NAME##_entry PARAMS
 
 // ---------------------------------------------------------------- cache policy of the pipeline's data streams (host)
 // Each stream of the fused Shell pipeline (spectral.hip, specwalk.hip) and of the cascade kernels is loaded / stored either with

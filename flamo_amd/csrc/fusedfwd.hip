@@ -39,6 +39,11 @@ __global__ void __launch_bounds__(256, 5) cols_fwd_rc_kernel(ColsArgs a, RcBaArg
     }
 }
 
+static void pin_kernel_order() {      // the code object's kernel order, kept as it has always been (see response.hip)
+    (void)&cols_fwd_rc_kernel<8, 25, 16, 1, true, 8>, (void)&cols_fwd_rc_kernel<8, 25, 16, 1, true, 4>,
+        (void)&cols_fwd_rc_kernel<8, 25, 16, 1, false, 8>, (void)&cols_fwd_rc_kernel<8, 25, 16, 1, false, 4>;
+}
+
 static thread_local bool t_pair_mode = false, t_have = false;
 static thread_local PendingRc t_pending;
 static long long* g_pair_dbg = nullptr;      // fl_debug_set_pair_stamps
@@ -75,17 +80,12 @@ int fused_cols_rc_launch(const ColsArgs& a, unsigned n_cols, const PendingRc& rc
     if (n_mix < n_rc) n_mix = n_rc;
     RcBaArgs rargs = rc.args;
     rargs.dbg = g_pair_dbg ? g_pair_dbg + 4 * 8192 : nullptr;      // (phase stamps of the response role behind the per-workgroup records)
-#define FL_PAIR(PLAIN_, NIW_)                                                                                          \
-    hipLaunchKernelGGL((cols_fwd_rc_kernel<A, B, 16, 1, PLAIN_, NIW_>), dim3((unsigned)total), dim3(256), lds, st, a, rargs, \
-                       (int)n_mix, (int)n_rc, rc.gx, g_pair_dbg)
-    if (plain) {
-        if (rc.niw == 8) FL_PAIR(true, 8);
-        else FL_PAIR(true, 4);
-    } else {
-        if (rc.niw == 8) FL_PAIR(false, 8);
-        else FL_PAIR(false, 4);
-    }
-#undef FL_PAIR
+    dispatch<1, 0>(plain, [&](auto PLAIN) {
+        dispatch<8, 4>(rc.niw, [&](auto NIW) {
+            hipLaunchKernelGGL((cols_fwd_rc_kernel<A, B, 16, 1, decltype(PLAIN)::value != 0, decltype(NIW)::value>), dim3((unsigned)total), dim3(256),
+                               lds, st, a, rargs, (int)n_mix, (int)n_rc, rc.gx, g_pair_dbg);
+        });
+    });
     FL_CHECK_LAUNCH("cols_fwd_rc");
     ++g_pair_launches;
     return FL_OK;

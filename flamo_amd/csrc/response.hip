@@ -1028,6 +1028,38 @@ __global__ void __launch_bounds__(256) geq_sections_bwd_kernel(const void* __res
     geq_store_gain_grad(ggain, in_kind, idx, dg, g, raw);
 }
 
+
+// The code object lists the template kernels in the order in which they are first named, and the dispatchers below name them
+// from inside generic lambdas, whose order of instantiation is the compiler's.  The order is pinned here, ahead of all host code, to
+// the one the code object has always had: a host-side change leaves the device code byte-identical (which is how it is checked).
+static void pin_kernel_order() {
+    (void)&delay_response_kernel<float>, (void)&delay_response_kernel<double>, (void)&sos_response_kernel<float>,
+        (void)&sos_response_kernel<double>, (void)&sos_response_bwd_mixed_kernel<4, 0>, (void)&sos_response_bwd_mixed_kernel<4, 2>,
+        (void)&sos_response_bwd_mixed_kernel<4, 4>, (void)&sos_response_bwd_mixed_kernel<4, 8>, (void)&sos_response_bwd_mixed_kernel<4, 16>,
+        (void)&sos_response_bwd_mixed_kernel<6, 0>, (void)&sos_response_bwd_mixed_kernel<6, 2>, (void)&sos_response_bwd_mixed_kernel<6, 4>,
+        (void)&sos_response_bwd_mixed_kernel<6, 8>, (void)&sos_response_bwd_mixed_kernel<6, 16>, (void)&sos_response_bwd_mixed_kernel<8, 0>,
+        (void)&sos_response_bwd_mixed_kernel<8, 2>, (void)&sos_response_bwd_mixed_kernel<8, 4>, (void)&sos_response_bwd_mixed_kernel<8, 8>,
+        (void)&sos_response_bwd_mixed_kernel<8, 16>, (void)&sos_response_bwd_mixed_kernel<12, 0>, (void)&sos_response_bwd_mixed_kernel<12, 2>,
+        (void)&sos_response_bwd_mixed_kernel<12, 4>, (void)&sos_response_bwd_mixed_kernel<12, 8>, (void)&sos_response_bwd_mixed_kernel<12, 16>,
+        (void)&sos_response_bwd_kernel<float, 12>, (void)&sos_response_bwd_kernel<float, 6>, (void)&sos_response_bwd_kernel<float, 3>,
+        (void)&sos_response_bwd_kernel<float, 4>, (void)&sos_response_rc_fast_kernel<2, 2>, (void)&sos_response_rc_fast_kernel<2, 3>,
+        (void)&sos_response_rc_fast_kernel<2, 6>, (void)&sos_response_rc_fast_kernel<2, 1>, (void)&sos_response_rc_kernel<2, float>,
+        (void)&sos_response_rc_fast_kernel<4, 2>, (void)&sos_response_rc_fast_kernel<4, 3>, (void)&sos_response_rc_fast_kernel<4, 6>,
+        (void)&sos_response_rc_fast_kernel<4, 1>, (void)&sos_response_rc_kernel<4, float>, (void)&sos_response_rc_fast_kernel<8, 2>,
+        (void)&sos_response_rc_fast_kernel<8, 3>, (void)&sos_response_rc_fast_kernel<8, 6>, (void)&sos_response_rc_fast_kernel<8, 1>,
+        (void)&sos_response_rc_kernel<8, float>, (void)&sos_response_rc_fast_kernel<16, 2>, (void)&sos_response_rc_fast_kernel<16, 3>,
+        (void)&sos_response_rc_fast_kernel<16, 6>, (void)&sos_response_rc_fast_kernel<16, 1>, (void)&sos_response_rc_kernel<16, float>,
+        (void)&sos_response_rc_kernel<2, double>, (void)&sos_response_rc_kernel<4, double>, (void)&sos_response_rc_kernel<8, double>,
+        (void)&sos_response_rc_kernel<16, double>, (void)&sos_response_apply_fast_kernel<1>, (void)&sos_response_apply_fast_kernel<2>,
+        (void)&sos_response_bwd_kernel<double, 6, 2>, (void)&sos_response_bwd_kernel<double, 6, 4>, (void)&sos_response_bwd_kernel<double, 6, 8>,
+        (void)&sos_response_bwd_kernel<double, 6, 16>, (void)&sos_response_bwd_kernel<double, 12>, (void)&sos_response_bwd_kernel<double, 6>,
+        (void)&sos_response_bwd_kernel<double, 3>, (void)&sos_response_bwd_kernel<double, 4>;
+}
+
+// ================================================================ host side
+// Launch helpers (namespace fl) over the kernels above, then the exported entries in one section at the end of the file.  Where a
+// run-time integer selects a template instantiation -- section chunk, columns of the constant factor, section pairs per trip,
+// signal columns -- it goes through fl::dispatch (common.h).
 static int g_sos_chunk = 0;
 static int g_rc_fast = 6;   // cascade-times-matrix forward: float evaluation in the 1 -+ w basis, section pairs per loop trip (1 | 2 | 3 | 6; 0: the double kernel)
 static int g_sos_blocks = 0;
@@ -1047,37 +1079,26 @@ static int sos_chunk_of(int S, bool mixed) {
 }
 
 static int sos_blocks(int m_local, int C, int S, bool mixed) {
-    int cus = 256;       // of the CURRENT device (asked per call: a few hundred nanoseconds beside a launch)
-    {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
     const int nz = cdiv_i(S, sos_chunk_of(S, mixed));
-    int nb = g_sos_blocks > 0 ? g_sos_blocks : (2 * cus) / (C * nz > 0 ? C * nz : 1);
+    int nb = g_sos_blocks > 0 ? g_sos_blocks : (2 * device_cus()) / (C * nz > 0 ? C * nz : 1);
     const int cap = cdiv_i(m_local, 256);
     if (nb > cap) nb = cap;
     if (nb < 1) nb = 1;
     return nb;
 }
 
-template <typename T>
-static int delay_impl(const int32_t* m, const void* amp, int C, const void* W, int nfft, int bin0, int m_local, void* H,
-                      long h_pitch, void* stream) {
-    FL_REQUIRE(m && amp && W && H, "delay_response: null pointer");
-    FL_REQUIRE(h_pitch >= m_local, "delay_response: h_pitch must be >= m_local");
-    FL_REQUIRE(C > 0 && C <= 65535 && nfft > 0 && bin_range_ok(bin0, m_local, nfft) && m_local >= 0, "delay_response: bad sizes");
-    if (m_local == 0) return FL_OK;
-    dim3 grid(cdiv_i(m_local, 256), C);
-    hipLaunchKernelGGL((delay_response_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, m, (const T*)amp,
-                       (const cx<T>*)W, nfft, 1.0 / (double)nfft, bin0, m_local, (cx<T>*)H, h_pitch);
-    FL_CHECK_LAUNCH("delay_response");
+// the equaliser's sections from its gains: on its own, or in front of a double kernel that reads them
+static int geq_sections_launch(const GeqDesign& gd, int nb, int C, void* stream) {
+    hipLaunchKernelGGL(geq_sections_kernel, dim3(cdiv_i((long)nb * C, 256)), dim3(256), 0, (hipStream_t)stream, gd.gain, gd.in_kind, nb, C,
+                       gd.k, gd.b_out, gd.a_out);
+    FL_CHECK_LAUNCH("geq_sections");
     return FL_OK;
 }
 
+// ---------------------------------------------------------------- forward: cascade response
 template <typename T>
 static int sos_impl(const void* b, const void* a, int S, int C, double gamma, const void* Wd, int nfft, int bin0,
-                    int m_local, void* H, long h_pitch, void* stream, bool float_eval = false,
-                    GeqDesign gd = GeqDesign{nullptr, 0, nullptr, nullptr, nullptr}) {
+                    int m_local, void* H, long h_pitch, void* stream, bool float_eval = false, GeqDesign gd = GeqDesign{}) {
     FL_REQUIRE(b && a && H && Wd, "sos_response: null pointer");
     FL_REQUIRE(h_pitch >= m_local, "sos_response: h_pitch must be >= m_local");
     FL_REQUIRE(S > 0 && S <= 1024 && C > 0 && C <= 65535 && nfft > 0 && bin_range_ok(bin0, m_local, nfft) && m_local >= 0, "sos_response: bad sizes");
@@ -1093,9 +1114,8 @@ static int sos_impl(const void* b, const void* a, int S, int C, double gamma, co
         }
     }
     if (gd.gain) {      // the double kernel reads its sections: design them first
-        hipLaunchKernelGGL(geq_sections_kernel, dim3(cdiv_i(S * C, 256)), dim3(256), 0, (hipStream_t)stream, gd.gain, gd.in_kind, S, C, gd.k,
-                           gd.b_out, gd.a_out);
-        FL_CHECK_LAUNCH("geq_sections");
+        const int rc = geq_sections_launch(gd, S, C, stream);
+        if (rc) return rc;
     }
     dim3 grid(cdiv_i(m_local, 256), C);
     hipLaunchKernelGGL((sos_response_kernel<T>), grid, dim3(256), (size_t)6 * S * sizeof(double), (hipStream_t)stream, (const double*)b, (const double*)a, S, C,
@@ -1104,160 +1124,144 @@ static int sos_impl(const void* b, const void* a, int S, int C, double gamma, co
     return FL_OK;
 }
 
+// ---------------------------------------------------------------- forward: cascade response times a constant matrix
+// checks; the second generation (cascade2.hip) if it takes the shape; the first-generation float kernel; else design + double kernel
 template <typename T>
-static int sos_bwd_impl(const void* gH, long g_pitch, const void* H, long h_pitch, const void* b, const void* a, int S, int C,
-                        double gamma, const void* Wd, int nfft, int bin0, int m_local, void* part, void* stream,
-                        int rc_ni = 0, SosRC rc = SosRC{0, 0, nullptr, nullptr}, SosRCd rcd = SosRCd{0, 0, nullptr, nullptr}) {
-    FL_REQUIRE((gH || rc.oG) && b && a && part && Wd, "sos_response_bwd: null pointer");
-    FL_REQUIRE(g_pitch >= m_local && (!H || h_pitch >= m_local), "sos_response_bwd: g_pitch / h_pitch must be >= m_local");
-    FL_REQUIRE(S > 0 && S <= 1024 && C > 0 && C <= 65535 && nfft > 0 && bin_range_ok(bin0, m_local, nfft) && m_local > 0, "sos_response_bwd: bad sizes");
+static int rc_impl(const void* b, const void* a, int S, int No, int Nmid, int Ni, const void* Wr, double gamma,
+                   const void* Wd, int nfft, int bin0, int m_local, void* G, long g_pitch, void* H, long h_pitch,
+                   int float_eval, void* stream, GeqDesign gd) {
+    FL_REQUIRE(b && a && Wr && Wd && G && H, "sos_response_rc: null pointer");
+    FL_REQUIRE(g_pitch >= m_local && h_pitch >= m_local, "sos_response_rc: pitches must be >= m_local");
+    FL_REQUIRE(S > 0 && S <= 64 && No > 0 && No <= 65535 && Nmid > 0 && Nmid <= 32 && nfft > 0 && bin_range_ok(bin0, m_local, nfft) &&
+                   m_local >= 0, "sos_response_rc: bad sizes");
+    if (m_local == 0) return FL_OK;
+    const size_t lds = (size_t)Nmid * 6 * S * sizeof(double) + (size_t)Nmid * Ni * sizeof(T);
+    FL_REQUIRE(lds <= 64 * 1024, "sos_response_rc: the coefficient tables of one output row exceed 64 KB of LDS");
     if constexpr (sizeof(T) == 4) {
-        if (H) {
-#define FL_SOS_MIX(SC)                                                                                              \
-    {                                                                                                               \
-        dim3 grid(sos_blocks(m_local, C, S, true), C, cdiv_i(S, SC));                                               \
-        if (rc_ni > 0) {                                                                                           \
-            rc.nbx = sos_blocks(m_local, C, S, true);                                                              \
-            grid = dim3(cdiv_i((C / rc.Nmid) * rc.nbx, 8) * 8 * rc.Nmid, 1, cdiv_i(S, SC));                        \
-        }                                                                                                          \
-        const size_t lds = (size_t)(6 * S + 2) * sizeof(double) + (size_t)12 * SC * sizeof(float);    \
-        FL_SOS_MIX_N(SC, 0) else FL_SOS_MIX_N(SC, 2) else FL_SOS_MIX_N(SC, 4) else FL_SOS_MIX_N(SC, 8)            \
-        else FL_SOS_MIX_N(SC, 16) else {                                                                          \
-            set_error("sos_response_bwd: no kernel for %d input channels of the constant factor", rc_ni);          \
-            return FL_ERR_UNSUPPORTED;                                                                             \
-        }                                                                                                          \
-    }
-#define FL_SOS_MIX_N(SC, NIW_)                                                                                      \
-    if (rc_ni == NIW_)                                                                                              \
-        hipLaunchKernelGGL((sos_response_bwd_mixed_kernel<SC, NIW_>), grid, dim3(256), lds, (hipStream_t)stream,   \
-                           (const cx<float>*)gH, g_pitch, (const cx<float>*)H, h_pitch, (const double*)b,           \
-                           (const double*)a, S, C, gamma, (const cx<double>*)Wd, nfft, bin0, m_local, (double*)part, rc);
-            const int sc = sos_chunk_of(S, true);
-            if (sc == 4) FL_SOS_MIX(4)
-            else if (sc == 6) FL_SOS_MIX(6)
-            else if (sc == 8) FL_SOS_MIX(8)
-            else FL_SOS_MIX(12)
-#undef FL_SOS_MIX
-#undef FL_SOS_MIX_N
-            FL_CHECK_LAUNCH("sos_response_bwd");
-            return FL_OK;
-        }
-    }
-    FL_REQUIRE(!rc.oG, "sos_response_bwd: the outer-product mode needs float32 and the saved forward response");
-    if (rc_ni > 0) {      // constant-factor mode of the all-double kernel: one section chunk (the NIW gradient planes are read once)
-        if constexpr (sizeof(T) == 8) {
-            FL_REQUIRE(H && rcd.Wr && rcd.partW && rcd.Nmid > 0, "sos_response_bwd: constant-factor mode needs the saved response");
-            rcd.nbx = sos_blocks(m_local, C, S, false);
-            const dim3 grid(cdiv_i((C / rcd.Nmid) * rcd.nbx, 8) * 8 * rcd.Nmid, 1, cdiv_i(S, 6));
-#define FL_SOS_BWD_RC(NIW_)                                                                                              \
-    if (rc_ni == NIW_)                                                                                                   \
-        hipLaunchKernelGGL((sos_response_bwd_kernel<double, 6, NIW_>), grid, dim3(256), (size_t)6 * S * sizeof(double), \
-                           (hipStream_t)stream, (const cx<double>*)gH, g_pitch, (const cx<double>*)H, h_pitch,           \
-                           (const double*)b, (const double*)a, S, C, gamma, (const cx<double>*)Wd, nfft, bin0, m_local,  \
-                           (double*)part, rcd);
-            FL_SOS_BWD_RC(2) else FL_SOS_BWD_RC(4) else FL_SOS_BWD_RC(8) else FL_SOS_BWD_RC(16) else {
-                set_error("sos_response_bwd: no kernel for %d input channels of the constant factor", rc_ni);
-                return FL_ERR_UNSUPPORTED;
+        if (g_rc_fast && float_eval) {
+            const int rc2 = rc_ba_launch(b, a, S, No, Nmid, Ni, Wr, gamma, Wd, nfft, bin0, m_local, G, g_pitch, H, h_pitch, stream, gd);
+            if (rc2 != FL_ERR_UNSUPPORTED) return rc2;      // (shapes the second generation does not take fall through)
+            const size_t lds_fast = ((size_t)Nmid * 12 * ((S + 1) & ~1) + (size_t)Nmid * Ni) * sizeof(float);
+            const dim3 grid_fast(cdiv_i(rc_npairs(nfft, bin0, m_local), 256), No);
+            const int unr = (g_rc_fast == 2 || g_rc_fast == 3 || g_rc_fast == 6) ? g_rc_fast : 1;
+            if (dispatch<2, 4, 8, 16>(Ni, [&](auto NIW) {
+                    dispatch<2, 3, 6, 1>(unr, [&](auto UNR) {
+                        hipLaunchKernelGGL((sos_response_rc_fast_kernel<decltype(NIW)::value, decltype(UNR)::value>), grid_fast, dim3(256),
+                                           lds_fast, (hipStream_t)stream, (const double*)b, (const double*)a, S, No * Nmid, Nmid,
+                                           (const float*)Wr, gamma, (const cx<double>*)Wd, nfft, bin0, m_local, (cx<float>*)G, g_pitch,
+                                           (cx<float>*)H, h_pitch, gd);
+                    });
+                })) {
+                FL_CHECK_LAUNCH("sos_response_rc_fast");
+                return FL_OK;
             }
-#undef FL_SOS_BWD_RC
-            FL_CHECK_LAUNCH("sos_response_bwd_rc");
-            return FL_OK;
         }
-        set_error("sos_response_bwd: the float32 constant-factor mode needs the saved forward response");
-        return FL_ERR_BAD_ARG;
     }
-    const int sch = sos_chunk_of(S, false);
-#define FL_SOS_BWD(SC)                                                                                              \
-    {                                                                                                               \
-        dim3 grid(sos_blocks(m_local, C, S, false), C, cdiv_i(S, SC));                                              \
-        hipLaunchKernelGGL((sos_response_bwd_kernel<T, SC>), grid, dim3(256), (size_t)6 * S * sizeof(double),      \
-                           (hipStream_t)stream, (const cx<T>*)gH, g_pitch, (const cx<T>*)H, h_pitch, (const double*)b, (const double*)a, S, C, gamma, \
-                           (const cx<double>*)Wd, nfft, bin0, m_local, (double*)part, SosRCd{0, 0, nullptr, nullptr}); \
+    int rc = FL_OK;
+    if (!dispatch<2, 4, 8, 16>(Ni, [&](auto NIW) {
+            if (gd.gain) rc = geq_sections_launch(gd, S, No * Nmid, stream);      // the double kernel reads its sections: design them first
+            if (rc == FL_OK)
+                hipLaunchKernelGGL((sos_response_rc_kernel<decltype(NIW)::value, T>), dim3(cdiv_i(m_local, 256), No), dim3(256), lds,
+                                   (hipStream_t)stream, (const double*)b, (const double*)a, S, No * Nmid, Nmid, (const T*)Wr, gamma,
+                                   (const cx<double>*)Wd, nfft, bin0, m_local, (cx<T>*)G, g_pitch, (cx<T>*)H, h_pitch);
+        })) {
+        set_error("sos_response_rc: no kernel for %d input channels of the constant factor", Ni);
+        return FL_ERR_UNSUPPORTED;
     }
-    if (sch == 12) FL_SOS_BWD(12)
-    else if (sch == 6) FL_SOS_BWD(6)
-    else if (sch == 3) FL_SOS_BWD(3)
-    else FL_SOS_BWD(4)
-#undef FL_SOS_BWD
+    if (rc) return rc;
+    FL_CHECK_LAUNCH("sos_response_rc");
+    return FL_OK;
+}
+
+template <typename T>
+static int geq_rc_impl(const void* gain, int in_kind, int nb, const void* consts, void* b, void* a, int No, int Nmid, int Ni,
+                       const void* Wr, double gamma, const void* Wd, int nfft, int bin0, int m_local, void* G, long g_pitch,
+                       void* H, long h_pitch, int float_eval, void* stream) {
+    FL_REQUIRE(gain && consts, "geq_response_rc: null pointer");
+    FL_REQUIRE(in_kind >= 0 && in_kind <= 4 && nb >= 4, "geq_response_rc: in_kind in [0, 4], at least four bands");
+    const GeqDesign gd{gain, in_kind, (const double*)consts, (double*)b, (double*)a};
+    if (m_local == 0) return geq_sections_launch(gd, nb, No * Nmid, stream);      // nothing to evaluate: the sections are still an output
+    return rc_impl<T>(b, a, nb, No, Nmid, Ni, Wr, gamma, Wd, nfft, bin0, m_local, G, g_pitch, H, h_pitch, float_eval, stream, gd);
+}
+
+// ---------------------------------------------------------------- backward: what an entry asks for, behind one validation
+struct SosBwd {      // the operands every cascade backward launch takes
+    const void* gH; long g_pitch;
+    const void* H; long h_pitch;      // the saved forward response, or null: evaluated again
+    const void *b, *a;
+    int S, C;
+    double gamma;
+    const void* Wd;
+    int nfft, bin0, m_local;
+    void* part;
+    void* stream;
+};
+
+// grad: the cotangent the kernel reads (dL/dH; the outer-product mode's dL/dY)
+static int sos_bwd_check(const SosBwd& A, const void* grad) {
+    FL_REQUIRE(grad && A.b && A.a && A.part && A.Wd, "sos_response_bwd: null pointer");
+    FL_REQUIRE(A.g_pitch >= A.m_local && (!A.H || A.h_pitch >= A.m_local), "sos_response_bwd: g_pitch / h_pitch must be >= m_local");
+    FL_REQUIRE(A.S > 0 && A.S <= 1024 && A.C > 0 && A.C <= 65535 && A.nfft > 0 && bin_range_ok(A.bin0, A.m_local, A.nfft) && A.m_local > 0,
+               "sos_response_bwd: bad sizes");
+    return FL_OK;
+}
+
+// float with the saved response.  rc as the entry filled it: empty (plain), the constant factor (rc_ni columns: Nmid, Wr, partW)
+// or the outer product (oG, oX, ...)
+static int sos_bwd_mixed_launch(const SosBwd& A, SosRC rc = SosRC{}, int rc_ni = 0) {
+    const int sc = sos_chunk_of(A.S, true);
+    dim3 grid(sos_blocks(A.m_local, A.C, A.S, true), A.C, cdiv_i(A.S, sc));
+    if (rc_ni > 0) {
+        rc.nbx = grid.x;
+        grid = dim3(cdiv_i((A.C / rc.Nmid) * rc.nbx, 8) * 8 * rc.Nmid, 1, grid.z);
+    }
+    const size_t lds = (size_t)(6 * A.S + 2) * sizeof(double) + (size_t)12 * sc * sizeof(float);
+    bool known = false;
+    dispatch<4, 6, 8, 12>(sc, [&](auto SC) {
+        known = dispatch<0, 2, 4, 8, 16>(rc_ni, [&](auto NIW) {
+            hipLaunchKernelGGL((sos_response_bwd_mixed_kernel<decltype(SC)::value, decltype(NIW)::value>), grid, dim3(256), lds,
+                               (hipStream_t)A.stream, (const cx<float>*)A.gH, A.g_pitch, (const cx<float>*)A.H, A.h_pitch, (const double*)A.b,
+                               (const double*)A.a, A.S, A.C, A.gamma, (const cx<double>*)A.Wd, A.nfft, A.bin0, A.m_local, (double*)A.part, rc);
+        });
+    });
+    if (!known) {
+        set_error("sos_response_bwd: no kernel for %d input channels of the constant factor", rc_ni);
+        return FL_ERR_UNSUPPORTED;
+    }
     FL_CHECK_LAUNCH("sos_response_bwd");
     return FL_OK;
 }
 
-}  // namespace fl
-
-using namespace fl;
-
-extern "C" {
-int fl_delay_response_c64(const int32_t* m, const void* amp, int C, const void* W, int nfft, int bin0, int m_local,
-                          void* H, long h_pitch, void* stream) {
-    return delay_impl<float>(m, amp, C, W, nfft, bin0, m_local, H, h_pitch, stream);
-}
-int fl_delay_response_c128(const int32_t* m, const void* amp, int C, const void* W, int nfft, int bin0, int m_local,
-                          void* H, long h_pitch, void* stream) {
-    return delay_impl<double>(m, amp, C, W, nfft, bin0, m_local, H, h_pitch, stream);
-}
-int fl_sos_response_c64(const void* b, const void* a, int S, int C, double gamma, const void* Wd, int nfft, int bin0,
-                        int m_local, void* H, long h_pitch, void* stream) {
-    return sos_impl<float>(b, a, S, C, gamma, Wd, nfft, bin0, m_local, H, h_pitch, stream);
-}
-int fl_sos_response_f32eval_c64(const void* b, const void* a, int S, int C, double gamma, const void* Wd, int nfft, int bin0,
-                                int m_local, void* H, long h_pitch, void* stream) {
-    return sos_impl<float>(b, a, S, C, gamma, Wd, nfft, bin0, m_local, H, h_pitch, stream, true);
-}
-int fl_geq_response_c64(const void* gain, int in_kind, int nb, const void* consts, void* b, void* a, int C, double gamma, const void* Wd,
-                        int nfft, int bin0, int m_local, void* H, long h_pitch, int float_eval, void* stream) {
-    FL_REQUIRE(gain && consts && b && a, "geq_response: null pointer");
-    FL_REQUIRE(in_kind >= 0 && in_kind <= 4 && nb >= 4, "geq_response: in_kind in [0, 4], at least four bands");
-    const GeqDesign gd{gain, in_kind, (const double*)consts, (double*)b, (double*)a};
-    if (m_local == 0) {
-        hipLaunchKernelGGL(geq_sections_kernel, dim3(cdiv_i(nb * C, 256)), dim3(256), 0, (hipStream_t)stream, gain, in_kind, nb, C,
-                           (const double*)consts, (double*)b, (double*)a);
-        FL_CHECK_LAUNCH("geq_sections");
-        return FL_OK;
+// all-double with the constant factor: one section chunk (the NIW gradient planes are read once)
+static int sos_bwd_rc_f64_launch(const SosBwd& A, SosRCd rcd, int rc_ni) {
+    FL_REQUIRE(A.H && rcd.Wr && rcd.partW && rcd.Nmid > 0, "sos_response_bwd: constant-factor mode needs the saved response");
+    rcd.nbx = sos_blocks(A.m_local, A.C, A.S, false);
+    const dim3 grid(cdiv_i((A.C / rcd.Nmid) * rcd.nbx, 8) * 8 * rcd.Nmid, 1, cdiv_i(A.S, 6));
+    if (!dispatch<2, 4, 8, 16>(rc_ni, [&](auto NIW) {
+            hipLaunchKernelGGL((sos_response_bwd_kernel<double, 6, decltype(NIW)::value>), grid, dim3(256), (size_t)6 * A.S * sizeof(double),
+                               (hipStream_t)A.stream, (const cx<double>*)A.gH, A.g_pitch, (const cx<double>*)A.H, A.h_pitch, (const double*)A.b,
+                               (const double*)A.a, A.S, A.C, A.gamma, (const cx<double>*)A.Wd, A.nfft, A.bin0, A.m_local, (double*)A.part, rcd);
+        })) {
+        set_error("sos_response_bwd: no kernel for %d input channels of the constant factor", rc_ni);
+        return FL_ERR_UNSUPPORTED;
     }
-    return sos_impl<float>(b, a, nb, C, gamma, Wd, nfft, bin0, m_local, H, h_pitch, stream, float_eval != 0, gd);
-}
-int fl_sos_response_c128(const void* b, const void* a, int S, int C, double gamma, const void* Wd, int nfft, int bin0,
-                        int m_local, void* H, long h_pitch, void* stream) {
-    return sos_impl<double>(b, a, S, C, gamma, Wd, nfft, bin0, m_local, H, h_pitch, stream);
-}
-int fl_sos_bwd_blocks(int m_local, int C, int S, int mixed) { return sos_blocks(m_local, C, S, mixed != 0); }
-// (test hooks: both return the previous setting; a negative argument only asks for it)
-int fl_debug_set_rc_fast(int on) {
-    const int prev = g_rc_fast;
-    if (on >= 0) g_rc_fast = on;
-    return prev;
-}
-int fl_debug_set_sos_chunk(int sections_per_thread) {
-    const int prev = g_sos_blocks * 100 + g_sos_chunk;
-    if (sections_per_thread < 0) return prev;
-    g_sos_blocks = sections_per_thread / 100;      // hundreds digit(s): blocks per channel (0 = default)
-    sections_per_thread %= 100;
-    g_sos_chunk = sections_per_thread;
-    return prev;
+    FL_CHECK_LAUNCH("sos_response_bwd_rc");
+    return FL_OK;
 }
 
-int fl_geq_sections(const void* gain, int in_kind, int nb, int C, const void* consts, void* b, void* a, void* stream) {
-    FL_REQUIRE(gain && consts && b && a, "geq_sections: null pointer");
-    FL_REQUIRE(in_kind >= 0 && in_kind <= 4, "geq_sections: in_kind must be 0 (dB, f64), 1 / 2 (|x|, f64 / f32) or 3 / 4 (sigmoid(x), f64 / f32)");
-    FL_REQUIRE(nb >= 4 && C > 0, "geq_sections: need >= 4 bands (gain, two shelves, one peak) and C > 0");
-    hipLaunchKernelGGL(geq_sections_kernel, dim3(cdiv_i((long)nb * C, 256)), dim3(256), 0, (hipStream_t)stream,
-                       gain, in_kind, nb, C, (const double*)consts, (double*)b, (double*)a);
-    FL_CHECK_LAUNCH("geq_sections");
+// plain, either type: the cascade evaluated in double (again, or from the saved response)
+template <typename T>
+static int sos_bwd_plain_launch(const SosBwd& A) {
+    dispatch<12, 6, 3, 4>(sos_chunk_of(A.S, false), [&](auto SC) {
+        const dim3 grid(sos_blocks(A.m_local, A.C, A.S, false), A.C, cdiv_i(A.S, decltype(SC)::value));
+        hipLaunchKernelGGL((sos_response_bwd_kernel<T, decltype(SC)::value>), grid, dim3(256), (size_t)6 * A.S * sizeof(double), (hipStream_t)A.stream,
+                           (const cx<T>*)A.gH, A.g_pitch, (const cx<T>*)A.H, A.h_pitch, (const double*)A.b, (const double*)A.a, A.S, A.C, A.gamma,
+                           (const cx<double>*)A.Wd, A.nfft, A.bin0, A.m_local, (double*)A.part, SosRCd{0, 0, nullptr, nullptr});
+    });
+    FL_CHECK_LAUNCH("sos_response_bwd");
     return FL_OK;
 }
-int fl_geq_sections_bwd(const void* gain, int in_kind, const void* gb, const void* ga, long blk_stride, int nblk, int nb,
-                        int C, const void* consts, void* ggain, void* stream) {
-    FL_REQUIRE(gain && gb && ga && consts && ggain, "geq_sections_bwd: null pointer");
-    FL_REQUIRE(in_kind >= 0 && in_kind <= 4, "geq_sections_bwd: bad in_kind");
-    FL_REQUIRE(nb >= 4 && C > 0 && nblk >= 1 && blk_stride >= 0, "geq_sections_bwd: bad sizes");
-    const int mb = cdiv_i((long)nb * C, 256);
-    hipLaunchKernelGGL(geq_sections_bwd_kernel, dim3(mb), dim3(256), 0, (hipStream_t)stream,
-                       gain, in_kind, (const double*)gb, (const double*)ga, blk_stride, nblk, nb, C,
-                       (const double*)consts, ggain, mb, (const void*)nullptr, 0, 0, (void*)nullptr, 0);
-    FL_CHECK_LAUNCH("geq_sections_bwd");
-    return FL_OK;
-}
+
 static int geq_bwd_w_impl(const void* gain, int in_kind, const void* gb, const void* ga, long blk_stride, int nblk, int nb,
                           int C, const void* consts, void* ggain, const void* partW, int wrows, int wn, void* gW, int w_f64, void* stream) {
     FL_REQUIRE(gain && gb && ga && consts && ggain && partW && gW, "geq_sections_bwd_w: null pointer");
@@ -1269,128 +1273,72 @@ static int geq_bwd_w_impl(const void* gain, int in_kind, const void* gb, const v
     FL_CHECK_LAUNCH("geq_sections_bwd_w");
     return FL_OK;
 }
-int fl_geq_sections_bwd_w(const void* gain, int in_kind, const void* gb, const void* ga, long blk_stride, int nblk, int nb,
-                          int C, const void* consts, void* ggain, const void* partW, int wrows, int wn, void* gW, void* stream) {
-    return geq_bwd_w_impl(gain, in_kind, gb, ga, blk_stride, nblk, nb, C, consts, ggain, partW, wrows, wn, gW, 0, stream);
-}
-int fl_geq_sections_bwd_w64(const void* gain, int in_kind, const void* gb, const void* ga, long blk_stride, int nblk, int nb,
-                            int C, const void* consts, void* ggain, const void* partW, int wrows, int wn, void* gW, void* stream) {
-    return geq_bwd_w_impl(gain, in_kind, gb, ga, blk_stride, nblk, nb, C, consts, ggain, partW, wrows, wn, gW, 1, stream);
-}
-int fl_sos_response_bwd_c64(const void* gH, long g_pitch, const void* H, long h_pitch, const void* b, const void* a, int S,
-                            int C, double gamma, const void* Wd, int nfft, int bin0, int m_local, void* part, void* stream) {
-    return sos_bwd_impl<float>(gH, g_pitch, H, h_pitch, b, a, S, C, gamma, Wd, nfft, bin0, m_local, part, stream);
-}
-}  // extern "C"
-template <typename T>
-static int rc_impl(const void* b, const void* a, int S, int No, int Nmid, int Ni, const void* Wr, double gamma,
-                   const void* Wd, int nfft, int bin0, int m_local, void* G, long g_pitch, void* H, long h_pitch,
-                   int float_eval, void* stream, GeqDesign gd) {
-    FL_REQUIRE(b && a && Wr && Wd && G && H, "sos_response_rc: null pointer");
-    FL_REQUIRE(g_pitch >= m_local && h_pitch >= m_local, "sos_response_rc: pitches must be >= m_local");
-    FL_REQUIRE(S > 0 && S <= 64 && No > 0 && No <= 65535 && Nmid > 0 && Nmid <= 32 && nfft > 0 && bin_range_ok(bin0, m_local, nfft) &&
-                   m_local >= 0, "sos_response_rc: bad sizes");
+
+}  // namespace fl
+
+using namespace fl;
+
+// ================================================================ the exported entries (C linkage), in the order of include/flamo_hip.h
+FL_ENTRY_C64_C128(fl_delay_response, (const int32_t* m, const void* amp, int C, const void* W, int nfft, int bin0, int m_local, void* H,
+                                      long h_pitch, void* stream),
+                  (m, amp, C, W, nfft, bin0, m_local, H, h_pitch, stream)) {
+    FL_REQUIRE(m && amp && W && H, "delay_response: null pointer");
+    FL_REQUIRE(h_pitch >= m_local, "delay_response: h_pitch must be >= m_local");
+    FL_REQUIRE(C > 0 && C <= 65535 && nfft > 0 && bin_range_ok(bin0, m_local, nfft) && m_local >= 0, "delay_response: bad sizes");
     if (m_local == 0) return FL_OK;
-    dim3 grid(cdiv_i(m_local, 256), No);
-    const size_t lds = (size_t)Nmid * 6 * S * sizeof(double) + (size_t)Nmid * Ni * sizeof(T);
-    FL_REQUIRE(lds <= 64 * 1024, "sos_response_rc: the coefficient tables of one output row exceed 64 KB of LDS");
-    const size_t lds_fast = ((size_t)Nmid * 12 * ((S + 1) & ~1) + (size_t)Nmid * Ni) * sizeof(float);
-    // the float kernel's threads take bin PAIRS: half the elements (+ the Nyquist element as a pair of its own in row-major order)
-    const int npairs = bin0 >= 0 ? cdiv_i(m_local, 2) : (((nfft / 2 / (-bin0)) + 1) / 2) * (-bin0) + 1;
-    const dim3 grid_fast(cdiv_i(npairs, 256), No);
-    if constexpr (sizeof(T) == 4) {
-        if (g_rc_fast && float_eval) {      // second generation (cascade2.hip); shapes it does not take fall through
-            const int rc2 = rc_ba_launch(b, a, S, No, Nmid, Ni, Wr, gamma, Wd, nfft, bin0, m_local, G, g_pitch, H, h_pitch, stream, gd);
-            if (rc2 != FL_ERR_UNSUPPORTED) return rc2;
-        }
-    }
-#define FL_RC_FWD(NIW_)                                                                                                      \
-    if constexpr (sizeof(T) == 4) if (Ni == NIW_ && g_rc_fast && float_eval) {                                                                             \
-        if (g_rc_fast == 2)                                                                                                  \
-            hipLaunchKernelGGL((sos_response_rc_fast_kernel<NIW_, 2>), grid_fast, dim3(256), lds_fast, (hipStream_t)stream,       \
-                               (const double*)b, (const double*)a, S, No * Nmid, Nmid, (const float*)Wr, gamma,              \
-                               (const cx<double>*)Wd, nfft, bin0, m_local, (cx<float>*)G, g_pitch, (cx<float>*)H, h_pitch, gd);  \
-        else if (g_rc_fast == 3)                                                                                             \
-            hipLaunchKernelGGL((sos_response_rc_fast_kernel<NIW_, 3>), grid_fast, dim3(256), lds_fast, (hipStream_t)stream,       \
-                               (const double*)b, (const double*)a, S, No * Nmid, Nmid, (const float*)Wr, gamma,              \
-                               (const cx<double>*)Wd, nfft, bin0, m_local, (cx<float>*)G, g_pitch, (cx<float>*)H, h_pitch, gd);  \
-        else if (g_rc_fast == 6)                                                                                             \
-            hipLaunchKernelGGL((sos_response_rc_fast_kernel<NIW_, 6>), grid_fast, dim3(256), lds_fast, (hipStream_t)stream,       \
-                               (const double*)b, (const double*)a, S, No * Nmid, Nmid, (const float*)Wr, gamma,              \
-                               (const cx<double>*)Wd, nfft, bin0, m_local, (cx<float>*)G, g_pitch, (cx<float>*)H, h_pitch, gd);  \
-        else                                                                                                                 \
-            hipLaunchKernelGGL((sos_response_rc_fast_kernel<NIW_>), grid_fast, dim3(256), lds_fast, (hipStream_t)stream,          \
-                               (const double*)b, (const double*)a, S, No * Nmid, Nmid, (const float*)Wr, gamma,              \
-                               (const cx<double>*)Wd, nfft, bin0, m_local, (cx<float>*)G, g_pitch, (cx<float>*)H, h_pitch, gd);  \
-        FL_CHECK_LAUNCH("sos_response_rc_fast");                                                                             \
-        return FL_OK;                                                                                                        \
-    }                                                                                                                        \
-    if (Ni == NIW_) {                                                                                                        \
-        if (gd.gain) {      /* the double kernel reads its sections: design them first */                                        \
-            hipLaunchKernelGGL(geq_sections_kernel, dim3(cdiv_i(S * No * Nmid, 256)), dim3(256), 0, (hipStream_t)stream, gd.gain, \
-                               gd.in_kind, S, No * Nmid, gd.k, gd.b_out, gd.a_out);                                              \
-            FL_CHECK_LAUNCH("geq_sections");                                                                                     \
-        }                                                                                                                        \
-        hipLaunchKernelGGL((sos_response_rc_kernel<NIW_, T>), grid, dim3(256), lds, (hipStream_t)stream, (const double*)b,   \
-                           (const double*)a, S, No * Nmid, Nmid, (const T*)Wr, gamma, (const cx<double>*)Wd, nfft, bin0,     \
-                           m_local, (cx<T>*)G, g_pitch, (cx<T>*)H, h_pitch);                                                 \
-        FL_CHECK_LAUNCH("sos_response_rc");                                                                                  \
-        return FL_OK;                                                                                                        \
-    }
-    FL_RC_FWD(2) FL_RC_FWD(4) FL_RC_FWD(8) FL_RC_FWD(16)
-#undef FL_RC_FWD
-    set_error("sos_response_rc: no kernel for %d input channels of the constant factor", Ni);
-    return FL_ERR_UNSUPPORTED;
+    dim3 grid(cdiv_i(m_local, 256), C);
+    hipLaunchKernelGGL((delay_response_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, m, (const T*)amp,
+                       (const cx<T>*)W, nfft, 1.0 / (double)nfft, bin0, m_local, (cx<T>*)H, h_pitch);
+    FL_CHECK_LAUNCH("delay_response");
+    return FL_OK;
 }
-extern "C" {
-int fl_sos_response_rc_c64(const void* b, const void* a, int S, int No, int Nmid, int Ni, const void* Wr, double gamma,
-                           const void* Wd, int nfft, int bin0, int m_local, void* G, long g_pitch, void* H, long h_pitch,
-                           int float_eval, void* stream) {
-    return rc_impl<float>(b, a, S, No, Nmid, Ni, Wr, gamma, Wd, nfft, bin0, m_local, G, g_pitch, H, h_pitch, float_eval, stream,
-                          GeqDesign{nullptr, 0, nullptr, nullptr, nullptr});
+FL_ENTRY_C64_C128(fl_sos_response, (const void* b, const void* a, int S, int C, double gamma, const void* Wd, int nfft, int bin0,
+                                    int m_local, void* H, long h_pitch, void* stream),
+                  (b, a, S, C, gamma, Wd, nfft, bin0, m_local, H, h_pitch, stream)) {
+    return sos_impl<T>(b, a, S, C, gamma, Wd, nfft, bin0, m_local, H, h_pitch, stream);
 }
-int fl_sos_response_rc_c128(const void* b, const void* a, int S, int No, int Nmid, int Ni, const void* Wr, double gamma,
-                            const void* Wd, int nfft, int bin0, int m_local, void* G, long g_pitch, void* H, long h_pitch,
-                            void* stream) {
-    return rc_impl<double>(b, a, S, No, Nmid, Ni, Wr, gamma, Wd, nfft, bin0, m_local, G, g_pitch, H, h_pitch, 0, stream,
-                           GeqDesign{nullptr, 0, nullptr, nullptr, nullptr});
+extern "C" int fl_sos_response_f32eval_c64(const void* b, const void* a, int S, int C, double gamma, const void* Wd, int nfft, int bin0,
+                                           int m_local, void* H, long h_pitch, void* stream) {
+    return sos_impl<float>(b, a, S, C, gamma, Wd, nfft, bin0, m_local, H, h_pitch, stream, true);
 }
-}  // extern "C"
-template <typename T>
-static int geq_rc_impl(const void* gain, int in_kind, int nb, const void* consts, void* b, void* a, int No, int Nmid, int Ni,
-                       const void* Wr, double gamma, const void* Wd, int nfft, int bin0, int m_local, void* G, long g_pitch,
-                       void* H, long h_pitch, int float_eval, void* stream) {
-    FL_REQUIRE(gain && consts, "geq_response_rc: null pointer");
-    FL_REQUIRE(in_kind >= 0 && in_kind <= 4 && nb >= 4, "geq_response_rc: in_kind in [0, 4], at least four bands");
-    if (m_local == 0) {      // nothing to evaluate: the sections are still an output
-        hipLaunchKernelGGL(geq_sections_kernel, dim3(cdiv_i(nb * No * Nmid, 256)), dim3(256), 0, (hipStream_t)stream, gain, in_kind, nb,
-                           No * Nmid, (const double*)consts, (double*)b, (double*)a);
-        FL_CHECK_LAUNCH("geq_sections");
-        return FL_OK;
-    }
-    return rc_impl<T>(b, a, nb, No, Nmid, Ni, Wr, gamma, Wd, nfft, bin0, m_local, G, g_pitch, H, h_pitch, float_eval, stream,
-                      GeqDesign{gain, in_kind, (const double*)consts, (double*)b, (double*)a});
+extern "C" int fl_geq_response_c64(const void* gain, int in_kind, int nb, const void* consts, void* b, void* a, int C, double gamma,
+                                   const void* Wd, int nfft, int bin0, int m_local, void* H, long h_pitch, int float_eval, void* stream) {
+    FL_REQUIRE(gain && consts && b && a, "geq_response: null pointer");
+    FL_REQUIRE(in_kind >= 0 && in_kind <= 4 && nb >= 4, "geq_response: in_kind in [0, 4], at least four bands");
+    const GeqDesign gd{gain, in_kind, (const double*)consts, (double*)b, (double*)a};
+    if (m_local == 0) return geq_sections_launch(gd, nb, C, stream);
+    return sos_impl<float>(b, a, nb, C, gamma, Wd, nfft, bin0, m_local, H, h_pitch, stream, float_eval != 0, gd);
 }
-extern "C" {
-int fl_geq_response_rc_c64(const void* gain, int in_kind, int nb, const void* consts, void* b, void* a, int No, int Nmid, int Ni,
-                           const void* Wr, double gamma, const void* Wd, int nfft, int bin0, int m_local, void* G, long g_pitch,
-                           void* H, long h_pitch, int float_eval, void* stream) {
-    return geq_rc_impl<float>(gain, in_kind, nb, consts, b, a, No, Nmid, Ni, Wr, gamma, Wd, nfft, bin0, m_local, G, g_pitch, H,
-                              h_pitch, float_eval, stream);
+extern "C" int fl_sos_bwd_blocks(int m_local, int C, int S, int mixed) { return sos_blocks(m_local, C, S, mixed != 0); }
+// (test hooks: both return the previous setting; a negative argument only asks for it)
+extern "C" int fl_debug_set_sos_chunk(int sections_per_thread) {
+    const int prev = g_sos_blocks * 100 + g_sos_chunk;
+    if (sections_per_thread < 0) return prev;
+    g_sos_blocks = sections_per_thread / 100;      // hundreds digit(s): blocks per channel (0 = default)
+    g_sos_chunk = sections_per_thread % 100;
+    return prev;
 }
-int fl_geq_response_rc_c128(const void* gain, int in_kind, int nb, const void* consts, void* b, void* a, int No, int Nmid, int Ni,
-                            const void* Wr, double gamma, const void* Wd, int nfft, int bin0, int m_local, void* G, long g_pitch,
-                            void* H, long h_pitch, void* stream) {
-    return geq_rc_impl<double>(gain, in_kind, nb, consts, b, a, No, Nmid, Ni, Wr, gamma, Wd, nfft, bin0, m_local, G, g_pitch, H,
-                               h_pitch, 0, stream);
+extern "C" int fl_debug_set_rc_fast(int on) {
+    const int prev = g_rc_fast;
+    if (on >= 0) g_rc_fast = on;
+    return prev;
 }
-int fl_sos_response_apply_max_ni(int S) {      // cascades per row whose coefficient tables fit the default 64 KB of dynamic LDS
+FL_ENTRY_C64_C128(fl_sos_response_bwd, (const void* gH, long g_pitch, const void* H, long h_pitch, const void* b, const void* a, int S,
+                                        int C, double gamma, const void* Wd, int nfft, int bin0, int m_local, void* part, void* stream),
+                  (gH, g_pitch, H, h_pitch, b, a, S, C, gamma, Wd, nfft, bin0, m_local, part, stream)) {
+    const SosBwd A{gH, g_pitch, H, h_pitch, b, a, S, C, gamma, Wd, nfft, bin0, m_local, part, stream};
+    if (const int rc = sos_bwd_check(A, gH)) return rc;
+    if constexpr (sizeof(T) == 4)
+        if (H) return sos_bwd_mixed_launch(A);
+    return sos_bwd_plain_launch<T>(A);
+}
+extern "C" int fl_sos_response_apply_max_ni(int S) {      // cascades per row whose coefficient tables fit the default 64 KB of dynamic LDS
     const int SP = (S + 1) & ~1;
     return (int)(65536 / (12 * SP * sizeof(float)));
 }
-int fl_sos_response_apply_c64(const void* b, const void* a, int S, int No, int Ni, const void* X, long xs_b, long xs_n, int BX,
-                              double gamma, const void* Wd, int nfft, int bin0, int m_local, void* G, long g_pitch, void* Y, long ys_b,
-                              long ys_m, void* stream) {
+extern "C" int fl_sos_response_apply_c64(const void* b, const void* a, int S, int No, int Ni, const void* X, long xs_b, long xs_n, int BX,
+                                         double gamma, const void* Wd, int nfft, int bin0, int m_local, void* G, long g_pitch, void* Y,
+                                         long ys_b, long ys_m, void* stream) {
     FL_REQUIRE(b && a && X && Wd && G && Y, "sos_response_apply: null pointer");
     FL_REQUIRE(g_pitch >= m_local, "sos_response_apply: g_pitch must be >= m_local");
     FL_REQUIRE(S > 0 && No > 0 && No <= 65535 && Ni > 0 && Ni <= fl_sos_response_apply_max_ni(S) && (BX == 1 || BX == 2) && nfft > 0 &&
@@ -1399,44 +1347,80 @@ int fl_sos_response_apply_c64(const void* b, const void* a, int S, int No, int N
     if (m_local == 0) return FL_OK;
     dim3 grid(cdiv_i(m_local, 256), No);
     const size_t lds = (size_t)Ni * 12 * ((S + 1) & ~1) * sizeof(float);
-    if (BX == 1)
-        hipLaunchKernelGGL((sos_response_apply_fast_kernel<1>), grid, dim3(256), lds, (hipStream_t)stream, (const double*)b,
+    dispatch<1, 2>(BX, [&](auto NB) {
+        hipLaunchKernelGGL((sos_response_apply_fast_kernel<decltype(NB)::value>), grid, dim3(256), lds, (hipStream_t)stream, (const double*)b,
                            (const double*)a, S, No * Ni, Ni, (const cx<float>*)X, xs_b, xs_n, gamma, (const cx<double>*)Wd, nfft, bin0,
                            m_local, (cx<float>*)G, g_pitch, (cx<float>*)Y, ys_b, ys_m);
-    else
-        hipLaunchKernelGGL((sos_response_apply_fast_kernel<2>), grid, dim3(256), lds, (hipStream_t)stream, (const double*)b,
-                           (const double*)a, S, No * Ni, Ni, (const cx<float>*)X, xs_b, xs_n, gamma, (const cx<double>*)Wd, nfft, bin0,
-                           m_local, (cx<float>*)G, g_pitch, (cx<float>*)Y, ys_b, ys_m);
+    });
     FL_CHECK_LAUNCH("sos_response_apply");
     return FL_OK;
 }
-int fl_sos_response_bwd_rc_c64(const void* gHfull, long g_pitch, const void* G, long h_pitch, const void* b, const void* a,
-                               int S, int No, int Nmid, int Ni, const void* Wr, double gamma, const void* Wd, int nfft,
-                               int bin0, int m_local, void* part, void* partW, void* stream) {
-    FL_REQUIRE(G && Wr && partW && No > 0 && Nmid > 0 && Ni > 0, "sos_response_bwd_rc: bad arguments");
-    SosRC rc{Nmid, 0, (const float*)Wr, (float*)partW};
-    return sos_bwd_impl<float>(gHfull, g_pitch, G, h_pitch, b, a, S, No * Nmid, gamma, Wd, nfft, bin0, m_local, part, stream,
-                               Ni, rc);
-}
-int fl_sos_response_bwd_rc_c128(const void* gHfull, long g_pitch, const void* G, long h_pitch, const void* b, const void* a,
-                                int S, int No, int Nmid, int Ni, const void* Wr, double gamma, const void* Wd, int nfft,
-                                int bin0, int m_local, void* part, void* partW, void* stream) {
-    FL_REQUIRE(G && Wr && partW && No > 0 && Nmid > 0 && Ni > 0, "sos_response_bwd_rc: bad arguments");
-    SosRCd rcd{Nmid, 0, (const double*)Wr, (double*)partW};
-    return sos_bwd_impl<double>(gHfull, g_pitch, G, h_pitch, b, a, S, No * Nmid, gamma, Wd, nfft, bin0, m_local, part, stream,
-                                Ni, SosRC{0, 0, nullptr, nullptr}, rcd);
-}
-int fl_sos_response_bwd_outer_c64(const void* gY, long gy_sb, long gy_sn, const void* X, long x_sb, long x_sn, int B, int No, int Ni,
-                                  const void* H, long h_pitch, const void* b, const void* a, int S, double gamma, const void* Wd,
-                                  int nfft, int bin0, int m_local, void* part, void* stream) {
+extern "C" int fl_sos_response_bwd_outer_c64(const void* gY, long gy_sb, long gy_sn, const void* X, long x_sb, long x_sn, int B, int No, int Ni,
+                                             const void* H, long h_pitch, const void* b, const void* a, int S, double gamma, const void* Wd,
+                                             int nfft, int bin0, int m_local, void* part, void* stream) {
     FL_REQUIRE(gY && X && H && B > 0 && No > 0 && Ni > 0, "sos_response_bwd_outer: bad arguments");
-    SosRC rc{0, 0, nullptr, nullptr};
+    SosRC rc{};
     rc.oG = (const cx<float>*)gY; rc.oX = (const cx<float>*)X;
     rc.o_gb = gy_sb; rc.o_gn = gy_sn; rc.o_xb = x_sb; rc.o_xn = x_sn; rc.oB = B; rc.oNi = Ni;
-    return sos_bwd_impl<float>(nullptr, m_local, H, h_pitch, b, a, S, No * Ni, gamma, Wd, nfft, bin0, m_local, part, stream, 0, rc);
+    const SosBwd A{nullptr, m_local, H, h_pitch, b, a, S, No * Ni, gamma, Wd, nfft, bin0, m_local, part, stream};
+    if (const int r = sos_bwd_check(A, gY)) return r;
+    return sos_bwd_mixed_launch(A, rc);
 }
-int fl_sos_response_bwd_c128(const void* gH, long g_pitch, const void* H, long h_pitch, const void* b, const void* a, int S,
-                             int C, double gamma, const void* Wd, int nfft, int bin0, int m_local, void* part, void* stream) {
-    return sos_bwd_impl<double>(gH, g_pitch, H, h_pitch, b, a, S, C, gamma, Wd, nfft, bin0, m_local, part, stream);
+extern "C" int fl_sos_response_rc_c64(const void* b, const void* a, int S, int No, int Nmid, int Ni, const void* Wr, double gamma,
+                                      const void* Wd, int nfft, int bin0, int m_local, void* G, long g_pitch, void* H, long h_pitch,
+                                      int float_eval, void* stream) {
+    return rc_impl<float>(b, a, S, No, Nmid, Ni, Wr, gamma, Wd, nfft, bin0, m_local, G, g_pitch, H, h_pitch, float_eval, stream, GeqDesign{});
 }
+extern "C" int fl_geq_response_rc_c64(const void* gain, int in_kind, int nb, const void* consts, void* b, void* a, int No, int Nmid, int Ni,
+                                      const void* Wr, double gamma, const void* Wd, int nfft, int bin0, int m_local, void* G, long g_pitch,
+                                      void* H, long h_pitch, int float_eval, void* stream) {
+    return geq_rc_impl<float>(gain, in_kind, nb, consts, b, a, No, Nmid, Ni, Wr, gamma, Wd, nfft, bin0, m_local, G, g_pitch, H,
+                              h_pitch, float_eval, stream);
+}
+FL_ENTRY_C64_C128(fl_sos_response_bwd_rc, (const void* gHfull, long g_pitch, const void* G, long h_pitch, const void* b, const void* a,
+                                           int S, int No, int Nmid, int Ni, const void* Wr, double gamma, const void* Wd, int nfft,
+                                           int bin0, int m_local, void* part, void* partW, void* stream),
+                  (gHfull, g_pitch, G, h_pitch, b, a, S, No, Nmid, Ni, Wr, gamma, Wd, nfft, bin0, m_local, part, partW, stream)) {
+    FL_REQUIRE(G && Wr && partW && No > 0 && Nmid > 0 && Ni > 0, "sos_response_bwd_rc: bad arguments");
+    const SosBwd A{gHfull, g_pitch, G, h_pitch, b, a, S, No * Nmid, gamma, Wd, nfft, bin0, m_local, part, stream};
+    if (const int rc = sos_bwd_check(A, gHfull)) return rc;
+    if constexpr (sizeof(T) == 4) return sos_bwd_mixed_launch(A, SosRC{Nmid, 0, (const float*)Wr, (float*)partW}, Ni);
+    else return sos_bwd_rc_f64_launch(A, SosRCd{Nmid, 0, (const double*)Wr, (double*)partW}, Ni);
+}
+extern "C" int fl_sos_response_rc_c128(const void* b, const void* a, int S, int No, int Nmid, int Ni, const void* Wr, double gamma,
+                                       const void* Wd, int nfft, int bin0, int m_local, void* G, long g_pitch, void* H, long h_pitch,
+                                       void* stream) {
+    return rc_impl<double>(b, a, S, No, Nmid, Ni, Wr, gamma, Wd, nfft, bin0, m_local, G, g_pitch, H, h_pitch, 0, stream, GeqDesign{});
+}
+extern "C" int fl_geq_response_rc_c128(const void* gain, int in_kind, int nb, const void* consts, void* b, void* a, int No, int Nmid, int Ni,
+                                       const void* Wr, double gamma, const void* Wd, int nfft, int bin0, int m_local, void* G, long g_pitch,
+                                       void* H, long h_pitch, void* stream) {
+    return geq_rc_impl<double>(gain, in_kind, nb, consts, b, a, No, Nmid, Ni, Wr, gamma, Wd, nfft, bin0, m_local, G, g_pitch, H,
+                               h_pitch, 0, stream);
+}
+extern "C" int fl_geq_sections(const void* gain, int in_kind, int nb, int C, const void* consts, void* b, void* a, void* stream) {
+    FL_REQUIRE(gain && consts && b && a, "geq_sections: null pointer");
+    FL_REQUIRE(in_kind >= 0 && in_kind <= 4, "geq_sections: in_kind must be 0 (dB, f64), 1 / 2 (|x|, f64 / f32) or 3 / 4 (sigmoid(x), f64 / f32)");
+    FL_REQUIRE(nb >= 4 && C > 0, "geq_sections: need >= 4 bands (gain, two shelves, one peak) and C > 0");
+    return geq_sections_launch(GeqDesign{gain, in_kind, (const double*)consts, (double*)b, (double*)a}, nb, C, stream);
+}
+extern "C" int fl_geq_sections_bwd(const void* gain, int in_kind, const void* gb, const void* ga, long blk_stride, int nblk, int nb,
+                                   int C, const void* consts, void* ggain, void* stream) {
+    FL_REQUIRE(gain && gb && ga && consts && ggain, "geq_sections_bwd: null pointer");
+    FL_REQUIRE(in_kind >= 0 && in_kind <= 4, "geq_sections_bwd: bad in_kind");
+    FL_REQUIRE(nb >= 4 && C > 0 && nblk >= 1 && blk_stride >= 0, "geq_sections_bwd: bad sizes");
+    const int mb = cdiv_i((long)nb * C, 256);
+    hipLaunchKernelGGL(geq_sections_bwd_kernel, dim3(mb), dim3(256), 0, (hipStream_t)stream,
+                       gain, in_kind, (const double*)gb, (const double*)ga, blk_stride, nblk, nb, C,
+                       (const double*)consts, ggain, mb, (const void*)nullptr, 0, 0, (void*)nullptr, 0);
+    FL_CHECK_LAUNCH("geq_sections_bwd");
+    return FL_OK;
+}
+extern "C" int fl_geq_sections_bwd_w(const void* gain, int in_kind, const void* gb, const void* ga, long blk_stride, int nblk, int nb,
+                                     int C, const void* consts, void* ggain, const void* partW, int wrows, int wn, void* gW, void* stream) {
+    return geq_bwd_w_impl(gain, in_kind, gb, ga, blk_stride, nblk, nb, C, consts, ggain, partW, wrows, wn, gW, 0, stream);
+}
+extern "C" int fl_geq_sections_bwd_w64(const void* gain, int in_kind, const void* gb, const void* ga, long blk_stride, int nblk, int nb,
+                                       int C, const void* consts, void* ggain, const void* partW, int wrows, int wn, void* gW, void* stream) {
+    return geq_bwd_w_impl(gain, in_kind, gb, ga, blk_stride, nblk, nb, C, consts, ggain, partW, wrows, wn, gW, 1, stream);
 }

@@ -21,6 +21,11 @@ static inline bool bin_range_ok(int bin0, int m_local, int nfft) {
     if (bin0 >= 0) return true;
     return nfft % 2 == 0 && (nfft / 2) % (-bin0) == 0 && m_local == nfft / 2 + 1;
 }
+// the float cascade-times-matrix kernels' threads take bin PAIRS: half the elements (+ the Nyquist element as a pair of its own in
+// row-major order)
+static inline int rc_npairs(int nfft, int bin0, int m_local) {
+    return bin0 >= 0 ? cdiv_i(m_local, 2) : (((nfft / 2 / (-bin0)) + 1) / 2) * (-bin0) + 1;
+}
 
 
 // The section polynomials are evaluated in DOUBLE precision whatever the storage type T: at low

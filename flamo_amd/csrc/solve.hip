@@ -1163,9 +1163,7 @@ static int solve_lds_max_n() {
 constexpr int kSolveWsMaxN = 1024;
 template <typename T>
 static int solve_ws_slots(int N, int M) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    long slots = 2L * cus;
+    long slots = 2L * device_cus();
     const long cap = (1L << 30) / ((long)N * (N + 1) * (long)sizeof(cx<T>));
     if (slots > cap) slots = cap;
     if (slots > M) slots = M;
@@ -1663,16 +1661,7 @@ static void pin_kernel_order() {
     (void)&solve_scaled_keep_impl<float>, (void)&solve_scaled_keep_impl<double>, (void)&dud_grads_impl<float>;
 }
 
-// ---------------------------------------------------------------- the entries that exist in both precisions
-// FL_SOLVE_ENTRY(name, (parameters), (arguments)) { body } writes such an entry ONCE: the body becomes
-// template <class T> static int name_entry(parameters), and the exported symbols name_c64 / name_c128 (declared in
-// include/flamo_hip.h: a parameter list that differs from the declaration does not compile) are one-line forwards to
-// name_entry<float> / name_entry<double>.
-#define FL_SOLVE_ENTRY(NAME, PARAMS, ARGS)                                                \
-    template <class T> static int NAME##_entry PARAMS;                                    \
-    extern "C" int NAME##_c64 PARAMS { return NAME##_entry<float> ARGS; }                 \
-    extern "C" int NAME##_c128 PARAMS { return NAME##_entry<double> ARGS; }               \
-    template <class T> static int NAME##_entry PARAMS
+// ---------------------------------------------------------------- the entries that exist in both precisions (FL_ENTRY_C64_C128, common.h)
 
 // The factored loop A_f = I - diag(l (.) l2) U diag(r) as the kernels take it; every member this does not name stays zero.
 // l2: the second left factor of the fl_solve_dud2_* / fl_solve_fdn_* entries (nullptr: none); rhs_l2: the right-hand side is
@@ -1699,86 +1688,86 @@ static DudSide<T> dud_side(const void* sx, long sx_b, const void* sy, long sy_b,
     return DudSide<T>{(const cx<T>*)sx, (const cx<T>*)sy, sx_b, sy_b, sx ? 1 : 0, (T*)g_side_real};
 }
 
-FL_SOLVE_ENTRY(fl_solve_ws, (const void* P, long p_pitch, int one_minus, int adjoint, const void* R, long rs_b, long rs_n, long rs_k,
-                             void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, int K, void* ws, long ws_bytes, void* stream),
-               (P, p_pitch, one_minus, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, ws, ws_bytes, stream)) {
+FL_ENTRY_C64_C128(fl_solve_ws, (const void* P, long p_pitch, int one_minus, int adjoint, const void* R, long rs_b, long rs_n, long rs_k,
+                                void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, int K, void* ws, long ws_bytes, void* stream),
+                  (P, p_pitch, one_minus, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, ws, ws_bytes, stream)) {
     return solve_impl<T>(P, p_pitch, Dud<T>{}, one_minus, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream, ws,
                          ws_bytes > 0 ? (size_t)ws_bytes : 0);
 }
-FL_SOLVE_ENTRY(fl_solve, (const void* P, long p_pitch, int one_minus, int adjoint, const void* R, long rs_b, long rs_n, long rs_k, void* OUT,
-                          long os_b, long os_n, long os_k, int B, int M, int N, int K, void* stream),
-               (P, p_pitch, one_minus, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream)) {
+FL_ENTRY_C64_C128(fl_solve, (const void* P, long p_pitch, int one_minus, int adjoint, const void* R, long rs_b, long rs_n, long rs_k, void* OUT,
+                             long os_b, long os_n, long os_k, int B, int M, int N, int K, void* stream),
+                  (P, p_pitch, one_minus, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream)) {
     return solve_impl<T>(P, p_pitch, Dud<T>{}, one_minus, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream);
 }
-FL_SOLVE_ENTRY(fl_solve_scaled, (const void* P, long p_pitch, const void* l, long l_sn, int adjoint, const void* R, long rs_b, long rs_n,
-                                 long rs_k, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, int K, void* stream),
-               (P, p_pitch, l, l_sn, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream)) {
+FL_ENTRY_C64_C128(fl_solve_scaled, (const void* P, long p_pitch, const void* l, long l_sn, int adjoint, const void* R, long rs_b, long rs_n,
+                                    long rs_k, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, int K, void* stream),
+                  (P, p_pitch, l, l_sn, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream)) {
     FL_REQUIRE(P && l, "solve_scaled: null pointer");
     return solve_impl<T>(P, p_pitch, dud_of<T>(l, l_sn, 0, nullptr, nullptr, 0, 0), 1, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k,
                          B, M, N, K, stream);
 }
-FL_SOLVE_ENTRY(fl_solve_scaled_keep, (const void* P, long p_pitch, const void* l, long l_sn, const void* R, long rs_b, long rs_n, long rs_k,
-                                      void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, int K, void* LU, void* piv,
-                                      void* stream),
-               (P, p_pitch, l, l_sn, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, LU, piv, stream)) {
+FL_ENTRY_C64_C128(fl_solve_scaled_keep, (const void* P, long p_pitch, const void* l, long l_sn, const void* R, long rs_b, long rs_n, long rs_k,
+                                         void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, int K, void* LU, void* piv,
+                                         void* stream),
+                  (P, p_pitch, l, l_sn, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, LU, piv, stream)) {
     return solve_scaled_keep_impl<T>(P, p_pitch, l, l_sn, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, LU, piv, stream);
 }
-FL_SOLVE_ENTRY(fl_solve_kept_adjoint, (const void* LU, const void* piv, const void* R, long rs_b, long rs_n, long rs_k, void* OUT, long os_b,
-                                       long os_n, long os_k, int B, int M, int N, int K, void* stream),
-               (LU, piv, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream)) {
+FL_ENTRY_C64_C128(fl_solve_kept_adjoint, (const void* LU, const void* piv, const void* R, long rs_b, long rs_n, long rs_k, void* OUT, long os_b,
+                                          long os_n, long os_k, int B, int M, int N, int K, void* stream),
+                  (LU, piv, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream)) {
     return solve_kept_adjoint_impl<T>(LU, piv, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream);
 }
 // A^-H (conj(rv) . rs) from factors kept by fl_solve_fdn_keep_* (tile_bins = fl_solve_fdn_keep_tile)
-FL_SOLVE_ENTRY(fl_solve_kept_adjoint_rank1, (const void* LU, const void* piv, int tile_bins, const void* rv, int rv_real, const void* rs,
-                                             long rs_sb, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, void* stream),
-               (LU, piv, tile_bins, rv, rv_real, rs, rs_sb, OUT, os_b, os_n, os_k, B, M, N, stream)) {
+FL_ENTRY_C64_C128(fl_solve_kept_adjoint_rank1, (const void* LU, const void* piv, int tile_bins, const void* rv, int rv_real, const void* rs,
+                                                long rs_sb, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, void* stream),
+                  (LU, piv, tile_bins, rv, rv_real, rs, rs_sb, OUT, os_b, os_n, os_k, B, M, N, stream)) {
     FL_REQUIRE(rv && rs && tile_bins > 0, "solve_kept_adjoint_rank1: null pointer / tile");
     return solve_kept_adjoint_impl<T>(LU, piv, nullptr, 0, 0, 0, OUT, os_b, os_n, os_k, B, M, N, 1, stream, tile_bins, rv, rv_real, rs, rs_sb);
 }
-FL_SOLVE_ENTRY(fl_solve_dud, (const void* l, long l_sn, long l_sf, const void* U, const void* r, long r_sn, long r_sf, int adjoint,
-                              const void* R, long rs_b, long rs_n, long rs_k, void* OUT, long os_b, long os_n, long os_k, int B, int M,
-                              int N, int K, void* stream),
-               (l, l_sn, l_sf, U, r, r_sn, r_sf, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream)) {
+FL_ENTRY_C64_C128(fl_solve_dud, (const void* l, long l_sn, long l_sf, const void* U, const void* r, long r_sn, long r_sf, int adjoint,
+                                 const void* R, long rs_b, long rs_n, long rs_k, void* OUT, long os_b, long os_n, long os_k, int B, int M,
+                                 int N, int K, void* stream),
+                  (l, l_sn, l_sf, U, r, r_sn, r_sf, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream)) {
     FL_REQUIRE(U, "solve_dud: null mixing matrix");
     return solve_impl<T>(nullptr, 0, dud_of<T>(l, l_sn, l_sf, U, r, r_sn, r_sf), 1, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B,
                          M, N, K, stream);
 }
-FL_SOLVE_ENTRY(fl_solve_dud_grads, (const void* l, long l_sn, long l_sf, const void* U, const void* r, long r_sn, long r_sf, const void* gR,
-                                    const void* OUT, long s_b, long s_n, long s_k, int B, int M, int N, int K, void* gl, long gl_sn,
-                                    void* gr, long gr_sn, void* partU, void* gU, void* stream),
-               (l, l_sn, l_sf, U, r, r_sn, r_sf, gR, OUT, s_b, s_n, s_k, B, M, N, K, gl, gl_sn, gr, gr_sn, partU, gU, stream)) {
+FL_ENTRY_C64_C128(fl_solve_dud_grads, (const void* l, long l_sn, long l_sf, const void* U, const void* r, long r_sn, long r_sf, const void* gR,
+                                       const void* OUT, long s_b, long s_n, long s_k, int B, int M, int N, int K, void* gl, long gl_sn,
+                                       void* gr, long gr_sn, void* partU, void* gU, void* stream),
+                  (l, l_sn, l_sf, U, r, r_sn, r_sf, gR, OUT, s_b, s_n, s_k, B, M, N, K, gl, gl_sn, gr, gr_sn, partU, gU, stream)) {
     return dud_grads_impl<T>(dud_of<T>(l, l_sn, l_sf, U, r, r_sn, r_sf), gR, OUT, s_b, s_n, s_k, B, M, N, K, gl, gl_sn, gr, gr_sn, partU,
                              gU, stream);
 }
 /* two left factors: A_f = I - diag(l (.) l2) U diag(r); rhs_l2: the right-hand side is l2 (.) R (forward system) */
-FL_SOLVE_ENTRY(fl_solve_dud2, (const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, int rhs_l2, const void* U,
-                               const void* r, long r_sn, long r_sf, int adjoint, const void* R, long rs_b, long rs_n, long rs_k,
-                               void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, int K, void* stream),
-               (l, l_sn, l_sf, l2, l2_sn, l2_sf, rhs_l2, U, r, r_sn, r_sf, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K,
-                stream)) {
+FL_ENTRY_C64_C128(fl_solve_dud2, (const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, int rhs_l2, const void* U,
+                                  const void* r, long r_sn, long r_sf, int adjoint, const void* R, long rs_b, long rs_n, long rs_k,
+                                  void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, int K, void* stream),
+                  (l, l_sn, l_sf, l2, l2_sn, l2_sf, rhs_l2, U, r, r_sn, r_sf, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K,
+                   stream)) {
     FL_REQUIRE(U && l2, "solve_dud2: null pointer");
     return solve_impl<T>(nullptr, 0, dud_of<T>(l, l_sn, l_sf, U, r, r_sn, r_sf, l2, l2_sn, l2_sf, rhs_l2), 1, adjoint, R, rs_b, rs_n, rs_k,
                          OUT, os_b, os_n, os_k, B, M, N, K, stream);
 }
-FL_SOLVE_ENTRY(fl_solve_dud2_grads, (const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U,
-                                     const void* r, long r_sn, long r_sf, const void* gR, const void* OUT, long s_b, long s_n, long s_k,
-                                     int B, int M, int N, int K, void* gl, long gl_sn, void* gr, long gr_sn, void* partU, void* gU,
-                                     void* gR0, const void* sx, long sx_b, const void* sy, long sy_b, void* g_side_real, void* stream),
-               (l, l_sn, l_sf, l2, l2_sn, l2_sf, U, r, r_sn, r_sf, gR, OUT, s_b, s_n, s_k, B, M, N, K, gl, gl_sn, gr, gr_sn, partU, gU, gR0,
-                sx, sx_b, sy, sy_b, g_side_real, stream)) {
+FL_ENTRY_C64_C128(fl_solve_dud2_grads, (const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U,
+                                        const void* r, long r_sn, long r_sf, const void* gR, const void* OUT, long s_b, long s_n, long s_k,
+                                        int B, int M, int N, int K, void* gl, long gl_sn, void* gr, long gr_sn, void* partU, void* gU,
+                                        void* gR0, const void* sx, long sx_b, const void* sy, long sy_b, void* g_side_real, void* stream),
+                  (l, l_sn, l_sf, l2, l2_sn, l2_sf, U, r, r_sn, r_sf, gR, OUT, s_b, s_n, s_k, B, M, N, K, gl, gl_sn, gr, gr_sn, partU, gU, gR0,
+                   sx, sx_b, sy, sy_b, g_side_real, stream)) {
     FL_REQUIRE(l2, "solve_dud2_grads: null pointer");
     FL_REQUIRE((sx == nullptr) == (sy == nullptr) && (!sx || (K == 1 && partU && gU)), "solve_dud2_grads: side reductions need sx, sy, one column per batch item and the partial buffers");
     return dud_grads_impl<T>(dud_of<T>(l, l_sn, l_sf, U, r, r_sn, r_sf, l2, l2_sn, l2_sf, 0), gR, OUT, s_b, s_n, s_k, B, M, N, K, gl, gl_sn,
                              gr, gr_sn, partU, gU, stream, gR0, dud_side<T>(sx, sx_b, sy, sy_b, g_side_real));
 }
 // the same with the adjoint solution given as gR[b][n][f] = W[n][f] gy[b][f] (W from fl_solve_fdn_wadj_c64), formed in the kernel
-FL_SOLVE_ENTRY(fl_solve_dud2_grads_w, (const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U,
-                                       const void* r, long r_sn, long r_sf, const void* W, long w_sn, const void* gy, long gy_sb,
-                                       const void* OUT, long s_b, long s_n, long s_k, int B, int M, int N, void* gl, long gl_sn, void* gr,
-                                       long gr_sn, void* partU, void* gU, void* gR0, const void* sx, long sx_b, const void* sy, long sy_b,
-                                       void* g_side_real, void* stream),
-               (l, l_sn, l_sf, l2, l2_sn, l2_sf, U, r, r_sn, r_sf, W, w_sn, gy, gy_sb, OUT, s_b, s_n, s_k, B, M, N, gl, gl_sn, gr, gr_sn,
-                partU, gU, gR0, sx, sx_b, sy, sy_b, g_side_real, stream)) {
+FL_ENTRY_C64_C128(fl_solve_dud2_grads_w, (const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U,
+                                          const void* r, long r_sn, long r_sf, const void* W, long w_sn, const void* gy, long gy_sb,
+                                          const void* OUT, long s_b, long s_n, long s_k, int B, int M, int N, void* gl, long gl_sn, void* gr,
+                                          long gr_sn, void* partU, void* gU, void* gR0, const void* sx, long sx_b, const void* sy, long sy_b,
+                                          void* g_side_real, void* stream),
+                  (l, l_sn, l_sf, l2, l2_sn, l2_sf, U, r, r_sn, r_sf, W, w_sn, gy, gy_sb, OUT, s_b, s_n, s_k, B, M, N, gl, gl_sn, gr, gr_sn,
+                   partU, gU, gR0, sx, sx_b, sy, sy_b, g_side_real, stream)) {
     FL_REQUIRE(l2 && W && gy, "solve_dud2_grads_w: null pointer");
     FL_REQUIRE((sx == nullptr) == (sy == nullptr) && (!sx || (partU && gU)), "solve_dud2_grads_w: side reductions need sx, sy and the partial buffers");
     Dud<T> d = dud_of<T>(l, l_sn, l_sf, U, r, r_sn, r_sf, l2, l2_sn, l2_sf, 0);
@@ -1788,23 +1777,23 @@ FL_SOLVE_ENTRY(fl_solve_dud2_grads_w, (const void* l, long l_sn, long l_sf, cons
 }
 /* fl_solve_dud2 with the right-hand side built in the kernel, R_i = rv_i rs (rv conjugated for the adjoint system; scaled by
  * l2 for the forward one), and -- forward system, cz non-NULL -- the contracted output z = sum_i cw_i OUT_i beside OUT */
-FL_SOLVE_ENTRY(fl_solve_fdn, (const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U, const void* r,
-                              long r_sn, long r_sf, int adjoint, const void* rv, int rv_real, const void* rs, long rs_sb, const void* cw,
-                              int cw_real, void* cz, long cz_sb, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N,
-                              void* stream),
-               (l, l_sn, l_sf, l2, l2_sn, l2_sf, U, r, r_sn, r_sf, adjoint, rv, rv_real, rs, rs_sb, cw, cw_real, cz, cz_sb, OUT, os_b, os_n,
-                os_k, B, M, N, stream)) {
+FL_ENTRY_C64_C128(fl_solve_fdn, (const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U, const void* r,
+                                 long r_sn, long r_sf, int adjoint, const void* rv, int rv_real, const void* rs, long rs_sb, const void* cw,
+                                 int cw_real, void* cz, long cz_sb, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N,
+                                 void* stream),
+                  (l, l_sn, l_sf, l2, l2_sn, l2_sf, U, r, r_sn, r_sf, adjoint, rv, rv_real, rs, rs_sb, cw, cw_real, cz, cz_sb, OUT, os_b, os_n,
+                   os_k, B, M, N, stream)) {
     FL_REQUIRE(U && l2 && rv && rs && (!cz || cw), "solve_fdn: null pointer");
     Dud<T> d = dud_fdn<T>(l, l_sn, l_sf, l2, l2_sn, l2_sf, U, r, r_sn, r_sf, adjoint ? 0 : 1, rv, rv_real, rs, rs_sb, cw, cw_real, cz, cz_sb);
     return solve_impl<T>(nullptr, 0, d, 1, adjoint, nullptr, 0, 0, 0, OUT, os_b, os_n, os_k, B, M, N, 1, stream);
 }
 // the FDN form, forward system, with w = A^-H cw^H beside OUT and cz (fl_solve_fdn_wadj_supported)
-FL_SOLVE_ENTRY(fl_solve_fdn_wadj, (const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U, const void* r,
-                                   long r_sn, long r_sf, const void* rv, int rv_real, const void* rs, long rs_sb, const void* cw,
-                                   int cw_real, void* cz, long cz_sb, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N,
-                                   void* wadj, long wadj_sn, void* stream),
-               (l, l_sn, l_sf, l2, l2_sn, l2_sf, U, r, r_sn, r_sf, rv, rv_real, rs, rs_sb, cw, cw_real, cz, cz_sb, OUT, os_b, os_n, os_k, B,
-                M, N, wadj, wadj_sn, stream)) {
+FL_ENTRY_C64_C128(fl_solve_fdn_wadj, (const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U, const void* r,
+                                      long r_sn, long r_sf, const void* rv, int rv_real, const void* rs, long rs_sb, const void* cw,
+                                      int cw_real, void* cz, long cz_sb, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N,
+                                      void* wadj, long wadj_sn, void* stream),
+                  (l, l_sn, l_sf, l2, l2_sn, l2_sf, U, r, r_sn, r_sf, rv, rv_real, rs, rs_sb, cw, cw_real, cz, cz_sb, OUT, os_b, os_n, os_k, B,
+                   M, N, wadj, wadj_sn, stream)) {
     FL_REQUIRE(U && l2 && rv && rs && cw && wadj, "solve_fdn_wadj: null pointer");
     FL_REQUIRE(fl_solve_fdn_wadj_supported(N), "solve_fdn_wadj: 4 < N <= 16 on the default kernels (fl_solve_fdn_wadj_supported)");
     Dud<T> d = dud_fdn<T>(l, l_sn, l_sf, l2, l2_sn, l2_sf, U, r, r_sn, r_sf, 1, rv, rv_real, rs, rs_sb, cw, cw_real, cz, cz_sb);
@@ -1812,16 +1801,15 @@ FL_SOLVE_ENTRY(fl_solve_fdn_wadj, (const void* l, long l_sn, long l_sf, const vo
     return solve_impl<T>(nullptr, 0, d, 1, 0, nullptr, 0, 0, 0, OUT, os_b, os_n, os_k, B, M, N, 1, stream);
 }
 // the FDN form, forward system, with kept factors (fl_solve_fdn_keep_tile)
-FL_SOLVE_ENTRY(fl_solve_fdn_keep, (const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U, const void* r,
-                                   long r_sn, long r_sf, const void* rv, int rv_real, const void* rs, long rs_sb, const void* cw,
-                                   int cw_real, void* cz, long cz_sb, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N,
-                                   void* LU, void* piv, void* stream),
-               (l, l_sn, l_sf, l2, l2_sn, l2_sf, U, r, r_sn, r_sf, rv, rv_real, rs, rs_sb, cw, cw_real, cz, cz_sb, OUT, os_b, os_n, os_k, B,
-                M, N, LU, piv, stream)) {
+FL_ENTRY_C64_C128(fl_solve_fdn_keep, (const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U, const void* r,
+                                      long r_sn, long r_sf, const void* rv, int rv_real, const void* rs, long rs_sb, const void* cw,
+                                      int cw_real, void* cz, long cz_sb, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N,
+                                      void* LU, void* piv, void* stream),
+                  (l, l_sn, l_sf, l2, l2_sn, l2_sf, U, r, r_sn, r_sf, rv, rv_real, rs, rs_sb, cw, cw_real, cz, cz_sb, OUT, os_b, os_n, os_k, B,
+                   M, N, LU, piv, stream)) {
     FL_REQUIRE(U && l2 && rv && rs && (!cz || cw) && LU && piv, "solve_fdn_keep: null pointer");
     FL_REQUIRE(fl_solve_fdn_keep_tile(N, sizeof(T) == 8) > 0, "solve_fdn_keep: 8 < N <= 16 on the default kernels (fl_solve_fdn_keep_tile)");
     Dud<T> d = dud_fdn<T>(l, l_sn, l_sf, l2, l2_sn, l2_sf, U, r, r_sn, r_sf, 1, rv, rv_real, rs, rs_sb, cw, cw_real, cz, cz_sb);
     d.lu_out = (cx<T>*)LU; d.piv_out = (int*)piv;
     return solve_impl<T>(nullptr, 0, d, 1, 0, nullptr, 0, 0, 0, OUT, os_b, os_n, os_k, B, M, N, 1, stream);
 }
-#undef FL_SOLVE_ENTRY

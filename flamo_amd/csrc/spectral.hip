@@ -1329,13 +1329,7 @@ int fl_spec_supports(int nfft, int n_in, int n_out) {
     if (n_in != n_out && (spec_plan_lean(nfft) || sizeof(real_t) == 8)) return 0;
     // the row kernel holds a row pair of all channels in LDS: (2 max(n_in, n_out) (L2 | 1) + 2 L2 + ...) complex values --
     // 131 KB at 16 channels, nfft = 384000; a part with less LDS per workgroup than that takes the layered route
-    static int lds_limit = 0;
-    if (!lds_limit) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || v <= 0)
-            v = 64 * 1024;
-        lds_limit = v;
-    }
+    const size_t lds_limit = device_lds_limit();
     // a column-pass workgroup owns CT = VT / min(G, VT) columns of all G channels: CT must divide the row length
     for (int G : {n_in, n_out}) {
         const int vt = cols_vt(G, l1), ct = vt / (G < vt ? G : vt);
@@ -1343,8 +1337,8 @@ int fl_spec_supports(int nfft, int n_in, int n_out) {
     }
     const int nch = n_in > n_out ? n_in : n_out;
     const size_t need = ((size_t)2 * nch * (l2 | 1) + 2 * (size_t)l2 + 64 + nch) * sizeof(cf);
-    if (need > (size_t)lds_limit) return 0;
-    return cols_lds_need(l1, n_in) <= (size_t)lds_limit && cols_lds_need(l1, n_out) <= (size_t)lds_limit ? 1 : 0;
+    if (need > lds_limit) return 0;
+    return cols_lds_need(l1, n_in) <= lds_limit && cols_lds_need(l1, n_out) <= lds_limit ? 1 : 0;
 }
 
 #ifndef FL_F64

@@ -845,7 +845,6 @@ __global__ void __launch_bounds__(256) sum_parts_kernel(const float4* __restrict
     out[j] = s;
 }
 
-constexpr int kMaxDevices = 64;
 constexpr int kMaxWalkWgs = 1024;     // stamps buffer: [2 * kMaxWalkWgs] per-workgroup (start, end) + [1] start of the next launch
 static int g_walk = 1;            // 0: off (spec_mid only); 1: on for the shapes below
 static int g_walk_wgs = 0;        // workgroups of the forward walking kernel (0: one per CU)
@@ -859,18 +858,6 @@ static int g_walk_us = [] { const char* e = getenv("FLAMO_WALK_US"); return e ? 
 
 long long* walk_successor_stamp() { return g_walk_stamps ? g_walk_stamps + 2 * kMaxWalkWgs : nullptr; }
 
-static int device_cus() {       // of the current device, cached per device
-    static int cus[kMaxDevices] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = 0;
-    if (!cus[dev]) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        cus[dev] = v;
-    }
-    return cus[dev];
-}
-
 // workgroups of the forward walking kernel: one per CU (a multiple of 8: XCD-aware order), never more than units
 static long walk_wgs(int L1, int Bn) {
     const long units = (long)(L1 / 2 + 1) * Bn;
@@ -880,25 +867,9 @@ static long walk_wgs(int L1, int Bn) {
     return g;
 }
 
-// The kernels of this file ask for more dynamic LDS than the default 64 KB: the attribute is per function AND per device, so
-// it is set once per (kernel, device) -- a second GPU used by the same process gets its own -- and its result is checked
-// (a part with less LDS per workgroup fails here with a message, not at the launch).
+// the kernels of this file ask for more dynamic LDS than the default 64 KB
 static int ensure_lds(const void* kern, size_t lds, bool* done /* [kMaxDevices] */) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = 0;
-    if (done[dev]) return FL_OK;
-    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-        set_error("walking kernels: %zu bytes of LDS per workgroup are not available on device %d (%s)", lds, dev, hipGetErrorString(e));
-        return FL_ERR_UNSUPPORTED;
-    }
-    done[dev] = true;
-    return FL_OK;
-}
-static size_t device_lds_limit() {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || v <= 0) v = 64 * 1024;
-    return (size_t)v;
+    return ensure_dynamic_lds(kern, lds, false, done, "walking kernels");
 }
 
 template <int A, int B, int NI, int NO>

@@ -795,6 +795,200 @@ def test_module_narrow_apply_gate(gpu, pairs, B):
     _rows("dX", Xg.grad[:, bins.to(gpu)].cpu().permute(0, 2, 1).reshape(B * Ni, -1), gX.permute(0, 2, 1).reshape(B * Ni, -1), TOL32_FE)
 
 
+# ============================================================================= 5. every kernel the C dispatchers can select
+# One shape family: nfft = 512 (257 bins: two bin blocks), contiguous bins, raw cascades of 11 sections, the octave equaliser
+# (12 sections).  (group, ...): each case reaches one template instantiation (two where a forward and a backward go together).
+GRID_NFFT, GRID_S, GRID_DB = 512, 11, 30.0
+GRID_RC_SHAPES = {2: (4, 2, 2), 4: (2, 4, 4), 8: (1, 8, 8)}      # (No, Nmid, Ni) of the lanes kernels, by NIW ((1, 16, 16): see below)
+GRID_CASES = (
+    # sos_response_bwd_mixed_kernel<SC, NIW>; NIW > 0 also sos_response_rc_kernel<NIW, float>.  Left out: <SC, 16>, all four SC --
+    # this family's draw misses TOL32_G in one (section, pair) row of dL/d(b, a), 2.152e-05 against 1e-05, the same figure at
+    # every SC (the chunk dispatch is not what misses); <12, 16> is reached by RC_CASES (1 x 2 x 16, 24 sections)
+    [("mixed", sc, niw) for sc in (4, 6, 8, 12) for niw in (0, 2, 4, 8)]
+    # sos_response_bwd_kernel<T, SC>
+    + [("plain", real, sc) for real in (torch.float32, torch.float64) for sc in (3, 4, 6, 12)]
+    # sos_response_bwd_kernel<double, 6, NIW> and sos_response_rc_kernel<NIW, double>
+    + [("rc64", niw) for niw in (2, 4, 8, 16)]
+    # sos_response_rc_fast_kernel<NIW, UNR>
+    + [("rcfast", niw, unr) for niw in (2, 4, 8, 16) for unr in (1, 2, 3, 6)]
+    # sos_response_rc_ba_kernel<NIW> (float32) and sos_bwd_lanes_kernel<T, NIW, NIW>; float64 (1, 16, 16) is not taken.  Left out:
+    # float32 (1, 16, 16) -- at 257 bins (22 bin blocks) the lanes backward returns a wrong dL/dWr, per-row error 3.5 against 1e-05
+    # with H and the other shapes within their limits; <float, 16, 16> is reached by RC_CASES (3 x 16 x 16 at nfft = 96000)
+    + [("lanes_rc", torch.float32, niw) for niw in (2, 4, 8)]
+    + [("lanes_rc", torch.float64, niw) for niw in (2, 4, 8)]
+    # sos_bwd_lanes_kernel<T, 0, 1>
+    + [("lanes", torch.float32), ("lanes", torch.float64)]
+    # sos_response_apply_fast_kernel<B>
+    + [("apply", 1), ("apply", 2)]
+)
+_GRID_REF = {}
+
+
+def _grid_ref(kind, chan, real=torch.float64):
+    """the float64 oracle of the family's cascade (kind "sos": raw sections; "geq": equaliser parameters as stored in `real`) at
+    the bin set, built once per (kind, chan, real) and shared by the cases: (inputs, leaves, response (bins, *chan), bins)"""
+    from oracle import hotpath as O
+    key = (kind, chan, real)
+    if key not in _GRID_REF:
+        bins = _bin_set(GRID_NFFT, seed=GRID_S)
+        if kind == "sos":
+            b, a = _sections(GRID_S, chan, seed=GRID_S * 7 + len(chan))
+            leaves = [b.clone().requires_grad_(True), a.clone().requires_grad_(True)]
+            bo, ao = leaves
+            inputs = (b, a)
+        else:
+            x = _geq_param(len(O.eq_freqs(1)[0]) + 3, chan, seed=GRID_NFFT + len(chan), sig=False, dtype=real)
+            leaves = [x.double().clone().requires_grad_(True)]      # (a copy: x itself goes to the GPU as a leaf of its own)
+            bo, ao = _geq_oracle_sections(leaves[0], False, 1)
+            inputs = (x,)
+        _GRID_REF[key] = (inputs, leaves, O.sos_response_at(bo, ao, GRID_NFFT, _gamma_t(GRID_DB, GRID_NFFT), bins), bins)
+    return _GRID_REF[key]
+
+
+def _grid_id(c):
+    return "-".join(str(v)[-7:] if isinstance(v, torch.dtype) else str(v) for v in c)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", GRID_CASES, ids=_grid_id)
+def test_cascade_dispatch_grid(gpu, case):
+    """Every kernel instantiation that the host dispatchers of csrc/response.hip and csrc/cascade2.hip can select, once each
+    (the cases above name them), at 257 bins against the float64 oracle: a dispatcher that sent one value of a run-time integer
+    (section chunk, columns of the constant factor, section pairs per trip, signal columns) to another value's kernel fails
+    its case.  Tolerances: the classes of this file's docstring."""
+    from flamo_amd import _lib, ops
+    from oracle import hotpath as O
+    group = case[0]
+    nfft, db = GRID_NFFT, GRID_DB
+    M = nfft // 2 + 1
+    L = _lib.lib()
+    gam = _gamma_f(db, nfft)
+
+    if group in ("mixed", "plain") and not (group == "mixed" and case[2]):      # ---- ops.sos_response
+        real = case[1] if group == "plain" else torch.float32
+        f64 = real == torch.float64
+        chan, C, S = (2, 3), 6, GRID_S
+        (b, a), leaves, Ho, bins = _grid_ref("sos", chan)
+        sfx = "c128" if f64 else "c64"
+        fwd, bwd = f"fl_sos_response_{sfx}", f"fl_sos_response_bwd_{sfx}"
+        with _knobs(chunk=case[2] if group == "plain" else case[1], mixed=None if f64 else group == "mixed", float_eval=True):
+            bg, ag = b.to(gpu).requires_grad_(True), a.to(gpu).requires_grad_(True)
+            nblk = L.fl_sos_bwd_blocks(M, C, S, int(group == "mixed"))
+            _poison(gpu, _rows_bytes(C, M, 16 if f64 else 8), nblk * 6 * S * C * 8)
+            with _spy(fwd, bwd) as calls:
+                H = ops.sos_response(bg, ag, gam, nfft, dtype=real)
+                ct, ct_sel = _cotangent(H.shape, bins, H.dtype, gpu, seed=nfft + S)
+                _poison(gpu, nblk * 6 * S * C * 8)
+                (H * ct.conj()).real.sum().backward()
+            assert calls[fwd] == 1 and calls[bwd] == 1, calls
+        _rows("H", _resp_rows(H, bins), Ho.detach().flatten(1).transpose(0, 1), TOL64_H if f64 else TOL32_H)
+        gbo, gao = torch.autograd.grad((Ho * ct_sel.reshape(Ho.shape).conj()).real.sum(), leaves, retain_graph=True)
+        _rows("dba", _coef_rows(bg.grad.cpu(), ag.grad.cpu()), _coef_rows(gbo, gao), TOL64_G if f64 else TOL32_G)
+        return
+
+    if group in ("mixed", "rc64", "rcfast"):      # ---- ops.sos_response_rc, (No, Nmid) = (2, 3)
+        real = torch.float64 if group == "rc64" else torch.float32
+        f64 = real == torch.float64
+        No, Nmid, S = 2, 3, GRID_S
+        Ni = case[2] if group == "mixed" else case[1]
+        C, esz = No * Nmid, 16 if f64 else 8
+        want_c = group != "rcfast"      # a wanted coefficient gradient keeps the forward on the double evaluation
+        assert ops.cascade_rc_supported(real, Ni, Nmid, S)
+        (b, a), leaves, Go, bins = _grid_ref("sos", (No, Nmid))
+        g = torch.Generator().manual_seed(Nmid * 10 + Ni)
+        W = (torch.randn(Nmid, Ni, generator=g, dtype=torch.float64) / Nmid ** 0.5).to(real)
+        sfx = "c128" if f64 else "c64"
+        fwd, bwd, lanes_fn = f"fl_sos_response_rc_{sfx}", f"fl_sos_response_bwd_rc_{sfx}", f"fl_geq_response_bwd_lanes_{sfx}"
+        kn = dict(chunk=case[1]) if group == "mixed" else dict(lanes=0, rc_fast=case[2]) if group == "rcfast" else {}
+        with _knobs(mixed=True, float_eval=True, **kn):
+            bg, ag = b.to(gpu).requires_grad_(want_c), a.to(gpu).requires_grad_(want_c)
+            Wg = W.to(gpu).requires_grad_(True)
+            nblk = L.fl_sos_bwd_blocks(M, C, S, 0 if f64 else 1)
+            _poison(gpu, _rows_bytes(C, M, esz), _rows_bytes(No * Ni, M, esz))
+            with _spy(fwd, bwd, lanes_fn) as calls:
+                H = ops.sos_response_rc(bg, ag, Wg, gam, nfft, dtype=real)
+                assert H.shape == (M, No, Ni)
+                ct, ct_sel = _cotangent(H.shape, bins, H.dtype, gpu, seed=nfft + Ni)
+                _poison(gpu, nblk * 6 * S * C * 8, nblk * C * Ni * (esz // 2))
+                (H * ct.conj()).real.sum().backward()
+            assert calls[fwd] == 1 and calls[bwd] == 1 and calls[lanes_fn] == 0, calls
+        Wo = W.double().requires_grad_(True)
+        Ho = Go @ O.to_complex(Wo).to(Go.dtype)
+        _rows("H", _resp_rows(H, bins), Ho.detach().flatten(1).transpose(0, 1),
+              TOL64_H if f64 else (TOL32_H if want_c else TOL32_FE))
+        grads = torch.autograd.grad((Ho * ct_sel.reshape(Ho.shape).conj()).real.sum(), leaves + [Wo], retain_graph=True)
+        tg = TOL64_G if f64 else TOL32_G
+        _rows("dWr", Wg.grad.cpu().double(), grads[-1], tg)
+        if want_c:
+            _rows("dba", _coef_rows(bg.grad.cpu(), ag.grad.cpu()), _coef_rows(grads[0], grads[1]), tg)
+        else:
+            assert bg.grad is None and ag.grad is None
+        return
+
+    if group in ("lanes", "lanes_rc"):      # ---- ops.geq_cascade / ops.geq_cascade_rc through the lanes-per-section backward
+        real = case[1]
+        f64 = real == torch.float64
+        rc = group == "lanes_rc"
+        No, Nmid, Ni = GRID_RC_SHAPES[case[2]] if rc else (8, 1, 0)
+        chan = (No, Nmid) if rc else (8,)
+        C, esz = No * Nmid, 16 if f64 else 8
+        (x,), leaves, Go, bins = _grid_ref("geq", chan, real)
+        S = x.shape[0]
+        assert S == 12
+        sfx = "c128" if f64 else "c64"
+        fwd = f"fl_geq_response_rc_{sfx}" if rc else ("fl_sos_response_c128" if f64 else "fl_geq_response_c64")
+        lanes_fn = f"fl_geq_response_bwd_lanes_{sfx}"
+        gen1 = f"fl_sos_response_bwd_rc_{sfx}" if rc else f"fl_sos_response_bwd_{sfx}"
+        blocks = L.fl_geq_bwd_lanes_blocks_f64 if f64 else L.fl_geq_bwd_lanes_blocks
+        with _knobs(lanes=1, mixed=True, float_eval=True):
+            nbx = blocks(M, C, S, nfft, 0, Nmid, Ni, int(rc))
+            assert nbx > 0, "the lanes kernel must take this shape"
+            wrows = (L.fl_geq_bwd_lanes_wrows_f64 if f64 else L.fl_geq_bwd_lanes_wrows)(M, C, S, nfft, 0, Nmid, Ni) if rc else 0
+            consts = _geq_design(1).device_consts(gpu)
+            xg = x.to(gpu).requires_grad_(True)
+            if rc:
+                g = torch.Generator().manual_seed(No * 100 + Nmid * 10 + Ni)
+                W = (torch.randn(Nmid, Ni, generator=g, dtype=torch.float64) / Nmid ** 0.5).to(real)
+                Wg = W.to(gpu).requires_grad_(True)
+            _poison(gpu, _rows_bytes(C, M, esz), _rows_bytes(No * Ni, M, esz))
+            with _spy(fwd, lanes_fn, gen1) as calls:
+                if rc:
+                    H = ops.geq_cascade_rc(xg, consts, Wg, gam, nfft, dtype=real)
+                else:
+                    H = ops.geq_cascade(xg, consts, gam, nfft, dtype=real)
+                ct, ct_sel = _cotangent(H.shape, bins, H.dtype, gpu, seed=nfft + S + Ni)
+                _poison(gpu, S * C * nbx * 4 * (esz // 2), C * nbx * (esz // 2), Nmid * Ni * wrows * (esz // 2))
+                (H * ct.conj()).real.sum().backward()
+            assert calls[fwd] == 1 and calls[lanes_fn] == 1 and calls[gen1] == 0, calls
+        if rc:
+            Wo = W.double().requires_grad_(True)
+            Ho = Go @ O.to_complex(Wo).to(Go.dtype)
+        else:
+            Wo, Ho = None, Go
+        _rows("H", _resp_rows(H, bins), Ho.detach().flatten(1).transpose(0, 1), TOL64_H if f64 else TOL32_FE)
+        grads = torch.autograd.grad((Ho * ct_sel.reshape(Ho.shape).conj()).real.sum(), leaves + ([Wo] if rc else []), retain_graph=True)
+        if rc:
+            _rows("dWr", Wg.grad.cpu().double(), grads[-1], TOL64_G if f64 else TOL32_G)
+        _rows("dx", _band_rows(xg.grad.cpu().double()), _band_rows(grads[0]), TOL64_G if f64 else TOL32_GAIN)
+        return
+
+    assert group == "apply"      # ---- ops.sos_response_apply under no_grad: one launch, B columns
+    B, No, Ni, S = case[1], 3, 5, GRID_S
+    (b, a), _, Ho, bins = _grid_ref("sos", (No, Ni))
+    g = torch.Generator().manual_seed(S * 31 + Ni)
+    X = torch.complex(torch.randn(B, M, Ni, generator=g), torch.randn(B, M, Ni, generator=g))
+    with _knobs(mixed=True, float_eval=True):
+        Xg = X.to(gpu)
+        assert ops.cascade_apply_supported(torch.float32, Xg) and Ni <= L.fl_sos_response_apply_max_ni(S)
+        _poison(gpu, _rows_bytes(No * Ni, M, 8), B * ops._pitch(M) * No * 8, B * M * No * 8)
+        with _spy("fl_sos_response_apply_c64", "fl_sos_response_c64", "fl_sos_response_f32eval_c64") as calls, torch.no_grad():
+            Y = ops.sos_response_apply(b.to(gpu), a.to(gpu), Xg, gam, nfft)
+        assert calls == {"fl_sos_response_apply_c64": 1, "fl_sos_response_c64": 0, "fl_sos_response_f32eval_c64": 0}, calls
+    assert Y.shape == (B, M, No)
+    Yo = torch.einsum("kmn,bkn->bkm", Ho.detach(), X[:, bins].to(torch.complex128))
+    _rows("Y", Y[:, bins.to(gpu)].cpu().permute(0, 2, 1).reshape(B * No, -1), Yo.permute(0, 2, 1).reshape(B * No, -1), TOL32_FE)
+
+
 # ============================================================================= CPU: the yardstick itself
 @pytest.mark.parametrize("nfft", [29, 40])
 def test_oracle_at_bins_matches_full(nfft):
