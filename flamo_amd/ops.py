@@ -22,7 +22,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["rfft", "irfft", "spectral_apply", "permute_bins", "mimo", "solve", "delay_response", "sos_response", "geq_sections", "solve_dud", "to_planar", "set_bin_shard",
+__all__ = ["rfft", "irfft", "spectral_apply", "permute_bins", "mimo", "solve", "delay_response", "scatter_response", "sos_response", "geq_sections", "solve_dud", "to_planar", "set_bin_shard",
            "bin_shard"]
 
 
@@ -1931,6 +1931,94 @@ def delay_response(m_int: torch.Tensor, amp: torch.Tensor, nfft: int) -> torch.T
     _lib.check(fn(m32.data_ptr(), amp.data_ptr(), C_, twiddles(nfft, real, dev).data_ptr(), nfft, bin0, m_local,
                   H.data_ptr(), _pitch(m_local), _stream()), "delay_response")
     return H.movedim(-1, 0)
+
+
+SCATTER_MAX_N = 32          # fl_scatter_response_*: 2 <= N <= 32 channels,
+SCATTER_MAX_STAGES = 8      # 2 <= K+1 <= 8 stage matrices
+
+
+def scatter_supported(N: int, stages: int) -> bool:
+    return 2 <= int(N) <= SCATTER_MAX_N and 2 <= int(stages) <= SCATTER_MAX_STAGES
+
+
+ScatterConsts = namedtuple("ScatterConsts", "shifts m_L m_R amp amp_L amp_R")
+
+
+def scatter_consts(shifts, m_L, m_R, gain_per_sample: float, gamma_f: float, nfft: int, real, dev) -> ScatterConsts:
+    """What the scattering kernels read beside the stage matrices: the delays reduced to [0, nfft) as int32 (the phase) and
+    the amplitudes of the unreduced ones, (gamma g)^shift per stage row and gamma^m for the outer delays, raised in float64."""
+    sh = shifts.to(device=dev, dtype=torch.float64).round()
+    mL = m_L.to(device=dev, dtype=torch.float64).round()
+    mR = m_R.to(device=dev, dtype=torch.float64).round()
+    red = lambda m: torch.remainder(m, nfft).to(torch.int32).contiguous()  # noqa: E731
+    amp = lambda base, m: torch.pow(torch.full_like(m, base), m).to(real).contiguous()  # noqa: E731
+    return ScatterConsts(red(sh), red(mL), red(mR), amp(float(gamma_f) * float(gain_per_sample), sh), amp(float(gamma_f), mL),
+                         amp(float(gamma_f), mR))
+
+
+def _scatter_args(Uc, c: ScatterConsts):
+    stages, N = Uc.shape[0], Uc.shape[1]
+    return (Uc.data_ptr(), c.amp.data_ptr(), c.shifts.data_ptr(), c.amp_L.data_ptr(), c.m_L.data_ptr(), c.amp_R.data_ptr(),
+            c.m_R.data_ptr(), N, stages)
+
+
+class _ScatterResponse(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, U, consts, nfft):
+        dev = _require_gpu(U, *consts)
+        real = _rdtype(U)
+        stages, N = U.shape[0], U.shape[1]
+        bin0, m_local = _bin0_arg(nfft)
+        if bin0 < 0:      # the row-major order is not generated here: natural order, DSP._response_in_order permutes it
+            bin0, m_local = 0, nfft // 2 + 1
+        Uc = U.contiguous()
+        W = twiddles(nfft, real, dev)
+        H = _empty_rows((N, N), m_local, _cdtype(real), dev)
+        fn = _fn("fl_scatter_response", real, True)
+        with kernel_timer.span("scatter_response"):
+            _lib.check(fn(*_scatter_args(Uc, consts), W.data_ptr(), nfft, bin0, m_local, H.data_ptr(), _pitch(m_local), _stream()),
+                       "scatter_response")
+        # the node holds every tensor the launches read (the backward reads them again)
+        ctx.keep = (Uc, consts, W)
+        ctx.cfg = (real, nfft, bin0, m_local)
+        return H.movedim(-1, 0)
+
+    @staticmethod
+    def backward(ctx, gH):
+        Uc, consts, W = ctx.keep
+        real, nfft, bin0, m_local = ctx.cfg
+        stages, N = Uc.shape[0], Uc.shape[1]
+        g = _h_planar(gH.resolve_conj().to(_cdtype(real)), True)
+        g_pitch = _lead_pitch(g.movedim(0, -1)) if m_local else 0
+        rows = _lib.lib().fl_scatter_bwd_blocks(N, m_local, int(real == torch.float64))
+        part = torch.empty((rows, stages, N, N), dtype=torch.float64, device=Uc.device)     # every entry is written
+        dU = torch.empty_like(Uc)
+        fn = _fn("fl_scatter_response_bwd", real, True)
+        with kernel_timer.span("scatter_response_bwd"):
+            _lib.check(fn(g.data_ptr(), g_pitch, *_scatter_args(Uc, consts), W.data_ptr(), nfft, bin0, m_local, part.data_ptr(),
+                          rows, dU.data_ptr(), _stream()), "scatter_response_bwd")
+        return dU, None, None
+
+
+def scatter_response(U: torch.Tensor, shifts: torch.Tensor, m_L: torch.Tensor, m_R: torch.Tensor, gain_per_sample: float,
+                     gamma_f: float, nfft: int, consts: Optional[ScatterConsts] = None) -> torch.Tensor:
+    """Per-bin response (m_local, N, N) of the scattering matrix D(m_L) U_K D(m_K) ... U_1 D(m_1) U_0 D(m_R) for the local bin
+    range, D(m) = diag((gamma^m) exp(-2 pi i (k m mod nfft) / nfft)) and row i of stage s also scaled by
+    gain_per_sample^shifts[s-1, i] (ScatteringMatrix / VelvetNoiseMatrix.get_freq_response, dsp.py:1162-1180, without the
+    (L, N, N) FIR matrix).  U: real (K+1, N, N) on the GPU, the only input with a gradient; shifts (K, N), m_L, m_R (N,):
+    integer-valued tensors.  ``consts``: the result of ``scatter_consts`` for these delays, when the caller keeps one."""
+    if U.dim() != 3 or U.shape[1] != U.shape[2] or U.dtype not in (torch.float32, torch.float64):
+        raise ValueError("scatter_response expects a real (K+1, N, N) stack of stage matrices")
+    dev = _require_gpu(U)
+    stages, N = U.shape[0], U.shape[1]
+    if not scatter_supported(N, stages):
+        raise ValueError(f"scatter_response: no kernel for N = {N}, {stages} stages (2 <= N <= {SCATTER_MAX_N}, "
+                         f"2 <= stages <= {SCATTER_MAX_STAGES})")
+    if consts is None:
+        if tuple(shifts.shape) != (stages - 1, N) or tuple(m_L.shape) != (N,) or tuple(m_R.shape) != (N,):
+            raise ValueError("scatter_response: shifts must be (K, N), m_L and m_R (N,)")
+        consts = scatter_consts(shifts, m_L, m_R, gain_per_sample, gamma_f, nfft, U.dtype, dev)
+    return _ScatterResponse.apply(U, consts, int(nfft))
 
 
 # float32 modules: evaluate the cascade forward in float (fl_sos_response_f32eval_c64: 3e-7 against 6e-8 of the double

@@ -8,6 +8,7 @@ import torch
 from torch import nn
 
 from .. import ops
+from .utils import generate_partitions
 
 
 class mse_loss(nn.Module):
@@ -30,6 +31,35 @@ class mse_loss(nn.Module):
         # summed columns than the kernel takes): the reference's own lines
         y_pred_sum = torch.sum(y_pred, dim=-1)
         return self.mse_loss(y_pred_sum, y_true.squeeze(-1))
+
+
+class masked_mse_loss(nn.Module):
+    """Mean squared error over a random subset of the frequency bins, flamo/optimize/loss.py:106-167: the bins are shuffled and
+    cut into sets of ``n_samples`` (``generate_partitions``), every call takes the next set, and when all are used the walk
+    starts over -- with freshly drawn sets when ``regenerate_mask``.  A few thousand samples per step: plain torch on
+    whatever device the prediction lives."""
+
+    def __init__(self, nfft: int, n_samples: int, n_sets: int = 1, regenerate_mask: bool = True, device: str = "cpu"):
+        super().__init__()
+        self.device = device
+        self.n_samples = n_samples
+        self.n_sets = n_sets
+        self.nfft = nfft
+        self.regenerate_mask = regenerate_mask
+        self.mask_indices = self._draw()
+        self.i = -1
+
+    def _draw(self):
+        return generate_partitions(torch.arange(self.nfft // 2 + 1), self.n_samples, self.n_sets)
+
+    def forward(self, y_pred, y_true):
+        self.i += 1
+        if self.i >= self.mask_indices.shape[0]:
+            self.i = 0
+            if self.regenerate_mask:
+                self.mask_indices = self._draw()
+        mask = self.mask_indices[self.i].to(y_pred.device)
+        return torch.mean(torch.pow(y_pred[:, mask] - y_true[:, mask], 2))
 
 
 # where the reference looks for the mixing matrix of an FDN core, in its order (optimize/loss.py:41-49)

@@ -25,6 +25,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..auxiliary.scattering import ScatteringMapping, hadamard_matrix
 from ..functional import (GEQDesign, accurate_geq, HadamardMatrix, RotationMatrix, bandpass_filter, eq_freqs, highpass_filter,
                           lowpass_filter, matrix_exp_capturable, rad2hertz, skew_matrix)
 from ..utils import to_complex
@@ -660,6 +661,131 @@ class parallelFilter(Filter):
 
     def probe(self, z: torch.Tensor):
         return torch.diag(self._probe_fir(z))
+
+
+# ============================================================================ scattering feedback matrices
+# ScatteringMatrix / VelvetNoiseMatrix: the response per bin from the factored form (ops.scatter_response) where its kernels
+# apply; False: always the FIR matrix through Filter's own response (tests compare the two)
+SCATTERING_PER_BIN = True
+
+
+def _orthogonal_stack_map(x):
+    """exp of the skew part of every stage (dsp.py:1134): one fused launch per stage each way on the GPU (ops.matrix_exp),
+    the fixed-schedule torch evaluation otherwise"""
+    if x.is_cuda and x.dim() == 3 and x.shape[-1] <= ops.EXPM_MAX_N and x.dtype in (torch.float32, torch.float64):
+        return torch.stack([ops.matrix_exp(x[s], skew=True) for s in range(x.shape[0])])
+    return matrix_exp_capturable(skew_matrix(x))
+
+
+class _ScatteringMixin:
+    """What ScatteringMatrix and VelvetNoiseMatrix share: ``map_filter`` (auxiliary.ScatteringMapping) holds the integer delays,
+    and the response of the stack U = map(param) is
+
+        H[f] = D(m_L) U_K G_K D(m_K) ... U_1 G_1 D(m_1) U_0 D(m_R),   D(m) = diag(gamma^m exp(-j w_f m)),  G_s = diag(g^m_s),
+
+    evaluated per bin by ``ops.scatter_response`` (no FIR matrix, exact integer phases) -- or, where that route does not apply
+    (host tensors, more taps than nfft, sizes outside the kernels' range, SCATTERING_PER_BIN off), as the reference does it:
+    rfft(map_filter(U) * gamma^n), truncated at nfft taps.  The delays are read from ``map_filter`` at every call."""
+
+    def _mapping_sparsity(self):
+        return self.sparsity
+
+    def initialize_class(self):
+        self.map_filter = ScatteringMapping(self.size[-1], n_stages=self.size[0] - 1, sparsity=self._mapping_sparsity(),
+                                            gain_per_sample=self.gain_per_sample, pulse_size=self.pulse_size, m_L=self.m_L,
+                                            m_R=self.m_R, device=self.device, dtype=self.dtype)
+        self.m_L, self.m_R = self.map_filter.m_L, self.map_filter.m_R
+        self.check_param_shape()
+        self.get_io()
+        self.get_freq_response()
+        self.get_freq_convolve()
+
+    def _delays(self, dev, real):
+        """(FIR length, ops.ScatterConsts on `dev` or None) for map_filter's current delay tensors: built once per tensor
+        identity / version counter (the entry keeps the tensors alive: their id() is the key)"""
+        mf = self.map_filter
+        held = (mf.shifts, mf.m_L, mf.m_R)
+        key = (tuple((id(t), t._version) for t in held), dev, real, float(mf.gain_per_sample), self._gamma_f)
+        hit = self.__dict__.get("_delay_cache")
+        if hit is None or hit[0] != key:
+            consts = None if dev is None else ops.scatter_consts(*held, mf.gain_per_sample, self._gamma_f, self.nfft, real, dev)
+            hit = self.__dict__["_delay_cache"] = (key, held, mf.fir_length(), consts)
+        return hit[2], hit[3]
+
+    def _per_bin_now(self, param) -> bool:
+        if not (SCATTERING_PER_BIN and torch.is_tensor(param) and param.is_cuda and param.dtype in (torch.float32, torch.float64)
+                and ops.scatter_supported(self.size[-1], self.size[0])):
+            return False
+        return self._delays(param.device, param.dtype)[0] <= self.nfft
+
+    def get_freq_response(self):
+        Filter.get_freq_response(self)
+        self.ir = lambda x: self.map_filter(self.map(x))
+        fir_response = self.freq_response
+
+        def response(param):
+            if not self._per_bin_now(param):
+                return fir_response(param)
+            mf = self.map_filter
+            consts = self._delays(param.device, param.dtype)[1]
+            return ops.scatter_response(self.map(param), mf.shifts, mf.m_L, mf.m_R, mf.gain_per_sample, self._gamma_f, self.nfft,
+                                        consts=consts)
+
+        self.freq_response = response
+
+    def probe(self, z: torch.Tensor):
+        """the factored form at a complex z: every delay m contributes (gamma / z)^m"""
+        mf = self.map_filter
+        U = to_complex(self.map(self.param))
+        q = self.gamma.to(U.device) / z
+        d = lambda m: q ** m.to(device=U.device, dtype=self.dtype)  # noqa: E731
+        H = U[0] * d(mf.m_R).unsqueeze(0)
+        for s in range(1, U.shape[0]):
+            gain = mf.gain_per_sample ** mf.shifts[s - 1].to(device=U.device, dtype=self.dtype)
+            H = U[s] @ ((gain * d(mf.shifts[s - 1])).unsqueeze(1) * H)
+        return d(mf.m_L).unsqueeze(1) * H
+
+
+class ScatteringMatrix(_ScatteringMixin, Filter):
+    """Scattering filter matrix, the filter feedback matrix of a scattering FDN (dsp.py:1052-1203): param (K+1, N, N), mapped
+    stage by stage to orthogonal matrices with sparse integer delays between them, which makes the matrix paraunitary
+    (lossless) for gain_per_sample = 1."""
+
+    def __init__(self, size: tuple = (1, 1, 1), nfft: int = 2 ** 11, sparsity: int = 3, gain_per_sample: float = 0.9999,
+                 pulse_size: int = 1, m_L: torch.Tensor = None, m_R: torch.Tensor = None, requires_grad: bool = False,
+                 alias_decay_db: float = 0.0, device: Optional[str] = None, dtype: torch.dtype = torch.float32):
+        self.sparsity = sparsity
+        self.gain_per_sample = gain_per_sample
+        self.pulse_size = pulse_size
+        self.m_L = m_L
+        self.m_R = m_R
+        assert size[1] == size[2], "Matrix must be square"
+        super().__init__(size=size, nfft=nfft, map=_orthogonal_stack_map, requires_grad=requires_grad,
+                         alias_decay_db=alias_decay_db, device=device, dtype=dtype)
+
+
+class VelvetNoiseMatrix(_ScatteringMixin, Filter):
+    """Velvet-noise filter matrix (dsp.py:1207-1348): the scattering structure with every stage the Hadamard matrix and
+    floor(1 / density) as the sparsity.  Not learnable."""
+
+    def __init__(self, size: tuple = (1, 1, 1), nfft: int = 2 ** 11, density: float = 0.03, gain_per_sample: float = 0.9999,
+                 m_L: torch.Tensor = None, m_R: torch.Tensor = None, alias_decay_db: float = 0.0, device: Optional[str] = None,
+                 dtype: torch.dtype = torch.float32):
+        self.sparsity = 1 / density
+        self.gain_per_sample = gain_per_sample
+        self.pulse_size = 1
+        self.m_L = m_L
+        self.m_R = m_R
+        assert size[1] == size[2], "Matrix must be square"
+        assert (size[1] & (size[1] - 1)) == 0, "At the moment the Matrix must have dimensions which are powers of 2"
+        super().__init__(size=size, nfft=nfft, map=_identity, requires_grad=False, alias_decay_db=alias_decay_db, device=device,
+                         dtype=dtype)
+        self.assign_value(hadamard_matrix(self.size[-1]).to(device=self.device, dtype=self.dtype).unsqueeze(0)
+                          .repeat(self.size[0], 1, 1))
+
+    def _mapping_sparsity(self):
+        import math
+        return math.floor(self.sparsity)
 
 
 # cascade-type filters applied to few columns: see _SOSMixin._apply_narrow

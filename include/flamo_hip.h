@@ -335,6 +335,37 @@ int fl_delay_response_c64(const int32_t* m, const void* amp, int C, const void* 
 int fl_delay_response_c128(const int32_t* m, const void* amp, int C, const void* W, int nfft,
                            int bin0, int m_local, void* H, long h_pitch, void* stream);
 
+/* Scattering feedback matrices, ScatteringMatrix / VelvetNoiseMatrix.get_freq_response (dsp.py:1162-1180, 1307-1325 over
+ * ScatteringMapping.forward, flamo/auxiliary/scattering.py:67-94: an (L, N, N) FIR matrix convolved together stage by stage, times
+ * the alias envelope, through rfft), evaluated per bin in the factored form it comes from:
+ *   H[f] = D(mL) U_K D(m_K) ... U_1 D(m_1) U_0 D(mR),   D(m) = diag(a_i exp(-2 pi i ((bin0+f) m_i mod nfft) / nfft)).
+ * U: real (stages, N, N), stages = K+1, same precision as H; shifts: int32 (K, N), mL / mR: int32 (N), every delay REDUCED by the
+ * caller to [0, nfft) (only the phase reads it); amp (K, N), ampL, ampR (N): real amplitudes of the UNREDUCED delays (alias
+ * envelope and per-sample gain raised to the delay, computed by the caller in float64); W: the master twiddle table of H's
+ * precision.  H planar (N, N, h_pitch): (i*N+j)*h_pitch + f is bin bin0+f of row i, column j.  bin0 >= 0 only: the row-major
+ * order is not generated here (FL_ERR_BAD_ARG; fl_permute_bins_* converts).  2 <= N <= 32, 2 <= stages <= 8
+ * (fl_scatter_supported: 1 / 0). */
+int fl_scatter_supported(int N, int stages);
+int fl_scatter_response_c64(const void* U, const void* amp, const int32_t* shifts, const void* ampL, const int32_t* mL,
+                            const void* ampR, const int32_t* mR, int N, int stages, const void* W, int nfft, int bin0,
+                            int m_local, void* H, long h_pitch, void* stream);
+int fl_scatter_response_c128(const void* U, const void* amp, const int32_t* shifts, const void* ampL, const int32_t* mL,
+                             const void* ampR, const int32_t* mR, int N, int stages, const void* W, int nfft, int bin0,
+                             int m_local, void* H, long h_pitch, void* stream);
+/* Its backward for the stage matrices: dU[s] = Re sum over the local bins and the columns of a_s w_s^H (torch's convention for
+ * the cotangent G, planar (N, N, g_pitch) like H).  The lanes recompute their stage vectors; no per-stage (M, N, N) tensor is
+ * written.  part: DOUBLE scratch (part_rows, stages, N, N), part_rows = fl_scatter_bwd_blocks(N, m_local, is_f64), one row per
+ * workgroup; dU: real (stages, N, N) = the rows summed in a fixed order by a second small launch (no atomics: the same bits every run). */
+int fl_scatter_bwd_blocks(int N, int m_local, int is_f64);
+int fl_scatter_response_bwd_c64(const void* G, long g_pitch, const void* U, const void* amp, const int32_t* shifts,
+                                const void* ampL, const int32_t* mL, const void* ampR, const int32_t* mR, int N, int stages,
+                                const void* W, int nfft, int bin0, int m_local, void* part, int part_rows, void* dU,
+                                void* stream);
+int fl_scatter_response_bwd_c128(const void* G, long g_pitch, const void* U, const void* amp, const int32_t* shifts,
+                                 const void* ampL, const int32_t* mL, const void* ampR, const int32_t* mR, int N, int stages,
+                                 const void* W, int nfft, int bin0, int m_local, void* part, int part_rows, void* dU,
+                                 void* stream);
+
 /* Second-order-section cascades, the tail shared by Biquad/SVF/GEQ/PEQ.get_poly_coeff
  * (dsp.py:1520-1526, 2587-2593):  per channel c and bin k,
  *   B_s = b[0,s,c] + b[1,s,c] g w + b[2,s,c] g^2 w^2,  A_s likewise,  w = exp(-2 pi i k/nfft),
