@@ -268,13 +268,18 @@ static inline size_t device_lds_limit() {
 // More dynamic LDS than the default 64 KB: the attribute is per function AND per device, so it is set once per (kernel, device)
 // -- a second GPU used by the same process gets its own -- and its result is checked (a part with less LDS per workgroup fails
 // here with a message that starts with `who`, not at the launch).  done: the kernel's own flags, one per device; to_limit: raise
-// the attribute to the device's limit rather than to this request.
+// the attribute to the device's limit (less the kernel's static LDS, which counts against the same limit) rather than to this request.
 constexpr int kMaxDevices = 64;
 static inline int ensure_dynamic_lds(const void* kern, size_t lds, bool to_limit, bool* done /* [kMaxDevices] */, const char* who) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = 0;
     if (done[dev]) return FL_OK;
-    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(to_limit ? device_lds_limit() : lds));
+    size_t want = lds;
+    if (to_limit) {
+        hipFuncAttributes fa;
+        want = device_lds_limit() - (hipFuncGetAttributes(&fa, kern) == hipSuccess ? fa.sharedSizeBytes : 0);
+    }
+    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want);
     if (e != hipSuccess) {
         set_error("%s: %zu bytes of LDS per workgroup are not available on device %d (%s)", who, lds, dev, hipGetErrorString(e));
         return FL_ERR_UNSUPPORTED;
@@ -286,12 +291,15 @@ static inline int ensure_dynamic_lds(const void* kern, size_t lds, bool to_limit
 // An entry that exists in both precisions, written ONCE: FL_ENTRY_C64_C128(name, (parameters), (arguments)) { body } makes the
 // body template <class T> static int name_entry(parameters), and the exported symbols name_c64 / name_c128 (declared in
 // include/flamo_hip.h: a parameter list that differs from the declaration does not compile) one-line forwards to
-// name_entry<float> / name_entry<double>.
-#define FL_ENTRY_C64_C128(NAME, PARAMS, ARGS)                                             \
+// name_entry<float> / name_entry<double>.  FL_ENTRY_F32_F64 is the same for the name_f32 / name_f64 pairs.  (At file scope or
+// inside namespace fl alike: the exported functions have C linkage either way.)
+#define FL_ENTRY_PAIR(NAME, SFX32, SFX64, PARAMS, ARGS)                                   \
     template <class T> static int NAME##_entry PARAMS;                                    \
-    extern "C" int NAME##_c64 PARAMS { return NAME##_entry<float> ARGS; }                 \
-    extern "C" int NAME##_c128 PARAMS { return NAME##_entry<double> ARGS; }               \
+    extern "C" int NAME##SFX32 PARAMS { return NAME##_entry<float> ARGS; }                \
+    extern "C" int NAME##SFX64 PARAMS { return NAME##_entry<double> ARGS; }               \
     template <class T> static int NAME##_entry PARAMS
+#define FL_ENTRY_C64_C128(NAME, PARAMS, ARGS) FL_ENTRY_PAIR(NAME, _c64, _c128, PARAMS, ARGS)
+#define FL_ENTRY_F32_F64(NAME, PARAMS, ARGS) FL_ENTRY_PAIR(NAME, _f32, _f64, PARAMS, ARGS)
 
 // ---------------------------------------------------------------- cache policy of the pipeline's data streams (host)
 // Each stream of the fused Shell pipeline (spectral.hip, specwalk.hip) and of the cascade kernels is loaded / stored either with

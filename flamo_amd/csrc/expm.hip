@@ -418,32 +418,26 @@ static int expm_threads(int N) {
     return t > 1024 ? 1024 : t;
 }
 
+// E / Ec (gE / gEc): the real and the complex-typed result (gradient); either may be null
 template <typename T>
 static int expm_fwd_impl(const void* X, int N, int skew, void* E, void* Ec, void* stash, void* stream) {
     FL_REQUIRE(X && (E || Ec) && stash, "matrix_exp: null pointer");
     FL_REQUIRE(N >= 1 && N <= 64, "matrix_exp: 1 <= N <= 64 (one workgroup, matrices in LDS)");
     const size_t lds = (size_t)3 * N * (N | 1) * sizeof(double);
-    if (lds > 64 * 1024) {
-        int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&expm_fwd_kernel<T, 0>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "matrix_exp LDS size");
+    if (lds > 64 * 1024) {      // (the fixed sizes all fit the default 64 KB of dynamic LDS)
+        static bool done[kMaxDevices];
+        const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&expm_fwd_kernel<T, 0>), lds, true, done, "matrix_exp");
         if (rc) return rc;
     }
     if (N == 16 && g_expm_mfma) {
         hipLaunchKernelGGL((expm16_fwd_kernel<T>), dim3(1), dim3(64), 0, (hipStream_t)stream, (const T*)X, skew, (T*)E, (T*)Ec, (double*)stash);
-        FL_CHECK_LAUNCH("matrix_exp");
-        return FL_OK;
+    } else {
+        auto launch = [&](auto NT) {
+            hipLaunchKernelGGL((expm_fwd_kernel<T, decltype(NT)::value>), dim3(1), dim3(expm_threads(N)), lds, (hipStream_t)stream, (const T*)X,
+                               N, skew, (T*)E, (T*)Ec, (double*)stash);
+        };
+        if (!dispatch<4, 8, 16, 32>(N, launch)) launch(std::integral_constant<int, 0>{});
     }
-#define FL_EXPM_FWD(NT_)                                                                                                   \
-    hipLaunchKernelGGL((expm_fwd_kernel<T, NT_>), dim3(1), dim3(expm_threads(N)), lds, (hipStream_t)stream, (const T*)X, N, \
-                       skew, (T*)E, (T*)Ec, (double*)stash)
-    switch (N) {        // (the fixed sizes all fit the default 64 KB of dynamic LDS)
-        case 4: FL_EXPM_FWD(4); break;
-        case 8: FL_EXPM_FWD(8); break;
-        case 16: FL_EXPM_FWD(16); break;
-        case 32: FL_EXPM_FWD(32); break;
-        default: FL_EXPM_FWD(0);
-    }
-#undef FL_EXPM_FWD
     FL_CHECK_LAUNCH("matrix_exp");
     return FL_OK;
 }
@@ -455,27 +449,20 @@ static int expm_bwd_impl(const void* gE, const void* gEc, int N, int skew, const
     size_t lds = (size_t)5 * N * (N | 1) * sizeof(double);
     if (lds > 160 * 1024) lds = (size_t)4 * N * (N | 1) * sizeof(double);
     if (lds > 64 * 1024) {
-        int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&expm_bwd_kernel<T, 0>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "matrix_exp_bwd LDS size");
+        static bool done[kMaxDevices];
+        const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&expm_bwd_kernel<T, 0>), lds, true, done, "matrix_exp_bwd");
         if (rc) return rc;
     }
     if (N == 16 && g_expm_mfma) {
         hipLaunchKernelGGL((expm16_bwd_kernel<T>), dim3(1), dim3(64), 0, (hipStream_t)stream, (const T*)gE, (const T*)gEc, skew,
                            (const double*)stash, (T*)gX);
-        FL_CHECK_LAUNCH("matrix_exp_bwd");
-        return FL_OK;
+    } else {
+        auto launch = [&](auto NT) {
+            hipLaunchKernelGGL((expm_bwd_kernel<T, decltype(NT)::value>), dim3(1), dim3(expm_threads(N)), lds, (hipStream_t)stream,
+                               (const T*)gE, (const T*)gEc, N, skew, (const double*)stash, (T*)gX);
+        };
+        if (!dispatch<4, 8, 16, 32>(N, launch)) launch(std::integral_constant<int, 0>{});
     }
-#define FL_EXPM_BWD(NT_)                                                                                                     \
-    hipLaunchKernelGGL((expm_bwd_kernel<T, NT_>), dim3(1), dim3(expm_threads(N)), lds, (hipStream_t)stream, (const T*)gE,    \
-                       (const T*)gEc, N, skew, (const double*)stash, (T*)gX)
-    switch (N) {
-        case 4: FL_EXPM_BWD(4); break;
-        case 8: FL_EXPM_BWD(8); break;
-        case 16: FL_EXPM_BWD(16); break;
-        case 32: FL_EXPM_BWD(32); break;
-        default: FL_EXPM_BWD(0);
-    }
-#undef FL_EXPM_BWD
     FL_CHECK_LAUNCH("matrix_exp_bwd");
     return FL_OK;
 }
@@ -484,47 +471,33 @@ static int expm_bwd_impl(const void* gE, const void* gEc, int N, int skew, const
 
 using namespace fl;
 
-extern "C" {
-int fl_debug_set_expm_mfma(int on) {
+extern "C" int fl_debug_set_expm_mfma(int on) {
     const int prev = g_expm_mfma;
     if (on >= 0) g_expm_mfma = on ? 1 : 0;
     return prev;
 }
-size_t fl_matrix_exp_stash_elems(int N) { return (size_t)EXPM_SLOTS * N * N + 1; }
-int fl_matrix_exp_f32(const void* X, int N, int skew, void* E, void* stash, void* stream) {
-    return expm_fwd_impl<float>(X, N, skew, E, nullptr, stash, stream);
+extern "C" size_t fl_matrix_exp_stash_elems(int N) { return (size_t)EXPM_SLOTS * N * N + 1; }
+
+// the real, the complex-typed and the two-result form: one body each way, null in the slot a form does not have
+FL_ENTRY_F32_F64(fl_matrix_exp, (const void* X, int N, int skew, void* E, void* stash, void* stream), (X, N, skew, E, stash, stream)) {
+    return expm_fwd_impl<T>(X, N, skew, E, nullptr, stash, stream);
 }
-int fl_matrix_exp_f64(const void* X, int N, int skew, void* E, void* stash, void* stream) {
-    return expm_fwd_impl<double>(X, N, skew, E, nullptr, stash, stream);
+FL_ENTRY_F32_F64(fl_matrix_exp_cplx, (const void* X, int N, int skew, void* E, void* stash, void* stream), (X, N, skew, E, stash, stream)) {
+    return expm_fwd_impl<T>(X, N, skew, nullptr, E, stash, stream);
 }
-int fl_matrix_exp_bwd_f32(const void* gE, int N, int skew, const void* stash, void* gX, void* stream) {
-    return expm_bwd_impl<float>(gE, nullptr, N, skew, stash, gX, stream);
+FL_ENTRY_F32_F64(fl_matrix_exp_both, (const void* X, int N, int skew, void* E, void* Ec, void* stash, void* stream),
+                 (X, N, skew, E, Ec, stash, stream)) {
+    return expm_fwd_impl<T>(X, N, skew, E, Ec, stash, stream);
 }
-int fl_matrix_exp_bwd_f64(const void* gE, int N, int skew, const void* stash, void* gX, void* stream) {
-    return expm_bwd_impl<double>(gE, nullptr, N, skew, stash, gX, stream);
+FL_ENTRY_F32_F64(fl_matrix_exp_bwd, (const void* gE, int N, int skew, const void* stash, void* gX, void* stream),
+                 (gE, N, skew, stash, gX, stream)) {
+    return expm_bwd_impl<T>(gE, nullptr, N, skew, stash, gX, stream);
 }
-int fl_matrix_exp_cplx_f32(const void* X, int N, int skew, void* E, void* stash, void* stream) {
-    return expm_fwd_impl<float>(X, N, skew, nullptr, E, stash, stream);
+FL_ENTRY_F32_F64(fl_matrix_exp_bwd_cplx, (const void* gE, int N, int skew, const void* stash, void* gX, void* stream),
+                 (gE, N, skew, stash, gX, stream)) {
+    return expm_bwd_impl<T>(nullptr, gE, N, skew, stash, gX, stream);
 }
-int fl_matrix_exp_cplx_f64(const void* X, int N, int skew, void* E, void* stash, void* stream) {
-    return expm_fwd_impl<double>(X, N, skew, nullptr, E, stash, stream);
-}
-int fl_matrix_exp_bwd_cplx_f32(const void* gE, int N, int skew, const void* stash, void* gX, void* stream) {
-    return expm_bwd_impl<float>(nullptr, gE, N, skew, stash, gX, stream);
-}
-int fl_matrix_exp_bwd_cplx_f64(const void* gE, int N, int skew, const void* stash, void* gX, void* stream) {
-    return expm_bwd_impl<double>(nullptr, gE, N, skew, stash, gX, stream);
-}
-int fl_matrix_exp_both_f32(const void* X, int N, int skew, void* E, void* Ec, void* stash, void* stream) {
-    return expm_fwd_impl<float>(X, N, skew, E, Ec, stash, stream);
-}
-int fl_matrix_exp_both_f64(const void* X, int N, int skew, void* E, void* Ec, void* stash, void* stream) {
-    return expm_fwd_impl<double>(X, N, skew, E, Ec, stash, stream);
-}
-int fl_matrix_exp_bwd_both_f32(const void* gE, const void* gEc, int N, int skew, const void* stash, void* gX, void* stream) {
-    return expm_bwd_impl<float>(gE, gEc, N, skew, stash, gX, stream);
-}
-int fl_matrix_exp_bwd_both_f64(const void* gE, const void* gEc, int N, int skew, const void* stash, void* gX, void* stream) {
-    return expm_bwd_impl<double>(gE, gEc, N, skew, stash, gX, stream);
-}
+FL_ENTRY_F32_F64(fl_matrix_exp_bwd_both, (const void* gE, const void* gEc, int N, int skew, const void* stash, void* gX, void* stream),
+                 (gE, gEc, N, skew, stash, gX, stream)) {
+    return expm_bwd_impl<T>(gE, gEc, N, skew, stash, gX, stream);
 }

@@ -1110,9 +1110,65 @@ static int rfft_impl(const void* x, long x_sig_stride, int ci_n, int t_in, void*
     return launch_fft<T>(false, a, p, nsig, (hipStream_t)stream);
 }
 
-template <typename T>
-static int irfft_impl(const void* X, long X_sig_stride, void* y, long y_sig_stride, int t_out, void* scratch, const void* W,
-                      int nsig, int nfft, double scale, double env_log2, int interior_half, void* stream) {
+// the unsigned word that moves an element of 4 / 8 / 16 bytes
+template <int BYTES>
+using word_t = std::conditional_t<BYTES == 4, uint32_t, std::conditional_t<BYTES == 8, uint64_t, uint4>>;
+
+}  // namespace fl
+
+using namespace fl;
+
+FL_ENTRY_F32_F64(fl_twiddle_fill, (void* W, int nfft, void* stream), (W, nfft, stream)) {
+    FL_REQUIRE(W && nfft > 0, "twiddle: bad arguments");
+    hipLaunchKernelGGL((twiddle_fill<T>), dim3(cdiv_i(nfft, 256)), dim3(256), 0, (hipStream_t)stream, (cx<T>*)W, nfft);
+    FL_CHECK_LAUNCH("twiddle_fill");
+    return FL_OK;
+}
+
+extern "C" int fl_fft_plan(int nfft, int is_f64, int* L1, int* L2) {
+    Plan p;
+    int rc = make_plan(nfft, is_f64 != 0, p);
+    if (rc) return rc;
+    if (L1) *L1 = p.L1;
+    if (L2) *L2 = p.L2;
+    return FL_OK;
+}
+
+extern "C" size_t fl_fft_scratch_elems(int nfft, int is_f64, int nsig) {
+    Plan p;
+    if (make_plan(nfft, is_f64 != 0, p) != FL_OK) return 0;
+    if (p.L1 == 1 || nsig <= 0) return 0;
+    return (size_t)p.L * (size_t)nsig;
+}
+
+extern "C" int fl_debug_set_fft_max_single(int max_half_len) {
+    g_max_single = max_half_len > 0 ? max_half_len : 0;
+    return FL_OK;
+}
+
+extern "C" int fl_debug_set_fft_fast(int enabled) {
+    g_fast_rt = enabled / 1000;
+    enabled %= 1000;
+    g_fast_enabled = enabled != 0;
+    g_fast_ct = (enabled == 32) ? 32 : (enabled == 16 ? 16 : 0);   // tuning: force 16- / 32-column tiles in pass 1
+    g_fast_pair = enabled != 2;                                     // 2: inverse column pass without mirror pairing
+    return FL_OK;
+}
+
+FL_ENTRY_F32_F64(fl_rfft, (const void* x, long xs, int t_in, void* X, long Xs, void* scratch, const void* W, int nsig, int nfft, double scale,
+                           double env_log2, int interior_x2, void* stream),
+                 (x, xs, t_in, X, Xs, scratch, W, nsig, nfft, scale, env_log2, interior_x2, stream)) {
+    return rfft_impl<T>(x, xs, 0, t_in, X, Xs, scratch, W, nsig, nfft, scale, env_log2, interior_x2, stream);
+}
+FL_ENTRY_F32_F64(fl_rfft_ci, (const void* x, int n_chan, int t_in, void* X, long Xs, void* scratch, const void* W, int nsig, int nfft,
+                              double scale, double env_log2, int interior_x2, void* stream),
+                 (x, n_chan, t_in, X, Xs, scratch, W, nsig, nfft, scale, env_log2, interior_x2, stream)) {
+    FL_REQUIRE(n_chan > 0, "rfft_ci: n_chan must be positive");
+    return rfft_impl<T>(x, 0, n_chan, t_in, X, Xs, scratch, W, nsig, nfft, scale, env_log2, interior_x2, stream);
+}
+FL_ENTRY_F32_F64(fl_irfft, (const void* X, long X_sig_stride, void* y, long y_sig_stride, int t_out, void* scratch, const void* W, int nsig,
+                            int nfft, double scale, double env_log2, int interior_half, void* stream),
+                 (X, X_sig_stride, y, y_sig_stride, t_out, scratch, W, nsig, nfft, scale, env_log2, interior_half, stream)) {
     Plan p;
     int rc = make_plan(nfft, sizeof(T) == 8, p);
     if (rc) return rc;
@@ -1134,82 +1190,7 @@ static int irfft_impl(const void* X, long X_sig_stride, void* y, long y_sig_stri
     return launch_fft<T>(true, a, p, nsig, (hipStream_t)stream);
 }
 
-template <typename T>
-static int twiddle_impl(void* W, int nfft, void* stream) {
-    FL_REQUIRE(W && nfft > 0, "twiddle: bad arguments");
-    hipLaunchKernelGGL((twiddle_fill<T>), dim3(cdiv_i(nfft, 256)), dim3(256), 0, (hipStream_t)stream, (cx<T>*)W, nfft);
-    FL_CHECK_LAUNCH("twiddle_fill");
-    return FL_OK;
-}
-
-}  // namespace fl
-
-using namespace fl;
-
-extern "C" {
-
-int fl_twiddle_fill_f32(void* W, int nfft, void* stream) { return twiddle_impl<float>(W, nfft, stream); }
-int fl_twiddle_fill_f64(void* W, int nfft, void* stream) { return twiddle_impl<double>(W, nfft, stream); }
-
-int fl_fft_plan(int nfft, int is_f64, int* L1, int* L2) {
-    Plan p;
-    int rc = make_plan(nfft, is_f64 != 0, p);
-    if (rc) return rc;
-    if (L1) *L1 = p.L1;
-    if (L2) *L2 = p.L2;
-    return FL_OK;
-}
-
-size_t fl_fft_scratch_elems(int nfft, int is_f64, int nsig) {
-    Plan p;
-    if (make_plan(nfft, is_f64 != 0, p) != FL_OK) return 0;
-    if (p.L1 == 1 || nsig <= 0) return 0;
-    return (size_t)p.L * (size_t)nsig;
-}
-
-int fl_debug_set_fft_max_single(int max_half_len) {
-    g_max_single = max_half_len > 0 ? max_half_len : 0;
-    return FL_OK;
-}
-
-int fl_debug_set_fft_fast(int enabled) {
-    g_fast_enabled = enabled != 0;
-    g_fast_rt = enabled / 1000;
-    enabled %= 1000;
-    g_fast_enabled = enabled != 0;
-    g_fast_ct = (enabled == 32) ? 32 : (enabled == 16 ? 16 : 0);   // tuning: force 16- / 32-column tiles in pass 1
-    g_fast_pair = enabled != 2;                                     // 2: inverse column pass without mirror pairing
-    return FL_OK;
-}
-
-int fl_rfft_f32(const void* x, long xs, int t_in, void* X, long Xs, void* scratch, const void* W, int nsig, int nfft,
-                double scale, double env_log2, int interior_x2, void* stream) {
-    return rfft_impl<float>(x, xs, 0, t_in, X, Xs, scratch, W, nsig, nfft, scale, env_log2, interior_x2, stream);
-}
-int fl_rfft_ci_f32(const void* x, int n_chan, int t_in, void* X, long Xs, void* scratch, const void* W, int nsig, int nfft,
-                   double scale, double env_log2, int interior_x2, void* stream) {
-    FL_REQUIRE(n_chan > 0, "rfft_ci: n_chan must be positive");
-    return rfft_impl<float>(x, 0, n_chan, t_in, X, Xs, scratch, W, nsig, nfft, scale, env_log2, interior_x2, stream);
-}
-int fl_rfft_f64(const void* x, long xs, int t_in, void* X, long Xs, void* scratch, const void* W, int nsig, int nfft,
-                double scale, double env_log2, int interior_x2, void* stream) {
-    return rfft_impl<double>(x, xs, 0, t_in, X, Xs, scratch, W, nsig, nfft, scale, env_log2, interior_x2, stream);
-}
-int fl_rfft_ci_f64(const void* x, int n_chan, int t_in, void* X, long Xs, void* scratch, const void* W, int nsig, int nfft,
-                   double scale, double env_log2, int interior_x2, void* stream) {
-    FL_REQUIRE(n_chan > 0, "rfft_ci: n_chan must be positive");
-    return rfft_impl<double>(x, 0, n_chan, t_in, X, Xs, scratch, W, nsig, nfft, scale, env_log2, interior_x2, stream);
-}
-int fl_irfft_f32(const void* X, long Xs, void* y, long ys, int t_out, void* scratch, const void* W, int nsig, int nfft,
-                 double scale, double env_log2, int interior_half, void* stream) {
-    return irfft_impl<float>(X, Xs, y, ys, t_out, scratch, W, nsig, nfft, scale, env_log2, interior_half, stream);
-}
-int fl_irfft_f64(const void* X, long Xs, void* y, long ys, int t_out, void* scratch, const void* W, int nsig, int nfft,
-                 double scale, double env_log2, int interior_half, void* stream) {
-    return irfft_impl<double>(X, Xs, y, ys, t_out, scratch, W, nsig, nfft, scale, env_log2, interior_half, stream);
-}
-
-int fl_transpose(const void* src, void* dst, int nbatch, int rows, int cols, long dst_pitch, int elem_bytes, void* stream) {
+extern "C" int fl_transpose(const void* src, void* dst, int nbatch, int rows, int cols, long dst_pitch, int elem_bytes, void* stream) {
     FL_REQUIRE(src && dst, "transpose: null pointer");
     FL_REQUIRE(nbatch >= 0 && rows >= 0 && cols >= 0 && dst_pitch >= rows, "transpose: bad sizes (dst_pitch >= rows)");
     if (nbatch == 0 || rows == 0 || cols == 0) return FL_OK;
@@ -1221,9 +1202,10 @@ int fl_transpose(const void* src, void* dst, int nbatch, int rows, int cols, lon
         const int tr = (cols == 4) ? 2048 : (cols == 8 ? 1024 : 512);   // 32 KB of LDS per workgroup
         dim3 g2(cdiv_i(rows, tr), nbatch);
         const size_t lds = (size_t)cols * (tr + 4) * 4;
-        if (cols == 4) hipLaunchKernelGGL((transpose_tall4_kernel<4>), g2, dim3(256), lds, st, (const uint32_t*)src, (uint32_t*)dst, rows, tr, dst_pitch);
-        else if (cols == 8) hipLaunchKernelGGL((transpose_tall4_kernel<8>), g2, dim3(256), lds, st, (const uint32_t*)src, (uint32_t*)dst, rows, tr, dst_pitch);
-        else hipLaunchKernelGGL((transpose_tall4_kernel<16>), g2, dim3(256), lds, st, (const uint32_t*)src, (uint32_t*)dst, rows, tr, dst_pitch);
+        dispatch<4, 8, 16>(cols, [&](auto NS) {
+            hipLaunchKernelGGL((transpose_tall4_kernel<decltype(NS)::value>), g2, dim3(256), lds, st, (const uint32_t*)src, (uint32_t*)dst, rows, tr,
+                               dst_pitch);
+        });
         FL_CHECK_LAUNCH("transpose_tall4");
         return FL_OK;
     }
@@ -1235,29 +1217,24 @@ int fl_transpose(const void* src, void* dst, int nbatch, int rows, int cols, lon
         if (TR < 64) TR = 64;
         dim3 g2(cdiv_i(nlong, TR), nbatch);
         const size_t lds = (size_t)TR * (nshort + 1) * elem_bytes;
-#define FL_TN(E) \
-        if (tall) hipLaunchKernelGGL((transpose_narrow_kernel<E, true>), g2, dim3(256), lds, st, (const E*)src, (E*)dst, nlong, nshort, TR, dst_pitch); \
-        else hipLaunchKernelGGL((transpose_narrow_kernel<E, false>), g2, dim3(256), lds, st, (const E*)src, (E*)dst, nlong, nshort, TR, dst_pitch)
-        switch (elem_bytes) {
-            case 4: FL_TN(uint32_t); break;
-            case 8: FL_TN(uint64_t); break;
-            case 16: FL_TN(uint4); break;
-            default: set_error("transpose: elem_bytes must be 4, 8 or 16"); return FL_ERR_BAD_ARG;
-        }
-#undef FL_TN
+        const bool known = dispatch<4, 8, 16>(elem_bytes, [&](auto EB) {
+            using E = word_t<decltype(EB)::value>;
+            dispatch<1, 0>(tall, [&](auto TALL) {
+                hipLaunchKernelGGL((transpose_narrow_kernel<E, decltype(TALL)::value != 0>), g2, dim3(256), lds, st, (const E*)src, (E*)dst, nlong,
+                                   nshort, TR, dst_pitch);
+            });
+        });
+        FL_REQUIRE(known, "transpose: elem_bytes must be 4, 8 or 16");
         FL_CHECK_LAUNCH("transpose_narrow");
         return FL_OK;
     }
     FL_REQUIRE(cdiv_i(rows, 32) <= 65535, "transpose: too many rows");
     dim3 grid(cdiv_i(cols, 32), cdiv_i(rows, 32), nbatch);
-    switch (elem_bytes) {
-        case 4: hipLaunchKernelGGL((transpose_kernel<uint32_t>), grid, dim3(256), 0, st, (const uint32_t*)src, (uint32_t*)dst, rows, cols, dst_pitch); break;
-        case 8: hipLaunchKernelGGL((transpose_kernel<uint64_t>), grid, dim3(256), 0, st, (const uint64_t*)src, (uint64_t*)dst, rows, cols, dst_pitch); break;
-        case 16: hipLaunchKernelGGL((transpose_kernel<uint4>), grid, dim3(256), 0, st, (const uint4*)src, (uint4*)dst, rows, cols, dst_pitch); break;
-        default: set_error("transpose: elem_bytes must be 4, 8 or 16"); return FL_ERR_BAD_ARG;
-    }
+    const bool known = dispatch<4, 8, 16>(elem_bytes, [&](auto EB) {
+        using E = word_t<decltype(EB)::value>;
+        hipLaunchKernelGGL((transpose_kernel<E>), grid, dim3(256), 0, st, (const E*)src, (E*)dst, rows, cols, dst_pitch);
+    });
+    FL_REQUIRE(known, "transpose: elem_bytes must be 4, 8 or 16");
     FL_CHECK_LAUNCH("transpose");
     return FL_OK;
 }
-
-}  // extern "C"

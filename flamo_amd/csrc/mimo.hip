@@ -409,7 +409,6 @@ __global__ void __launch_bounds__(256) mimo_mfma_lds_kernel(MmaArgs a) {
     }
 }
 
-static int g_mfma_vec = 1;   // tuning: 0 = direct 8-byte stores from the accumulator layout
 static int g_mfma_enabled = 1, g_mfma_tile16 = 0;   // tuning: off / always the 64-bin 16x16 tile
 
 // rows >= 16, >= 8 output columns and a contraction >= 8: below that the product is HBM-bound and the
@@ -423,7 +422,7 @@ static int launch_mfma(MmaArgs a, hipStream_t st, int red_slots = 0, int* slots_
     a.nct = cdiv_i(a.J1 * a.J2, ctile);
     long nb = (long)cdiv_i(cdiv_i(a.M, bins), 8) * 8 * a.nrt * a.nct;
     if (a.part) nb = (long)min(red_slots, cdiv_i(a.M, bins)) * a.nrt * a.nct;   // red_slots bin-tile slots
-    a.vec_store = !a.part && g_mfma_vec && ((uintptr_t)a.D % 16 == 0) && a.sd_i % 2 == 0 && a.sd_j1 % 2 == 0 && a.sd_j2 % 2 == 0;
+    a.vec_store = !a.part && ((uintptr_t)a.D % 16 == 0) && a.sd_i % 2 == 0 && a.sd_j1 % 2 == 0 && a.sd_j2 % 2 == 0;
     FL_REQUIRE(nb < (1ll << 31), "mimo: grid too large");
     if (wide) hipLaunchKernelGGL((mimo_mfma_lds_kernel<2, 2, 8, 4>), dim3((unsigned)nb), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((mimo_mfma_lds_kernel<4, 1, 4, 4>), dim3((unsigned)nb), dim3(256), 0, st, a);
@@ -431,251 +430,6 @@ static int launch_mfma(MmaArgs a, hipStream_t st, int red_slots = 0, int* slots_
     if (slots_used) *slots_used = (int)(nb / (a.nrt * a.nct));
     return FL_OK;
 }
-
-// ---------------------------------------------------------------- streaming form of the per-bin product (8 x 8, vector signals)
-// Y[b,:,f] = H[:,:,f] X[b,:,f] with the SIGNAL streamed through an LDS ring by LDS-DMA (global_load_lds, 16 bytes per lane:
-// one instruction moves two 512-byte plane rows of a 64-bin tile, no VGPR round trip) and the RESPONSE of the tile held in
-// registers for the whole batch: one wavefront per workgroup owns 64 bins, fetches its 64 response values per lane once
-// (H crosses the fabric exactly once, whatever the L2 does), then walks the batch in chunks of CB columns -- the chunk
-// t+1 is in flight while chunk t is multiplied and stored.  No barriers (single wavefront), ~32 KB of LDS per workgroup so
-// that the ~3 workgroups a CU gets are resident together.  Bin tiles past M read clamped addresses and store nothing.
-template <int NCH, int CB>
-__global__ void __launch_bounds__(64) mimo_stream_kernel(const cx<float>* __restrict__ H, long hs_m, long hs_n, int conj_h,
-                                                         const cx<float>* __restrict__ X, long xs_b, long xs_n,
-                                                         cx<float>* __restrict__ Y, long ys_b, long ys_m, int B, int M, long x_rows_end) {
-    __shared__ __attribute__((aligned(16))) cx<float> xt[2][CB][NCH][64];
-    const int lane = threadIdx.x;
-    // XCD-aware order is not needed: nothing is shared between workgroups
-    const int f0 = blockIdx.x * 64;
-    const int f = f0 + lane;
-    const bool live = f < M;
-    const int fc = live ? f : M - 1;
-    cx<float> h[NCH][NCH];
-#pragma unroll
-    for (int m = 0; m < NCH; ++m)
-#pragma unroll
-        for (int n = 0; n < NCH; ++n) {
-            h[m][n] = H[(long)m * hs_m + (long)n * hs_n + fc];
-            if (conj_h) h[m][n].y = -h[m][n].y;
-        }
-    // DMA of one chunk: instruction (c, np) moves plane rows n = 2 np and 2 np + 1 of column c: lanes 0..31 the first row,
-    // 32..63 the second, 16 bytes (two bins) each; the LDS image [c][n][64 bins] is lane-linear as the instruction requires
-    const int half = lane >> 5, piece = lane & 31;
-    auto dma = [&](int chunk, int buf) {
-#pragma unroll
-        for (int c = 0; c < CB; ++c) {
-            const int col = chunk * CB + c;
-            const cx<float>* colp = X + (long)(col < B ? col : B - 1) * xs_b;
-#pragma unroll
-            for (int np = 0; np < NCH / 2; ++np) {
-                long off = (long)(2 * np + half) * xs_n + f0 + 2 * piece;
-                if (off + 2 > x_rows_end) off = x_rows_end - 2;          // last tile of the last plane: stay inside the allocation
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(colp + off),
-                                                 (__attribute__((address_space(3))) void*)(&xt[buf][c][2 * np][0]), 16, 0, 0);
-            }
-        }
-    };
-    // gridDim.y batch splits: workgroup (tile, s) walks columns [s*per, (s+1)*per)
-    const int per = ((B + (int)gridDim.y - 1) / (int)gridDim.y + CB - 1) / CB * CB;
-    const int c_begin = blockIdx.y * per, c_end = min(B, c_begin + per);
-    if (c_begin >= c_end) return;
-    const int chunk0 = c_begin / CB, nchunk = (c_end - c_begin + CB - 1) / CB;
-    dma(chunk0, 0);
-    for (int tt = 0; tt < nchunk; ++tt) {
-        const int t = chunk0 + tt;
-        const int buf = tt & 1;
-        __builtin_amdgcn_s_waitcnt(0x0F70);            // vmcnt(0): chunk t has landed (and the previous chunk's stores have left)
-        if (tt + 1 < nchunk) dma(t + 1, buf ^ 1);
-#pragma unroll
-        for (int c = 0; c < CB; ++c) {
-            const int col = t * CB + c;
-            if (col >= c_end) break;
-            cx<float> x[NCH];
-#pragma unroll
-            for (int n = 0; n < NCH; ++n) x[n] = xt[buf][c][n][lane];
-            cx<float>* yp = Y + (long)col * ys_b + f;
-#pragma unroll
-            for (int m = 0; m < NCH; ++m) {
-                cx<float> acc(0.f, 0.f);
-#pragma unroll
-                for (int n = 0; n < NCH; ++n) fma_cx(acc, h[m][n], x[n]);
-                if (live) yp[(long)m * ys_m] = acc;
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------- host dispatch
-static int g_mimo_variant = 0;   // tuning hook: mt*100 + bt*10 + nu (0 = default choice)
-
-static int g_mimo_stream_split = 1, g_mimo_stream_cb = 4;
-static int g_mimo_stream = 0;   // 8x8 vector-signal products through the LDS-DMA streaming kernel (tuning hook: gradw_cap -16)
-static int g_mimo_hc = 1;
-static int g_gradh_tile = 4;   // 4 = 4x4 tiles (default), 84 = 8x4, 8 = 8x8 where the matrix allows (tuning hook)   // tuning: 0 = constant matrices through the per-bin addressing (gradw_cap -4)
-
-template <typename T, int MT, int BT, int NU>
-static void launch_full_one(dim3 grid, int nct, int nmt, hipStream_t st, const cx<T>* H, long hs_f, long hs_m, long hs_n, int conj_h,
-                            const cx<T>* X, long xs_b, long xs_n, long xs_k, cx<T>* Y, long ys_b, long ys_m, long ys_k,
-                            int B, int M, int No, int Ni, int K) {
-    if (NU == 1 && hs_f == 0 && (g_mimo_hc || (conj_h & 2)))
-        hipLaunchKernelGGL((mimo_full_kernel<T, MT, BT, 1, true>), grid, dim3(256), 0, st, H, hs_f, hs_m, hs_n, conj_h, X, xs_b, xs_n,
-                           xs_k, Y, ys_b, ys_m, ys_k, B, M, No, Ni, K, nct, nmt);
-    else
-        hipLaunchKernelGGL((mimo_full_kernel<T, MT, BT, NU>), grid, dim3(256), 0, st, H, hs_f, hs_m, hs_n, conj_h, X, xs_b, xs_n,
-                           xs_k, Y, ys_b, ys_m, ys_k, B, M, No, Ni, K, nct, nmt);
-}
-
-template <typename T>
-static int mimo_impl(const void* H, long hs_f, long hs_m, long hs_n, int conj_h, const void* X, long xs_b, long xs_n,
-                     long xs_k, void* Y, long ys_b, long ys_m, long ys_k, int B, int M, int No, int Ni, int K,
-                     void* stream) {
-    FL_REQUIRE(H && X && Y, "mimo: null pointer");
-    FL_REQUIRE(B >= 0 && M >= 0 && No > 0 && Ni > 0 && K > 0, "mimo: bad sizes");
-    if (B == 0 || M == 0) return FL_OK;
-    const int ncols = B * K;
-    const bool h_real = (conj_h & 2) != 0;
-    FL_REQUIRE(!h_real || (hs_f == 0 && g_mimo_variant == 0), "mimo: a real matrix must be frequency independent (hs_f = 0)");
-    if constexpr (sizeof(T) == 4) {
-        if (g_mimo_variant == 0 && !h_real && mfma_applies(No, ncols, Ni)) {
-            MmaArgs a = {};
-            a.A = (const cx<float>*)H; a.sa_f = hs_f; a.sa_i = hs_m; a.sa_t1 = 0; a.sa_t2 = hs_n; a.conj_a = conj_h;
-            a.B = (const cx<float>*)X; a.sb_j1 = xs_b; a.sb_j2 = xs_k; a.sb_t1 = 0; a.sb_t2 = xs_n; a.conj_b = 0;
-            a.D = (cx<float>*)Y; a.sd_i = ys_m; a.sd_j1 = ys_b; a.sd_j2 = ys_k; a.scale = 1.f;
-            a.M = M; a.NI = No; a.J1 = B; a.J2 = K; a.T1 = 1; a.T2 = Ni;
-            return launch_mfma(a, (hipStream_t)stream);
-        }
-    }
-    if constexpr (sizeof(T) == 4) {
-        // 8 x 8 per-bin responses on vector signals with 16-byte-aligned planes: the streaming kernel
-        if (g_mimo_stream && g_mimo_variant == 0 && !h_real && hs_f == 1 && K == 1 && No == 8 && Ni == 8 && B >= 4 &&
-            reinterpret_cast<uintptr_t>(X) % 16 == 0 && xs_n % 2 == 0 && xs_b % 2 == 0) {
-            const long x_rows_end = (long)(Ni - 1) * xs_n + (xs_n < M + 2 ? xs_n : ((M + 1) & ~1L));   // elements addressable in a column
-            const int bs = g_mimo_stream_split > 0 ? g_mimo_stream_split : 1;
-            if (g_mimo_stream_cb == 2)
-                hipLaunchKernelGGL((mimo_stream_kernel<8, 2>), dim3(cdiv_i(M, 64), bs), dim3(64), 0, (hipStream_t)stream,
-                                   (const cx<float>*)H, hs_m, hs_n, conj_h, (const cx<float>*)X, xs_b, xs_n, (cx<float>*)Y, ys_b,
-                                   ys_m, B, M, x_rows_end);
-            else
-                hipLaunchKernelGGL((mimo_stream_kernel<8, 4>), dim3(cdiv_i(M, 64), bs), dim3(64), 0, (hipStream_t)stream,
-                                   (const cx<float>*)H, hs_m, hs_n, conj_h, (const cx<float>*)X, xs_b, xs_n, (cx<float>*)Y, ys_b,
-                                   ys_m, B, M, x_rows_end);
-            FL_CHECK_LAUNCH("mimo_stream");
-            return FL_OK;
-        }
-    }
-    int bt = ncols >= 4 ? 4 : (ncols >= 2 ? 2 : 1);
-    int mt = No >= 8 ? 8 : (No >= 4 ? 4 : (No >= 2 ? 2 : 1));
-    int nu = 1;
-    if (g_mimo_variant > 0) {
-        mt = g_mimo_variant / 100;
-        bt = (g_mimo_variant / 10) % 10;
-        nu = g_mimo_variant % 10;
-    }
-    const int nct = cdiv_i(ncols, bt), nmt = cdiv_i(No, mt);
-    const size_t nblk = (size_t)cdiv_i(cdiv_i(M, 256), 8) * 8 * nct * nmt;
-    FL_REQUIRE(nblk < (1ull << 31), "mimo: grid too large");
-    dim3 grid((unsigned)nblk);
-    hipStream_t st = (hipStream_t)stream;
-    const cx<T>* h = (const cx<T>*)H;
-    const cx<T>* x = (const cx<T>*)X;
-    cx<T>* y = (cx<T>*)Y;
-#define FL_MIMO_CASE(MT_, BT_, NU_)                                                                                   \
-    if (mt == MT_ && bt == BT_ && nu == NU_) {                                                                        \
-        launch_full_one<T, MT_, BT_, NU_>(grid, nct, nmt, st, h, hs_f, hs_m, hs_n, conj_h, x, xs_b, xs_n, xs_k, y, ys_b, \
-                                          ys_m, ys_k, B, M, No, Ni, K);                                               \
-        FL_CHECK_LAUNCH("mimo_full");                                                                                 \
-        return FL_OK;                                                                                                 \
-    }
-    FL_MIMO_CASE(8, 4, 1) FL_MIMO_CASE(8, 2, 1) FL_MIMO_CASE(8, 1, 1)
-    FL_MIMO_CASE(4, 4, 1) FL_MIMO_CASE(4, 2, 1) FL_MIMO_CASE(4, 1, 1)
-    FL_MIMO_CASE(2, 4, 1) FL_MIMO_CASE(2, 2, 1) FL_MIMO_CASE(2, 1, 1)
-    FL_MIMO_CASE(1, 4, 1) FL_MIMO_CASE(1, 2, 1) FL_MIMO_CASE(1, 1, 1)
-    // tuning variants
-    FL_MIMO_CASE(8, 4, 2) FL_MIMO_CASE(8, 2, 2) FL_MIMO_CASE(8, 2, 4) FL_MIMO_CASE(4, 4, 2) FL_MIMO_CASE(4, 4, 4)
-    FL_MIMO_CASE(4, 8, 1) FL_MIMO_CASE(4, 8, 2) FL_MIMO_CASE(8, 8, 1) FL_MIMO_CASE(4, 2, 4) FL_MIMO_CASE(4, 2, 2)
-#undef FL_MIMO_CASE
-    set_error("mimo: no kernel variant mt=%d bt=%d nu=%d", mt, bt, nu);
-    return FL_ERR_UNSUPPORTED;
-}
-
-template <typename T>
-static int mimo_diag_impl(const void* h, long hs_f, long hs_n, int conj_h, const void* X, long xs_b, long xs_n, long xs_k,
-                          void* Y, long ys_b, long ys_n, long ys_k, int B, int M, int N, int K, void* stream) {
-    FL_REQUIRE(h && X && Y, "mimo_diag: null pointer");
-    FL_REQUIRE(B >= 0 && M >= 0 && N > 0 && K > 0 && N <= 65535, "mimo_diag: bad sizes");
-    if (B == 0 || M == 0) return FL_OK;
-    int gz = B * K;
-    if (gz > 1024) gz = 1024;
-    dim3 grid(cdiv_i(M, 256), N, gz);
-    hipLaunchKernelGGL((mimo_diag_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const cx<T>*)h, hs_f, hs_n, conj_h,
-                       (const cx<T>*)X, xs_b, xs_n, xs_k, (cx<T>*)Y, ys_b, ys_n, ys_k, B, M, N, K);
-    FL_CHECK_LAUNCH("mimo_diag");
-    return FL_OK;
-}
-
-template <typename T>
-static int gradh_impl(const void* G, long gs_b, long gs_m, long gs_k, const void* X, long xs_b, long xs_n, long xs_k,
-                      void* dH, long dh_pitch, double scale, int B, int M, int No, int Ni, int K, void* stream,
-                      const void* dev_scale_ = nullptr) {
-    const T* dev_scale = (const T*)dev_scale_;
-    FL_REQUIRE(G && X && dH, "mimo_gradh: null pointer");
-    FL_REQUIRE(dh_pitch >= M, "mimo_gradh: dh_pitch must be >= M");
-    FL_REQUIRE(B >= 0 && M >= 0 && No > 0 && Ni > 0 && K > 0, "mimo_gradh: bad sizes");
-    if (M == 0) return FL_OK;
-    hipStream_t st = (hipStream_t)stream;
-    if constexpr (sizeof(T) == 4) {
-        if (g_mimo_variant == 0 && !dev_scale && mfma_applies(No, Ni, B * K)) {      // (a device-side factor: the lane kernels)
-            MmaArgs a = {};
-            a.A = (const cx<float>*)G; a.sa_f = 1; a.sa_i = gs_m; a.sa_t1 = gs_b; a.sa_t2 = gs_k; a.conj_a = 0;
-            a.B = (const cx<float>*)X; a.sb_j1 = 0; a.sb_j2 = xs_n; a.sb_t1 = xs_b; a.sb_t2 = xs_k; a.conj_b = 1;
-            a.D = (cx<float>*)dH; a.sd_i = (long)Ni * dh_pitch; a.sd_j1 = 0; a.sd_j2 = dh_pitch; a.scale = (float)scale;
-            a.M = M; a.NI = No; a.J1 = 1; a.J2 = Ni; a.T1 = B; a.T2 = K;
-            return launch_mfma(a, st);
-        }
-    }
-    // Larger register tiles read G and X once per bin instead of once per 4x4 tile (config 2: 326 -> 221 MB of fabric
-    // traffic per launch) -- and measure SLOWER: 4x4 65 us, 8x4 68 us, 8x8 88 us (tools/dbg/archive/gradh_tile.py, cold caches):
-    // the second read of a 4x4 tile comes from the L2, while 64 / 128 accumulator registers cost occupancy.  Kept
-    // behind the tuning hook.
-    if (sizeof(T) == 4 && No >= 8 && Ni >= 8 && g_gradh_tile != 4) {
-        const int tn = g_gradh_tile == 84 ? 4 : 8;
-        dim3 grid(cdiv_i(M, 256), cdiv_i(No, 8), cdiv_i(Ni, tn));
-        FL_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "mimo_gradh: too many channels");
-        if (tn == 8)
-            hipLaunchKernelGGL((mimo_gradh_kernel<T, 8, 8>), grid, dim3(256), 0, st, (const cx<T>*)G, gs_b, gs_m, gs_k,
-                               (const cx<T>*)X, xs_b, xs_n, xs_k, (cx<T>*)dH, dh_pitch, (T)scale, B, M, No, Ni, K, dev_scale);
-        else
-            hipLaunchKernelGGL((mimo_gradh_kernel<T, 8, 4>), grid, dim3(256), 0, st, (const cx<T>*)G, gs_b, gs_m, gs_k,
-                               (const cx<T>*)X, xs_b, xs_n, xs_k, (cx<T>*)dH, dh_pitch, (T)scale, B, M, No, Ni, K, dev_scale);
-    } else if (No >= 4 && Ni >= 4) {
-        dim3 grid(cdiv_i(M, 256), cdiv_i(No, 4), cdiv_i(Ni, 4));
-        FL_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "mimo_gradh: too many channels");
-        hipLaunchKernelGGL((mimo_gradh_kernel<T, 4, 4>), grid, dim3(256), 0, st, (const cx<T>*)G, gs_b, gs_m, gs_k,
-                           (const cx<T>*)X, xs_b, xs_n, xs_k, (cx<T>*)dH, dh_pitch, (T)scale, B, M, No, Ni, K, dev_scale);
-    } else {
-        dim3 grid(cdiv_i(M, 256), No, Ni);
-        FL_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "mimo_gradh: too many channels");
-        hipLaunchKernelGGL((mimo_gradh_kernel<T, 1, 1>), grid, dim3(256), 0, st, (const cx<T>*)G, gs_b, gs_m, gs_k,
-                           (const cx<T>*)X, xs_b, xs_n, xs_k, (cx<T>*)dH, dh_pitch, (T)scale, B, M, No, Ni, K, dev_scale);
-    }
-    FL_CHECK_LAUNCH("mimo_gradh");
-    return FL_OK;
-}
-
-template <typename T>
-static int gradh_diag_impl(const void* G, long gs_b, long gs_n, long gs_k, const void* X, long xs_b, long xs_n,
-                           long xs_k, void* dh, long dh_pitch, int B, int M, int N, int K, void* stream) {
-    FL_REQUIRE(G && X && dh, "mimo_gradh_diag: null pointer");
-    FL_REQUIRE(dh_pitch >= M, "mimo_gradh_diag: dh_pitch must be >= M");
-    FL_REQUIRE(B >= 0 && M >= 0 && N > 0 && K > 0 && N <= 65535, "mimo_gradh_diag: bad sizes");
-    if (M == 0) return FL_OK;
-    dim3 grid(cdiv_i(M, 256), N);
-    hipLaunchKernelGGL((mimo_gradh_diag_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const cx<T>*)G, gs_b, gs_n,
-                       gs_k, (const cx<T>*)X, xs_b, xs_n, xs_k, (cx<T>*)dh, dh_pitch, B, M, N, K);
-    FL_CHECK_LAUNCH("mimo_gradh_diag");
-    return FL_OK;
-}
-
 
 // dW[m,n] = sum_{b,k,f} G[b,m,k,f] conj(X[b,n,k,f]) -- the gradient of a frequency-INDEPENDENT
 // matrix (Gain/Matrix, the FDN mixing matrix) reduced over bins inside the kernel: each block
@@ -760,6 +514,7 @@ __global__ void __launch_bounds__(256) mimo_gradw_final_kernel(const cx<T>* __re
     }
 }
 
+// ---------------------------------------------------------------- host dispatch
 static int g_gradw_cap = 0;
 static int gradw_blocks(int M) {
     int nb = cdiv_i(M, 256);
@@ -769,132 +524,183 @@ static int gradw_blocks(int M) {
     return nb;
 }
 
+}  // namespace fl
+
+using namespace fl;
+
+extern "C" int fl_mimo_gradw_blocks(int M) { return gradw_blocks(M); }
+extern "C" int fl_debug_set_mimo_variant(int variant, int gradw_cap) {
+    FL_REQUIRE(variant == 0 || variant == -1 || variant == -14, "debug_set_mimo_variant: variant %d is not 0, -1 or -14", variant);
+    FL_REQUIRE(gradw_cap >= 0, "debug_set_mimo_variant: gradw_cap %d is negative", gradw_cap);
+    g_mfma_enabled = variant != -1;        // -1: lane-per-bin kernels everywhere
+    g_mfma_tile16 = variant == -14;        // -14: MFMA kernels with the 64-bin 16x16 tile everywhere
+    g_gradw_cap = gradw_cap;
+    return FL_OK;
+}
+
+FL_ENTRY_C64_C128(fl_mimo, (const void* H, long hs_f, long hs_m, long hs_n, int conj_h, const void* X, long xs_b, long xs_n, long xs_k,
+                            void* Y, long ys_b, long ys_m, long ys_k, int B, int M, int No, int Ni, int K, void* stream),
+                  (H, hs_f, hs_m, hs_n, conj_h, X, xs_b, xs_n, xs_k, Y, ys_b, ys_m, ys_k, B, M, No, Ni, K, stream)) {
+    FL_REQUIRE(H && X && Y, "mimo: null pointer");
+    FL_REQUIRE(B >= 0 && M >= 0 && No > 0 && Ni > 0 && K > 0, "mimo: bad sizes");
+    if (B == 0 || M == 0) return FL_OK;
+    const int ncols = B * K;
+    const bool h_real = (conj_h & 2) != 0;
+    FL_REQUIRE(!h_real || hs_f == 0, "mimo: a real matrix must be frequency independent (hs_f = 0)");
+    if constexpr (sizeof(T) == 4) {
+        if (!h_real && mfma_applies(No, ncols, Ni)) {
+            MmaArgs a = {};
+            a.A = (const cx<float>*)H; a.sa_f = hs_f; a.sa_i = hs_m; a.sa_t1 = 0; a.sa_t2 = hs_n; a.conj_a = conj_h;
+            a.B = (const cx<float>*)X; a.sb_j1 = xs_b; a.sb_j2 = xs_k; a.sb_t1 = 0; a.sb_t2 = xs_n; a.conj_b = 0;
+            a.D = (cx<float>*)Y; a.sd_i = ys_m; a.sd_j1 = ys_b; a.sd_j2 = ys_k; a.scale = 1.f;
+            a.M = M; a.NI = No; a.J1 = B; a.J2 = K; a.T1 = 1; a.T2 = Ni;
+            return launch_mfma(a, (hipStream_t)stream);
+        }
+    }
+    // register tile: MT output channels x BT columns; a bin-independent matrix (hs_f = 0) through the HC instantiation
+    const int bt = ncols >= 4 ? 4 : (ncols >= 2 ? 2 : 1);
+    const int mt = No >= 8 ? 8 : (No >= 4 ? 4 : (No >= 2 ? 2 : 1));
+    const int nct = cdiv_i(ncols, bt), nmt = cdiv_i(No, mt);
+    const size_t nblk = (size_t)cdiv_i(cdiv_i(M, 256), 8) * 8 * nct * nmt;
+    FL_REQUIRE(nblk < (1ull << 31), "mimo: grid too large");
+    dispatch<8, 4, 2, 1>(mt, [&](auto MT) {
+        dispatch<4, 2, 1>(bt, [&](auto BT) {
+            dispatch<1, 0>(hs_f == 0, [&](auto HC) {
+                hipLaunchKernelGGL((mimo_full_kernel<T, decltype(MT)::value, decltype(BT)::value, 1, decltype(HC)::value != 0>),
+                                   dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, (const cx<T>*)H, hs_f, hs_m, hs_n, conj_h,
+                                   (const cx<T>*)X, xs_b, xs_n, xs_k, (cx<T>*)Y, ys_b, ys_m, ys_k, B, M, No, Ni, K, nct, nmt);
+            });
+        });
+    });
+    FL_CHECK_LAUNCH("mimo_full");
+    return FL_OK;
+}
+
+FL_ENTRY_C64_C128(fl_mimo_diag, (const void* h, long hs_f, long hs_n, int conj_h, const void* X, long xs_b, long xs_n, long xs_k, void* Y,
+                                 long ys_b, long ys_n, long ys_k, int B, int M, int N, int K, void* stream),
+                  (h, hs_f, hs_n, conj_h, X, xs_b, xs_n, xs_k, Y, ys_b, ys_n, ys_k, B, M, N, K, stream)) {
+    FL_REQUIRE(h && X && Y, "mimo_diag: null pointer");
+    FL_REQUIRE(B >= 0 && M >= 0 && N > 0 && K > 0 && N <= 65535, "mimo_diag: bad sizes");
+    if (B == 0 || M == 0) return FL_OK;
+    int gz = B * K;
+    if (gz > 1024) gz = 1024;
+    dim3 grid(cdiv_i(M, 256), N, gz);
+    hipLaunchKernelGGL((mimo_diag_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const cx<T>*)h, hs_f, hs_n, conj_h,
+                       (const cx<T>*)X, xs_b, xs_n, xs_k, (cx<T>*)Y, ys_b, ys_n, ys_k, B, M, N, K);
+    FL_CHECK_LAUNCH("mimo_diag");
+    return FL_OK;
+}
+
+// dev_scale: null (fl_mimo_gradh_*) or a device scalar multiplied into `scale` by the kernel (fl_mimo_gradh_scaled_*)
+template <typename T>
+static int gradh_impl(const void* G, long gs_b, long gs_m, long gs_k, const void* X, long xs_b, long xs_n, long xs_k,
+                      void* dH, long dh_pitch, double scale, const void* dev_scale, int B, int M, int No, int Ni, int K, void* stream) {
+    FL_REQUIRE(G && X && dH, "mimo_gradh: null pointer");
+    FL_REQUIRE(dh_pitch >= M, "mimo_gradh: dh_pitch must be >= M");
+    FL_REQUIRE(B >= 0 && M >= 0 && No > 0 && Ni > 0 && K > 0, "mimo_gradh: bad sizes");
+    if (M == 0) return FL_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if constexpr (sizeof(T) == 4) {
+        if (!dev_scale && mfma_applies(No, Ni, B * K)) {      // (a device-side factor: the lane kernels)
+            MmaArgs a = {};
+            a.A = (const cx<float>*)G; a.sa_f = 1; a.sa_i = gs_m; a.sa_t1 = gs_b; a.sa_t2 = gs_k; a.conj_a = 0;
+            a.B = (const cx<float>*)X; a.sb_j1 = 0; a.sb_j2 = xs_n; a.sb_t1 = xs_b; a.sb_t2 = xs_k; a.conj_b = 1;
+            a.D = (cx<float>*)dH; a.sd_i = (long)Ni * dh_pitch; a.sd_j1 = 0; a.sd_j2 = dh_pitch; a.scale = (float)scale;
+            a.M = M; a.NI = No; a.J1 = 1; a.J2 = Ni; a.T1 = B; a.T2 = K;
+            return launch_mfma(a, st);
+        }
+    }
+    // 4x4 register tiles (larger ones read G and X less often and measured slower: DESIGN_HISTORY), 1x1 below four channels
+    const int tile = (No >= 4 && Ni >= 4) ? 4 : 1;
+    dim3 grid(cdiv_i(M, 256), cdiv_i(No, tile), cdiv_i(Ni, tile));
+    FL_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "mimo_gradh: too many channels");
+    dispatch<4, 1>(tile, [&](auto TL) {
+        hipLaunchKernelGGL((mimo_gradh_kernel<T, decltype(TL)::value, decltype(TL)::value>), grid, dim3(256), 0, st, (const cx<T>*)G, gs_b,
+                           gs_m, gs_k, (const cx<T>*)X, xs_b, xs_n, xs_k, (cx<T>*)dH, dh_pitch, (T)scale, B, M, No, Ni, K, (const T*)dev_scale);
+    });
+    FL_CHECK_LAUNCH("mimo_gradh");
+    return FL_OK;
+}
+
+FL_ENTRY_C64_C128(fl_mimo_gradh, (const void* G, long gs_b, long gs_m, long gs_k, const void* X, long xs_b, long xs_n, long xs_k, void* dH,
+                                  long dh_pitch, double scale, int B, int M, int No, int Ni, int K, void* stream),
+                  (G, gs_b, gs_m, gs_k, X, xs_b, xs_n, xs_k, dH, dh_pitch, scale, B, M, No, Ni, K, stream)) {
+    return gradh_impl<T>(G, gs_b, gs_m, gs_k, X, xs_b, xs_n, xs_k, dH, dh_pitch, scale, nullptr, B, M, No, Ni, K, stream);
+}
+
+FL_ENTRY_C64_C128(fl_mimo_gradh_scaled, (const void* G, long gs_b, long gs_m, long gs_k, const void* X, long xs_b, long xs_n, long xs_k,
+                                         void* dH, long dh_pitch, double scale, const void* dev_scale, int B, int M, int No, int Ni, int K,
+                                         void* stream),
+                  (G, gs_b, gs_m, gs_k, X, xs_b, xs_n, xs_k, dH, dh_pitch, scale, dev_scale, B, M, No, Ni, K, stream)) {
+    FL_REQUIRE(dev_scale, "mimo_gradh_scaled: null pointer");
+    return gradh_impl<T>(G, gs_b, gs_m, gs_k, X, xs_b, xs_n, xs_k, dH, dh_pitch, scale, dev_scale, B, M, No, Ni, K, stream);
+}
+
+FL_ENTRY_C64_C128(fl_mimo_gradh_diag, (const void* G, long gs_b, long gs_n, long gs_k, const void* X, long xs_b, long xs_n, long xs_k,
+                                       void* dh, long dh_pitch, int B, int M, int N, int K, void* stream),
+                  (G, gs_b, gs_n, gs_k, X, xs_b, xs_n, xs_k, dh, dh_pitch, B, M, N, K, stream)) {
+    FL_REQUIRE(G && X && dh, "mimo_gradh_diag: null pointer");
+    FL_REQUIRE(dh_pitch >= M, "mimo_gradh_diag: dh_pitch must be >= M");
+    FL_REQUIRE(B >= 0 && M >= 0 && N > 0 && K > 0 && N <= 65535, "mimo_gradh_diag: bad sizes");
+    if (M == 0) return FL_OK;
+    dim3 grid(cdiv_i(M, 256), N);
+    hipLaunchKernelGGL((mimo_gradh_diag_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const cx<T>*)G, gs_b, gs_n,
+                       gs_k, (const cx<T>*)X, xs_b, xs_n, xs_k, (cx<T>*)dh, dh_pitch, B, M, N, K);
+    FL_CHECK_LAUNCH("mimo_gradh_diag");
+    return FL_OK;
+}
+
+// real_out: dW is a real (No, Ni) array holding the real part of the sum (fl_mimo_gradw_re_*)
 template <typename T>
 static int gradw_impl(const void* G, long gs_b, long gs_m, long gs_k, const void* X, long xs_b, long xs_n, long xs_k,
-                      void* part, void* dW, int B, int M, int No, int Ni, int K, void* stream, int real_out = 0) {
+                      void* part, void* dW, int B, int M, int No, int Ni, int K, void* stream, int real_out) {
     FL_REQUIRE(G && X && part && dW, "mimo_gradw: null pointer");
     FL_REQUIRE(B >= 0 && M >= 0 && No > 0 && Ni > 0 && K > 0, "mimo_gradw: bad sizes");
-    // 8x8 tiles where the matrix allows: every element of G and X is then read No/8 (Ni/8) times
-    // instead of No/4 -- at N = 32 with matrix-valued signals that is 12 GB instead of 25 GB per launch
+    hipStream_t st = (hipStream_t)stream;
+    int slots = 0;      // partial tiles written per entry of dW
+    bool on_mfma = false;
     if constexpr (sizeof(T) == 4) {
-        if (g_mimo_variant == 0 && mfma_applies(No, Ni, B * K)) {
+        if (mfma_applies(No, Ni, B * K)) {
             // per-bin outer products on the matrix cores, summed over bins in the accumulators (mimo_mfma_lds_kernel)
             MmaArgs a = {};
             a.A = (const cx<float>*)G; a.sa_f = 1; a.sa_i = gs_m; a.sa_t1 = gs_b; a.sa_t2 = gs_k; a.conj_a = 0;
             a.B = (const cx<float>*)X; a.sb_j1 = 0; a.sb_j2 = xs_n; a.sb_t1 = xs_b; a.sb_t2 = xs_k; a.conj_b = 1;
             a.part = (cx<float>*)part; a.scale = 1.f;
             a.M = M; a.NI = No; a.J1 = 1; a.J2 = Ni; a.T1 = B; a.T2 = K;
-            int slots = 0;
-            int rc = launch_mfma(a, (hipStream_t)stream, gradw_blocks(M), &slots);
+            const int rc = launch_mfma(a, st, gradw_blocks(M), &slots);
             if (rc) return rc;
-            hipLaunchKernelGGL((mimo_gradw_final_kernel<T>), dim3(cdiv_i((long)No * Ni, 4)), dim3(256), 0, (hipStream_t)stream,
-                               (const cx<T>*)part, slots, No * Ni, (cx<T>*)dW, real_out);
-            FL_CHECK_LAUNCH("mimo_gradw_final");
-            return FL_OK;
+            on_mfma = true;
         }
     }
-    // (double: 256 accumulator registers -- pays once a bin carries several columns, 3.5 -> 2.2 ms at N = 32 with
-    // matrix-valued signals, 215 -> 160 us at N = 16, batch 8; a single column per bin keeps the 4x4 tile)
-    const bool big = No >= 8 && Ni >= 8 && (sizeof(T) == 4 || (long)B * K >= 4);
-    const int tm = big ? 8 : 4;
-    dim3 grid(gradw_blocks(M), cdiv_i(No, tm), cdiv_i(Ni, tm));
-    FL_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "mimo_gradw: too many channels");
-    if (big)
-        hipLaunchKernelGGL((mimo_gradw_kernel<T, 8, 8>), grid, dim3(256), 0, (hipStream_t)stream, (const cx<T>*)G, gs_b, gs_m,
-                           gs_k, (const cx<T>*)X, xs_b, xs_n, xs_k, (cx<T>*)part, B, M, No, Ni, K);
-    else
-        hipLaunchKernelGGL((mimo_gradw_kernel<T, 4, 4>), grid, dim3(256), 0, (hipStream_t)stream, (const cx<T>*)G, gs_b, gs_m,
-                           gs_k, (const cx<T>*)X, xs_b, xs_n, xs_k, (cx<T>*)part, B, M, No, Ni, K);
-    FL_CHECK_LAUNCH("mimo_gradw");
-    hipLaunchKernelGGL((mimo_gradw_final_kernel<T>), dim3(cdiv_i((long)No * Ni, 4)), dim3(256), 0, (hipStream_t)stream,
-                       (const cx<T>*)part, (int)grid.x, No * Ni, (cx<T>*)dW, real_out);
+    if (!on_mfma) {
+        // 8x8 tiles where the matrix allows: every element of G and X is then read No/8 (Ni/8) times instead of No/4 -- at
+        // N = 32 with matrix-valued signals that is 12 GB instead of 25 GB per launch.  (double: 256 accumulator registers --
+        // pays once a bin carries several columns, 3.5 -> 2.2 ms at N = 32 with matrix-valued signals, 215 -> 160 us at N = 16,
+        // batch 8; a single column per bin keeps the 4x4 tile)
+        const int tm = (No >= 8 && Ni >= 8 && (sizeof(T) == 4 || (long)B * K >= 4)) ? 8 : 4;
+        dim3 grid(gradw_blocks(M), cdiv_i(No, tm), cdiv_i(Ni, tm));
+        FL_REQUIRE(grid.y <= 65535 && grid.z <= 65535, "mimo_gradw: too many channels");
+        dispatch<8, 4>(tm, [&](auto TM) {
+            hipLaunchKernelGGL((mimo_gradw_kernel<T, decltype(TM)::value, decltype(TM)::value>), grid, dim3(256), 0, st, (const cx<T>*)G,
+                               gs_b, gs_m, gs_k, (const cx<T>*)X, xs_b, xs_n, xs_k, (cx<T>*)part, B, M, No, Ni, K);
+        });
+        FL_CHECK_LAUNCH("mimo_gradw");
+        slots = (int)grid.x;
+    }
+    hipLaunchKernelGGL((mimo_gradw_final_kernel<T>), dim3(cdiv_i((long)No * Ni, 4)), dim3(256), 0, st, (const cx<T>*)part, slots,
+                       No * Ni, (cx<T>*)dW, real_out);
     FL_CHECK_LAUNCH("mimo_gradw_final");
     return FL_OK;
 }
 
-}  // namespace fl
-
-using namespace fl;
-
-extern "C" {
-
-int fl_mimo_gradw_blocks(int M) { return gradw_blocks(M); }
-int fl_debug_set_mimo_variant(int variant, int gradw_cap) {
-    g_mfma_enabled = variant != -1;        // -1: lane-per-bin kernels everywhere (default tiles)
-    g_mfma_tile16 = variant == -14;        // -14: MFMA kernels with the 64-bin 16x16 tile everywhere
-    if (variant < 0) variant = 0;
-    g_mimo_variant = variant;
-    g_mfma_vec = gradw_cap != -2;          // gradw_cap -2: direct stores in the MFMA kernels
-    g_mimo_hc = gradw_cap != -4;
-    g_mimo_stream = gradw_cap <= -1600 || gradw_cap == -16;      // -16, or -(1600 + 10*splits + cb)
-    if (gradw_cap <= -1600) {
-        g_mimo_stream_split = ((-gradw_cap - 1600) / 10);
-        g_mimo_stream_cb = (-gradw_cap - 1600) % 10;
-    }
-    g_gradh_tile = gradw_cap == -88 ? 8 : (gradw_cap == -84 ? 84 : 4);
-    if (gradw_cap < 0) gradw_cap = 0;
-    g_gradw_cap = gradw_cap;
-    return FL_OK;
-}
-int fl_mimo_gradw_c64(const void* G, long gs_b, long gs_m, long gs_k, const void* X, long xs_b, long xs_n, long xs_k,
-                      void* part, void* dW, int B, int M, int No, int Ni, int K, void* stream) {
-    return gradw_impl<float>(G, gs_b, gs_m, gs_k, X, xs_b, xs_n, xs_k, part, dW, B, M, No, Ni, K, stream);
-}
-int fl_mimo_gradw_c128(const void* G, long gs_b, long gs_m, long gs_k, const void* X, long xs_b, long xs_n, long xs_k,
-                       void* part, void* dW, int B, int M, int No, int Ni, int K, void* stream) {
-    return gradw_impl<double>(G, gs_b, gs_m, gs_k, X, xs_b, xs_n, xs_k, part, dW, B, M, No, Ni, K, stream);
+FL_ENTRY_C64_C128(fl_mimo_gradw, (const void* G, long gs_b, long gs_m, long gs_k, const void* X, long xs_b, long xs_n, long xs_k,
+                                  void* part, void* dW, int B, int M, int No, int Ni, int K, void* stream),
+                  (G, gs_b, gs_m, gs_k, X, xs_b, xs_n, xs_k, part, dW, B, M, No, Ni, K, stream)) {
+    return gradw_impl<T>(G, gs_b, gs_m, gs_k, X, xs_b, xs_n, xs_k, part, dW, B, M, No, Ni, K, stream, 0);
 }
 
-int fl_mimo_gradw_re_c64(const void* G, long gs_b, long gs_m, long gs_k, const void* X, long xs_b, long xs_n, long xs_k,
-                         void* part, void* dW, int B, int M, int No, int Ni, int K, void* stream) {
-    return gradw_impl<float>(G, gs_b, gs_m, gs_k, X, xs_b, xs_n, xs_k, part, dW, B, M, No, Ni, K, stream, 1);
+FL_ENTRY_C64_C128(fl_mimo_gradw_re, (const void* G, long gs_b, long gs_m, long gs_k, const void* X, long xs_b, long xs_n, long xs_k,
+                                     void* part, void* dW, int B, int M, int No, int Ni, int K, void* stream),
+                  (G, gs_b, gs_m, gs_k, X, xs_b, xs_n, xs_k, part, dW, B, M, No, Ni, K, stream)) {
+    return gradw_impl<T>(G, gs_b, gs_m, gs_k, X, xs_b, xs_n, xs_k, part, dW, B, M, No, Ni, K, stream, 1);
 }
-int fl_mimo_gradw_re_c128(const void* G, long gs_b, long gs_m, long gs_k, const void* X, long xs_b, long xs_n, long xs_k,
-                          void* part, void* dW, int B, int M, int No, int Ni, int K, void* stream) {
-    return gradw_impl<double>(G, gs_b, gs_m, gs_k, X, xs_b, xs_n, xs_k, part, dW, B, M, No, Ni, K, stream, 1);
-}
-
-int fl_mimo_c64(const void* H, long hs_f, long hs_m, long hs_n, int conj_h, const void* X, long xs_b, long xs_n, long xs_k,
-                void* Y, long ys_b, long ys_m, long ys_k, int B, int M, int No, int Ni, int K, void* stream) {
-    return mimo_impl<float>(H, hs_f, hs_m, hs_n, conj_h, X, xs_b, xs_n, xs_k, Y, ys_b, ys_m, ys_k, B, M, No, Ni, K, stream);
-}
-int fl_mimo_c128(const void* H, long hs_f, long hs_m, long hs_n, int conj_h, const void* X, long xs_b, long xs_n, long xs_k,
-                 void* Y, long ys_b, long ys_m, long ys_k, int B, int M, int No, int Ni, int K, void* stream) {
-    return mimo_impl<double>(H, hs_f, hs_m, hs_n, conj_h, X, xs_b, xs_n, xs_k, Y, ys_b, ys_m, ys_k, B, M, No, Ni, K, stream);
-}
-int fl_mimo_diag_c64(const void* h, long hs_f, long hs_n, int conj_h, const void* X, long xs_b, long xs_n, long xs_k,
-                     void* Y, long ys_b, long ys_n, long ys_k, int B, int M, int N, int K, void* stream) {
-    return mimo_diag_impl<float>(h, hs_f, hs_n, conj_h, X, xs_b, xs_n, xs_k, Y, ys_b, ys_n, ys_k, B, M, N, K, stream);
-}
-int fl_mimo_diag_c128(const void* h, long hs_f, long hs_n, int conj_h, const void* X, long xs_b, long xs_n, long xs_k,
-                      void* Y, long ys_b, long ys_n, long ys_k, int B, int M, int N, int K, void* stream) {
-    return mimo_diag_impl<double>(h, hs_f, hs_n, conj_h, X, xs_b, xs_n, xs_k, Y, ys_b, ys_n, ys_k, B, M, N, K, stream);
-}
-int fl_mimo_gradh_c64(const void* G, long gs_b, long gs_m, long gs_k, const void* X, long xs_b, long xs_n, long xs_k,
-                      void* dH, long dh_pitch, double scale, int B, int M, int No, int Ni, int K, void* stream) {
-    return gradh_impl<float>(G, gs_b, gs_m, gs_k, X, xs_b, xs_n, xs_k, dH, dh_pitch, scale, B, M, No, Ni, K, stream);
-}
-int fl_mimo_gradh_c128(const void* G, long gs_b, long gs_m, long gs_k, const void* X, long xs_b, long xs_n, long xs_k,
-                       void* dH, long dh_pitch, double scale, int B, int M, int No, int Ni, int K, void* stream) {
-    return gradh_impl<double>(G, gs_b, gs_m, gs_k, X, xs_b, xs_n, xs_k, dH, dh_pitch, scale, B, M, No, Ni, K, stream);
-}
-int fl_mimo_gradh_scaled_c64(const void* G, long gs_b, long gs_m, long gs_k, const void* X, long xs_b, long xs_n, long xs_k,
-                             void* dH, long dh_pitch, double scale, const void* dev_scale, int B, int M, int No, int Ni, int K, void* stream) {
-    FL_REQUIRE(dev_scale, "mimo_gradh_scaled: null pointer");
-    return gradh_impl<float>(G, gs_b, gs_m, gs_k, X, xs_b, xs_n, xs_k, dH, dh_pitch, scale, B, M, No, Ni, K, stream, dev_scale);
-}
-int fl_mimo_gradh_scaled_c128(const void* G, long gs_b, long gs_m, long gs_k, const void* X, long xs_b, long xs_n, long xs_k,
-                              void* dH, long dh_pitch, double scale, const void* dev_scale, int B, int M, int No, int Ni, int K, void* stream) {
-    FL_REQUIRE(dev_scale, "mimo_gradh_scaled: null pointer");
-    return gradh_impl<double>(G, gs_b, gs_m, gs_k, X, xs_b, xs_n, xs_k, dH, dh_pitch, scale, B, M, No, Ni, K, stream, dev_scale);
-}
-int fl_mimo_gradh_diag_c64(const void* G, long gs_b, long gs_n, long gs_k, const void* X, long xs_b, long xs_n, long xs_k,
-                           void* dh, long dh_pitch, int B, int M, int N, int K, void* stream) {
-    return gradh_diag_impl<float>(G, gs_b, gs_n, gs_k, X, xs_b, xs_n, xs_k, dh, dh_pitch, B, M, N, K, stream);
-}
-int fl_mimo_gradh_diag_c128(const void* G, long gs_b, long gs_n, long gs_k, const void* X, long xs_b, long xs_n, long xs_k,
-                            void* dh, long dh_pitch, int B, int M, int N, int K, void* stream) {
-    return gradh_diag_impl<double>(G, gs_b, gs_n, gs_k, X, xs_b, xs_n, xs_k, dh, dh_pitch, B, M, N, K, stream);
-}
-
-}  // extern "C"

@@ -144,8 +144,8 @@ static int pick_vec(const void* p, const void* q, long cols, long pitch, long ro
     return ok ? 4 : 1;
 }
 
-template <typename T>
-static int mean_square_impl(const void* y, long rows, long cols, long pitch, void* loss, void* scratch, void* stream) {
+FL_ENTRY_F32_F64(fl_mean_square, (const void* y, long rows, long cols, long pitch, void* loss, void* scratch, void* stream),
+                 (y, rows, cols, pitch, loss, scratch, stream)) {
     FL_REQUIRE(y && loss && scratch, "mean_square: null pointer");
     FL_REQUIRE(rows > 0 && cols > 0 && pitch >= cols, "mean_square: bad sizes (rows, cols > 0, pitch >= cols)");
     if (pitch == cols) { cols *= rows; rows = 1; pitch = cols; }
@@ -166,8 +166,8 @@ static int mean_square_impl(const void* y, long rows, long cols, long pitch, voi
     return FL_OK;
 }
 
-template <typename T>
-static int mean_square_bwd_impl(const void* y, const void* gloss, void* gy, long rows, long cols, long pitch, void* stream) {
+FL_ENTRY_F32_F64(fl_mean_square_bwd, (const void* y, const void* gloss, void* gy, long rows, long cols, long pitch, void* stream),
+                 (y, gloss, gy, rows, cols, pitch, stream)) {
     FL_REQUIRE(y && gloss && gy, "mean_square_bwd: null pointer");
     FL_REQUIRE(rows > 0 && cols > 0 && pitch >= cols, "mean_square_bwd: bad sizes");
     const double two_inv = 2.0 / ((double)rows * (double)cols);
@@ -259,8 +259,8 @@ static int mse_blocks(long rows) {
     return (int)(g < 1 ? 1 : g);
 }
 
-template <typename T>
-static int mse_impl(const void* y, const void* t, long rows, int ncols, void* loss, void* scratch, void* stream) {
+FL_ENTRY_F32_F64(fl_mse, (const void* y, const void* t, long rows, int ncols, void* loss, void* scratch, void* stream),
+                 (y, t, rows, ncols, loss, scratch, stream)) {
     FL_REQUIRE(y && t && loss && scratch, "mse: null pointer");
     FL_REQUIRE(rows > 0 && ncols > 0 && ncols <= 4096, "mse: bad sizes");
     const int nblk = mse_blocks(rows);
@@ -281,8 +281,8 @@ static int mse_impl(const void* y, const void* t, long rows, int ncols, void* lo
     return FL_OK;
 }
 
-template <typename T>
-static int mse_bwd_impl(const void* y, const void* t, const void* gloss, void* gy, long rows, int ncols, void* stream) {
+FL_ENTRY_F32_F64(fl_mse_bwd, (const void* y, const void* t, const void* gloss, void* gy, long rows, int ncols, void* stream),
+                 (y, t, gloss, gy, rows, ncols, stream)) {
     FL_REQUIRE(y && t && gloss && gy, "mse_bwd: null pointer");
     FL_REQUIRE(rows > 0 && ncols > 0 && ncols <= 4096, "mse_bwd: bad sizes");
     long g = (rows + 1023) / 1024;      // four rows per lane
@@ -370,16 +370,16 @@ __global__ void __launch_bounds__(256) sparsity_bwd_kernel(const T* __restrict__
     }
 }
 
-template <typename T>
-static int sparsity_impl(const void* A, int C, int N, void* loss, void* stream) {
+FL_ENTRY_F32_F64(fl_sparsity, (const void* A, int C, int N, void* loss, void* stream),
+                 (A, C, N, loss, stream)) {
     FL_REQUIRE(A && loss, "sparsity: null pointer");
     FL_REQUIRE(C >= 1 && N >= 2, "sparsity: at least one matrix of at least 2 x 2");
     hipLaunchKernelGGL((sparsity_kernel<T>), dim3(1), dim3(256), 0, (hipStream_t)stream, (const T*)A, C, N, (T*)loss);
     FL_CHECK_LAUNCH("sparsity");
     return FL_OK;
 }
-template <typename T>
-static int sparsity_bwd_impl(const void* A, const void* gloss, int C, int N, void* gA, void* stream) {
+FL_ENTRY_F32_F64(fl_sparsity_bwd, (const void* A, const void* gloss, int C, int N, void* gA, void* stream),
+                 (A, gloss, C, N, gA, stream)) {
     FL_REQUIRE(A && gloss && gA, "sparsity_bwd: null pointer");
     FL_REQUIRE(C >= 1 && N >= 2, "sparsity_bwd: at least one matrix of at least 2 x 2");
     const size_t n = (size_t)C * N * N;
@@ -423,8 +423,8 @@ static dim3 cabs_grid(long rows, long cols) {
     if (gy < 1) gy = 1;
     return dim3((unsigned)gx, (unsigned)gy);
 }
-template <typename T>
-static int cabs_impl(const void* z, void* out, long rows, long cols, long pitch, long opitch, void* stream) {
+FL_ENTRY_C64_C128(fl_cabs, (const void* z, void* out, long rows, long cols, long pitch, long opitch, void* stream),
+                 (z, out, rows, cols, pitch, opitch, stream)) {
     FL_REQUIRE(z && out, "cabs: null pointer");
     FL_REQUIRE(rows > 0 && cols > 0 && pitch >= cols && opitch >= cols, "cabs: bad sizes");
     hipLaunchKernelGGL((cabs_kernel<T>), cabs_grid(rows, cols), dim3(256), 0, (hipStream_t)stream, (const cx<T>*)z, (T*)out, rows, cols,
@@ -432,8 +432,8 @@ static int cabs_impl(const void* z, void* out, long rows, long cols, long pitch,
     FL_CHECK_LAUNCH("cabs");
     return FL_OK;
 }
-template <typename T>
-static int cabs_bwd_impl(const void* z, const void* g, void* gz, long rows, long cols, long pitch, long gpitch, void* stream) {
+FL_ENTRY_C64_C128(fl_cabs_bwd, (const void* z, const void* g, void* gz, long rows, long cols, long pitch, long gpitch, void* stream),
+                 (z, g, gz, rows, cols, pitch, gpitch, stream)) {
     FL_REQUIRE(z && g && gz, "cabs_bwd: null pointer");
     FL_REQUIRE(rows > 0 && cols > 0 && pitch >= cols && gpitch >= cols, "cabs_bwd: bad sizes");
     hipLaunchKernelGGL((cabs_bwd_kernel<T>), cabs_grid(rows, cols), dim3(256), 0, (hipStream_t)stream, (const cx<T>*)z, (const T*)g,
@@ -446,69 +446,18 @@ static int cabs_bwd_impl(const void* z, const void* g, void* gz, long rows, long
 
 using namespace fl;
 
-extern "C" {
-size_t fl_mean_square_scratch_bytes(void) { return MS_MAX_BLOCKS * sizeof(double); }
-int fl_mean_square_f32(const void* y, long rows, long cols, long pitch, void* loss, void* scratch, void* stream) {
-    return mean_square_impl<float>(y, rows, cols, pitch, loss, scratch, stream);
-}
-int fl_mean_square_f64(const void* y, long rows, long cols, long pitch, void* loss, void* scratch, void* stream) {
-    return mean_square_impl<double>(y, rows, cols, pitch, loss, scratch, stream);
-}
-int fl_mean_square_final_f32(const void* parts, int n_parts, double inv_count, void* loss, void* stream) {
+extern "C" size_t fl_mean_square_scratch_bytes(void) { return MS_MAX_BLOCKS * sizeof(double); }
+FL_ENTRY_F32_F64(fl_mean_square_final, (const void* parts, int n_parts, double inv_count, void* loss, void* stream),
+                 (parts, n_parts, inv_count, loss, stream)) {
     FL_REQUIRE(parts && loss && n_parts > 0, "mean_square_final: bad arguments");
-    hipLaunchKernelGGL((mean_square_final_kernel<float>), dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)parts, n_parts, inv_count, (float*)loss);
+    hipLaunchKernelGGL((mean_square_final_kernel<T>), dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)parts, n_parts, inv_count, (T*)loss);
     FL_CHECK_LAUNCH("mean_square_final");
     return FL_OK;
 }
-int fl_mean_square_final_f64(const void* parts, int n_parts, double inv_count, void* loss, void* stream) {
-    FL_REQUIRE(parts && loss && n_parts > 0, "mean_square_final: bad arguments");
-    hipLaunchKernelGGL((mean_square_final_kernel<double>), dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)parts, n_parts, inv_count, (double*)loss);
-    FL_CHECK_LAUNCH("mean_square_final");
-    return FL_OK;
-}
-int fl_mse_f32(const void* y, const void* t, long rows, int ncols, void* loss, void* scratch, void* stream) {
-    return mse_impl<float>(y, t, rows, ncols, loss, scratch, stream);
-}
-int fl_mse_f64(const void* y, const void* t, long rows, int ncols, void* loss, void* scratch, void* stream) {
-    return mse_impl<double>(y, t, rows, ncols, loss, scratch, stream);
-}
-int fl_mse_bwd_f32(const void* y, const void* t, const void* gloss, void* gy, long rows, int ncols, void* stream) {
-    return mse_bwd_impl<float>(y, t, gloss, gy, rows, ncols, stream);
-}
-int fl_mse_bwd_f64(const void* y, const void* t, const void* gloss, void* gy, long rows, int ncols, void* stream) {
-    return mse_bwd_impl<double>(y, t, gloss, gy, rows, ncols, stream);
-}
-int fl_pack_toggle(const void* table, int count, void* flat0, void* flat1, void* state, void* stream) {
+extern "C" int fl_pack_toggle(const void* table, int count, void* flat0, void* flat1, void* state, void* stream) {
     FL_REQUIRE(table && flat0 && flat1 && state && count > 0 && count <= 65535, "pack_toggle: bad arguments");
     hipLaunchKernelGGL(pack_toggle_kernel, dim3(count), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)table, count,
                        (char*)flat0, (char*)flat1, (int*)state);
     FL_CHECK_LAUNCH("pack_toggle");
     return FL_OK;
-}
-int fl_mean_square_bwd_f32(const void* y, const void* gloss, void* gy, long rows, long cols, long pitch, void* stream) {
-    return mean_square_bwd_impl<float>(y, gloss, gy, rows, cols, pitch, stream);
-}
-int fl_mean_square_bwd_f64(const void* y, const void* gloss, void* gy, long rows, long cols, long pitch, void* stream) {
-    return mean_square_bwd_impl<double>(y, gloss, gy, rows, cols, pitch, stream);
-}
-int fl_sparsity_f32(const void* A, int C, int N, void* loss, void* stream) { return sparsity_impl<float>(A, C, N, loss, stream); }
-int fl_sparsity_f64(const void* A, int C, int N, void* loss, void* stream) { return sparsity_impl<double>(A, C, N, loss, stream); }
-int fl_sparsity_bwd_f32(const void* A, const void* gloss, int C, int N, void* gA, void* stream) {
-    return sparsity_bwd_impl<float>(A, gloss, C, N, gA, stream);
-}
-int fl_sparsity_bwd_f64(const void* A, const void* gloss, int C, int N, void* gA, void* stream) {
-    return sparsity_bwd_impl<double>(A, gloss, C, N, gA, stream);
-}
-int fl_cabs_c64(const void* z, void* out, long rows, long cols, long pitch, long opitch, void* stream) {
-    return cabs_impl<float>(z, out, rows, cols, pitch, opitch, stream);
-}
-int fl_cabs_c128(const void* z, void* out, long rows, long cols, long pitch, long opitch, void* stream) {
-    return cabs_impl<double>(z, out, rows, cols, pitch, opitch, stream);
-}
-int fl_cabs_bwd_c64(const void* z, const void* g, void* gz, long rows, long cols, long pitch, long gpitch, void* stream) {
-    return cabs_bwd_impl<float>(z, g, gz, rows, cols, pitch, gpitch, stream);
-}
-int fl_cabs_bwd_c128(const void* z, const void* g, void* gz, long rows, long cols, long pitch, long gpitch, void* stream) {
-    return cabs_bwd_impl<double>(z, g, gz, rows, cols, pitch, gpitch, stream);
-}
 }

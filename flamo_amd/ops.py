@@ -500,24 +500,24 @@ _NORM_FWD = {"backward": lambda n: 1.0, "ortho": lambda n: 1.0 / math.sqrt(n), "
 _NORM_INV = {"backward": lambda n: 1.0 / n, "ortho": lambda n: 1.0 / math.sqrt(n), "forward": lambda n: 1.0}
 
 
+def _fft_call(name, real, dev, nsig, nfft, io, scale, env_log2, interior):
+    """The layered transform entry fl_``name``_f32 / _f64 on ``nsig`` signals: fn(*io, scratch, twiddles, nsig, nfft, scale,
+    env_log2, interior, stream) with the scratch rows the plan asks for; ``io``: the entry's own source / destination arguments."""
+    n_scr = _lib.lib().fl_fft_scratch_elems(nfft, int(real == torch.float64), nsig)
+    scratch = torch.empty(max(n_scr, 1), dtype=_cdtype(real), device=dev)
+    _lib.check(_fn("fl_" + name, real)(*io, scratch.data_ptr(), twiddles(nfft, real, dev).data_ptr(), nsig, nfft, scale, env_log2,
+                                       interior, _stream()), name)
+
+
 def _rfft_launch(xp: torch.Tensor, t_in: int, nfft: int, scale: float, env_log2: float, interior_x2: int):
     """xp: signal-planar real, logical (B, T, rest...), memory (B, rest..., pitch).  Returns planar X."""
     real = _rdtype(xp)
-    dev = xp.device
     B = xp.shape[0]
     rest = tuple(xp.shape[2:])
-    nsig = B * _prod(rest)
     M = nfft // 2 + 1
-    x_pitch = _lead_pitch(xp.movedim(1, -1))
-    X = _empty_rows((B, *rest), M, _cdtype(real), dev)
-    L = _lib.lib()
-    f64 = int(real == torch.float64)
-    n_scr = L.fl_fft_scratch_elems(nfft, f64, nsig)
-    scratch = torch.empty(max(n_scr, 1), dtype=_cdtype(real), device=dev)
-    fn = _fn("fl_rfft", real)
-    _lib.check(fn(xp.data_ptr(), x_pitch, t_in, X.data_ptr(), _pitch(M),
-                  scratch.data_ptr(), twiddles(nfft, real, dev).data_ptr(), nsig, nfft, scale, env_log2, interior_x2,
-                  _stream()), "rfft")
+    X = _empty_rows((B, *rest), M, _cdtype(real), xp.device)
+    io = (xp.data_ptr(), _lead_pitch(xp.movedim(1, -1)), t_in, X.data_ptr(), _pitch(M))
+    _fft_call("rfft", real, xp.device, B * _prod(rest), nfft, io, scale, env_log2, interior_x2)
     return X.movedim(-1, 1)
 
 
@@ -531,20 +531,13 @@ CI_MAX_CHANNELS = 0
 def _rfft_launch_ci(x: torch.Tensor, nfft: int, scale: float, env_log2: float, interior_x2: int):
     """x: contiguous channel-innermost real (B, T, rest...).  Returns planar X (B, M, rest...)."""
     real = _rdtype(x)
-    dev = x.device
     B, T = x.shape[0], x.shape[1]
     rest = tuple(x.shape[2:])
     C_ = _prod(rest)
-    nsig = B * C_
     M = nfft // 2 + 1
-    X = _empty_rows((B, *rest), M, _cdtype(real), dev)
-    L = _lib.lib()
-    f64 = int(real == torch.float64)
-    n_scr = L.fl_fft_scratch_elems(nfft, f64, nsig)
-    scratch = torch.empty(max(n_scr, 1), dtype=_cdtype(real), device=dev)
-    fn = _fn("fl_rfft_ci", real)
-    _lib.check(fn(x.data_ptr(), C_, T, X.data_ptr(), _pitch(M), scratch.data_ptr(),
-                  twiddles(nfft, real, dev).data_ptr(), nsig, nfft, scale, env_log2, interior_x2, _stream()), "rfft_ci")
+    X = _empty_rows((B, *rest), M, _cdtype(real), x.device)
+    io = (x.data_ptr(), C_, T, X.data_ptr(), _pitch(M))
+    _fft_call("rfft_ci", real, x.device, B * C_, nfft, io, scale, env_log2, interior_x2)
     return X.movedim(-1, 1)
 
 
@@ -561,20 +554,12 @@ def _irfft_launch(Xp: torch.Tensor, nfft: int, t_out: int, t_alloc: int, scale: 
                   interior_half: int):
     """Xp: bin-planar complex (B, M, rest...).  Returns signal-planar real (B, t_alloc, rest...)."""
     real = _rdtype(Xp)
-    dev = Xp.device
     B = Xp.shape[0]
     rest = tuple(Xp.shape[2:])
-    nsig = B * _prod(rest)
-    X_pitch = _lead_pitch(Xp.movedim(1, -1))
     alloc = torch.zeros if t_alloc > t_out else torch.empty
-    y = alloc((B, *rest, t_alloc), dtype=real, device=dev)
-    L = _lib.lib()
-    f64 = int(real == torch.float64)
-    n_scr = L.fl_fft_scratch_elems(nfft, f64, nsig)
-    scratch = torch.empty(max(n_scr, 1), dtype=_cdtype(real), device=dev)
-    fn = _fn("fl_irfft", real)
-    _lib.check(fn(Xp.data_ptr(), X_pitch, y.data_ptr(), t_alloc, t_out, scratch.data_ptr(),
-                  twiddles(nfft, real, dev).data_ptr(), nsig, nfft, scale, env_log2, interior_half, _stream()), "irfft")
+    y = alloc((B, *rest, t_alloc), dtype=real, device=Xp.device)
+    io = (Xp.data_ptr(), _lead_pitch(Xp.movedim(1, -1)), y.data_ptr(), t_alloc, t_out)
+    _fft_call("irfft", real, Xp.device, B * _prod(rest), nfft, io, scale, env_log2, interior_half)
     return y.movedim(-1, 1)
 
 
@@ -1242,6 +1227,9 @@ def spectral_apply(x: torch.Tensor, Hrm: torch.Tensor, nfft: int, norm_f: str = 
 
 
 # ----------------------------------------------------------------------------- per-bin MIMO product
+# ---- one layer over the fl_mimo_* entries, each called from ONE place: _mimo_launch (fl_mimo_* for a per-bin, a constant and a
+# ---- real constant matrix operand; fl_mimo_diag_* for the diagonal patterns), _gradh_launch (fl_mimo_gradh_* / _gradh_scaled_*,
+# ---- fl_mimo_gradh_diag_*) and _gradw_launch (fl_mimo_gradw_* / _gradw_re_*); one autograd node, _Mimo, over the three
 def _h_planar(H: torch.Tensor, per_bin: bool) -> torch.Tensor:
     """Per-bin responses (M, ...) are used with the bin axis contiguous (rows possibly padded)."""
     if not per_bin:
@@ -1256,7 +1244,9 @@ def _h_planar(H: torch.Tensor, per_bin: bool) -> torch.Tensor:
 
 
 def _mimo_launch(H, per_bin, diag, conj_t, X):
-    """Y = op(H) X.  conj_t: use H^H (swap m/n, conjugate)."""
+    """Y = op(H) X.  conj_t: use H^H (swap m/n, conjugate).  A REAL frequency-independent (No, Ni) matrix of X's precision is
+    applied as it is (flag bit 1, strides in real elements): einsum("mn,bfn...->bfm...", to_complex(W), X) of dsp.py:466-468
+    without forming to_complex(W)."""
     real = _rdtype(X)
     B, M, Nx, K, xs_b, xs_n, xs_k = _bnk(X)
     hp = _lead_pitch(H.movedim(0, -1)) if per_bin else 0   # pitch of the per-bin response rows
@@ -1269,21 +1259,21 @@ def _mimo_launch(H, per_bin, diag, conj_t, X):
         _lib.check(fn(H.data_ptr(), hs_f, hs_n, int(conj_t), X.data_ptr(), xs_b, xs_n, xs_k, Y.data_ptr(), ys_b, ys_n,
                       ys_k, B, M, N, K, _stream()), "mimo_diag")
         return Y
-    No_h, Ni_h = H.shape[-2], H.shape[-1]
+    # the matrix operand: strides, sizes, flag bits and span tag
+    No, Ni = H.shape[-2], H.shape[-1]
     if per_bin:
-        hs_f, hs_m, hs_n = 1, Ni_h * hp, hp
+        hs_f, hs_m, hs_n, flags, kind = 1, Ni * hp, hp, int(conj_t), "mimo_bin"
+    elif H.is_complex():
+        hs_f, hs_m, hs_n, flags, kind = 0, H.stride(-2), H.stride(-1), int(conj_t), "mimo_const"
     else:
-        hs_f, hs_m, hs_n = 0, H.stride(-2), H.stride(-1)
+        hs_f, hs_m, hs_n, flags, kind = 0, H.stride(-2), H.stride(-1), 2, "mimo_const_real"
     if conj_t:
-        No, Ni, hs_m, hs_n = Ni_h, No_h, hs_n, hs_m
-    else:
-        No, Ni = No_h, Ni_h
+        No, Ni, hs_m, hs_n = Ni, No, hs_n, hs_m
     Y = _empty_planar((B, M, No, *X.shape[3:]), X.dtype, X.device)
     _, _, _, _, ys_b, ys_m, ys_k = _bnk(Y)
     fn = _fn("fl_mimo", real, True)
-    tag = ("mimo_bin" if per_bin else "mimo_const") + ("_adj" if conj_t else "_fwd") + f"[cols={B * K},{No}x{Ni}]"
-    with kernel_timer.span(tag):
-        _lib.check(fn(H.data_ptr(), hs_f, hs_m, hs_n, int(conj_t), X.data_ptr(), xs_b, xs_n, xs_k, Y.data_ptr(), ys_b,
+    with kernel_timer.span(kind + ("_adj" if conj_t else "_fwd") + f"[cols={B * K},{No}x{Ni}]"):
+        _lib.check(fn(H.data_ptr(), hs_f, hs_m, hs_n, flags, X.data_ptr(), xs_b, xs_n, xs_k, Y.data_ptr(), ys_b,
                       ys_m, ys_k, B, M, No, Ni, K, _stream()), "mimo")
     return Y
 
@@ -1301,39 +1291,47 @@ def _gradh_launch(G, X, diag, scale=1.0, dev_scale=None):
         _lib.check(fn(G.data_ptr(), gs_b, gs_m, gs_k, X.data_ptr(), xs_b, xs_n, xs_k, dh.data_ptr(), P, B, M, Ni, K,
                       _stream()), "mimo_gradh_diag")
         return dh if scale == 1.0 else dh * scale
+    if dev_scale is None:
+        name, factor = "mimo_gradh", (float(scale),)
+    else:
+        if dev_scale.dtype != real or not dev_scale.is_cuda or dev_scale.numel() != 1:
+            raise ValueError("mimo_gradh: dev_scale must be one device scalar of the signal's real dtype")
+        name, factor = "mimo_gradh_scaled", (float(scale), dev_scale.data_ptr())
     dH = _empty_rows((No, Ni), M, X.dtype, X.device)
-    fn = _fn("fl_mimo_gradh", real, True)
+    fn = _fn("fl_" + name, real, True)
     with kernel_timer.span(f"mimo_gradh[cols={B * K},{No}x{Ni}]"):
-        if dev_scale is not None:
-            if dev_scale.dtype != real or not dev_scale.is_cuda or dev_scale.numel() != 1:
-                raise ValueError("mimo_gradh: dev_scale must be one device scalar of the signal's real dtype")
-            fn = _fn("fl_mimo_gradh_scaled", real, True)
-            _lib.check(fn(G.data_ptr(), gs_b, gs_m, gs_k, X.data_ptr(), xs_b, xs_n, xs_k, dH.data_ptr(), P, float(scale),
-                          dev_scale.data_ptr(), B, M, No, Ni, K, _stream()), "mimo_gradh_scaled")
-        else:
-            _lib.check(fn(G.data_ptr(), gs_b, gs_m, gs_k, X.data_ptr(), xs_b, xs_n, xs_k, dH.data_ptr(), P, float(scale), B, M,
-                          No, Ni, K, _stream()), "mimo_gradh")
+        _lib.check(fn(G.data_ptr(), gs_b, gs_m, gs_k, X.data_ptr(), xs_b, xs_n, xs_k, dH.data_ptr(), P, *factor, B, M, No, Ni, K,
+                      _stream()), name)
     return dH
 
 
-def _gradw_launch(G, X):
+def _gradw_launch(G, X, real_out=False):
     """sum over batch, trailing dims AND bins of G x conj(X): (No, Ni) -- gradient of a
-    frequency-independent matrix, reduced in the kernel."""
+    frequency-independent matrix, reduced in the kernel.  real_out: the real part as a real array (the gradient of a real
+    matrix whose complex cast was never formed)."""
     real = _rdtype(X)
     B, M, Ni, K, xs_b, xs_n, xs_k = _bnk(X)
     _, _, No, _, gs_b, gs_m, gs_k = _bnk(G)
     L = _lib.lib()
     nblk = L.fl_mimo_gradw_blocks(M)
     part = torch.empty((nblk, No, Ni), dtype=X.dtype, device=X.device)
-    dW = torch.empty((No, Ni), dtype=X.dtype, device=X.device)
-    fn = _fn("fl_mimo_gradw", real, True)
+    dW = torch.empty((No, Ni), dtype=real if real_out else X.dtype, device=X.device)
+    fn = _fn("fl_mimo_gradw_re" if real_out else "fl_mimo_gradw", real, True)
     with kernel_timer.span(f"mimo_gradw[cols={B * K},{No}x{Ni}]"):
         _lib.check(fn(G.data_ptr(), gs_b, gs_m, gs_k, X.data_ptr(), xs_b, xs_n, xs_k, part.data_ptr(), dW.data_ptr(), B, M, No, Ni,
                       K, _stream()), "mimo_gradw")
     return dW
 
 
+# A real frequency-independent matrix (Gain, Matrix) is applied as it is (fl_mimo_* with conj_h bit 1, real gradient from
+# fl_mimo_gradw_re_*): the real -> complex cast of the reference (dsp.py:466-468) and its backward are three tiny launches
+# per module and step, which at batch 1 is what a feedback delay network's input and output gains cost.  False = cast.
+REAL_CONST_MIMO = True
+
+
 class _Mimo(torch.autograd.Function):
+    """Y = H X for the operand kinds of _mimo_launch; ctx.cfg = (per_bin, diag, real_const)."""
+
     @staticmethod
     def forward(ctx, H, X, diag):
         _require_gpu(H, X)
@@ -1347,16 +1345,17 @@ class _Mimo(torch.autograd.Function):
             raise ValueError(f"response has {H.shape[0]} bins, signal has {M}")
         if H.shape[-1] != X.shape[2]:
             raise ValueError(f"response expects {H.shape[-1]} input channels, signal has {X.shape[2]}")
-        Hp = _h_planar(H.resolve_conj(), per_bin)
+        real_const = not H.is_complex()      # (mimo() routes a real matrix here only where _real_const_applies)
+        Hp = H if real_const else _h_planar(H.resolve_conj(), per_bin)
         Xp = to_planar(X.resolve_conj())
         ctx.save_for_backward(Hp, Xp)
-        ctx.cfg = (per_bin, bool(diag))
+        ctx.cfg = (per_bin, bool(diag), real_const)
         return _mimo_launch(Hp, per_bin, diag, False, Xp)
 
     @staticmethod
     def backward(ctx, gY):
         Hp, Xp = ctx.saved_tensors
-        per_bin, diag = ctx.cfg
+        per_bin, diag, real_const = ctx.cfg
         gY = to_planar(gY.resolve_conj())
         gH = gX = None
         if ctx.needs_input_grad[1]:
@@ -1366,63 +1365,8 @@ class _Mimo(torch.autograd.Function):
                 g = _gradh_launch(gY, Xp, diag)  # planar (.., M)
                 gH = g.movedim(-1, 0) if per_bin else g.sum(dim=-1)
             else:
-                gH = _gradw_launch(gY, Xp)       # frequency-independent matrix: reduced over bins in-kernel
+                gH = _gradw_launch(gY, Xp, real_const)       # frequency-independent matrix: reduced over bins in-kernel
         return gH, gX, None
-
-
-# A real frequency-independent matrix (Gain, Matrix) is applied as it is (fl_mimo_* with conj_h bit 1, real gradient from
-# fl_mimo_gradw_re_*): the real -> complex cast of the reference (dsp.py:466-468) and its backward are three tiny launches
-# per module and step, which at batch 1 is what a feedback delay network's input and output gains cost.  False = cast.
-REAL_CONST_MIMO = True
-
-
-def _mimo_real_launch(W, conj_t, X):
-    """Y = W X or W^T X for a real (No, Ni) matrix W of X's precision: einsum("mn,bfn...->bfm...", to_complex(W), X) of
-    dsp.py:466-468 without forming to_complex(W)."""
-    real = _rdtype(X)
-    B, M, Nx, K, xs_b, xs_n, xs_k = _bnk(X)
-    hs_m, hs_n = W.stride(0), W.stride(1)
-    No, Ni = W.shape
-    if conj_t:
-        No, Ni, hs_m, hs_n = Ni, No, hs_n, hs_m
-    if Ni != Nx:
-        raise ValueError(f"response expects {Ni} input channels, signal has {Nx}")
-    Y = _empty_planar((B, M, No, *X.shape[3:]), X.dtype, X.device)
-    _, _, _, _, ys_b, ys_m, ys_k = _bnk(Y)
-    fn = _fn("fl_mimo", real, True)
-    with kernel_timer.span("mimo_const_real" + ("_adj" if conj_t else "_fwd") + f"[cols={B * K},{No}x{Ni}]"):
-        _lib.check(fn(W.data_ptr(), 0, hs_m, hs_n, 2, X.data_ptr(), xs_b, xs_n, xs_k, Y.data_ptr(), ys_b, ys_m, ys_k, B, M, No, Ni,
-                      K, _stream()), "mimo")
-    return Y
-
-
-class _MimoRealConst(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, W, X):
-        _require_gpu(W, X)
-        Xp = to_planar(X.resolve_conj())
-        ctx.save_for_backward(W, Xp)
-        return _mimo_real_launch(W, False, Xp)
-
-    @staticmethod
-    def backward(ctx, gY):
-        W, Xp = ctx.saved_tensors
-        gY = to_planar(gY.resolve_conj())
-        gW = gX = None
-        if ctx.needs_input_grad[1]:
-            gX = _mimo_real_launch(W, True, gY)
-        if ctx.needs_input_grad[0]:
-            real = _rdtype(Xp)
-            B, M, Ni, K, xs_b, xs_n, xs_k = _bnk(Xp)
-            _, _, No, _, gs_b, gs_m, gs_k = _bnk(gY)
-            L = _lib.lib()
-            part = torch.empty((L.fl_mimo_gradw_blocks(M), No, Ni), dtype=Xp.dtype, device=Xp.device)
-            gW = torch.empty((No, Ni), dtype=real, device=Xp.device)
-            fn = _fn("fl_mimo_gradw_re", real, True)
-            with kernel_timer.span(f"mimo_gradw[cols={B * K},{No}x{Ni}]"):
-                _lib.check(fn(gY.data_ptr(), gs_b, gs_m, gs_k, Xp.data_ptr(), xs_b, xs_n, xs_k, part.data_ptr(), gW.data_ptr(), B, M,
-                              No, Ni, K, _stream()), "mimo_gradw")
-        return gW, gX
 
 
 def _real_const_applies(H, X, diag) -> bool:
@@ -1441,11 +1385,7 @@ def mimo(H: torch.Tensor, X: torch.Tensor, diag: bool = False) -> torch.Tensor:
     ``diag=True``.  ``X``: (B, M, Ni, ...).  Implements the four flamo einsum patterns
     "fmn,bfn...->bfm...", "mn,bfn...->bfm...", "fn,bfn...->bfn...", "n,bfn...->bfn...".
     A real frequency-independent ``H`` is accepted as it is (no complex cast is formed for small matrices)."""
-    if _real_const_applies(H, X, diag):
-        if H.shape[-1] != X.shape[2]:
-            raise ValueError(f"response expects {H.shape[-1]} input channels, signal has {X.shape[2]}")
-        return _MimoRealConst.apply(H, X)
-    if H.dtype != X.dtype:
+    if H.dtype != X.dtype and not _real_const_applies(H, X, diag):
         H = H.to(X.dtype)  # differentiable cast (real -> complex, or precision)
     return _Mimo.apply(H, X, bool(diag))
 
@@ -1672,8 +1612,6 @@ def solve_dud2(l: Optional[torch.Tensor], l2: torch.Tensor, U: torch.Tensor, r: 
 
 def _apply_const(W, transpose, X):
     """W X or W^T X (W^H for a complex W) for a frequency-independent (No, Ni) matrix, real or complex"""
-    if not W.is_complex():
-        return _mimo_real_launch(W, transpose, X)
     return _mimo_launch(W, False, False, transpose, X)
 
 
@@ -2578,6 +2516,16 @@ def _rows_of(y: torch.Tensor):
     return yc, 1, yc.numel(), yc.numel()
 
 
+def _scalar_loss(real: torch.dtype, dev: torch.device) -> torch.Tensor:
+    """the 0-dim tensor a scalar-loss kernel writes"""
+    return torch.empty((), dtype=real, device=dev)
+
+
+def _gloss_as(gloss: torch.Tensor, real: torch.dtype) -> torch.Tensor:
+    """the loss's cotangent as the one device scalar of the data's precision the backward kernels read"""
+    return gloss.to(real).contiguous()
+
+
 class _MeanSquare(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y):
@@ -2587,7 +2535,7 @@ class _MeanSquare(torch.autograd.Function):
         if y.numel() == 0:
             raise ValueError("mean_square of an empty tensor")
         ym, rows, cols, pitch = _rows_of(y)
-        loss = torch.empty((), dtype=y.dtype, device=dev)
+        loss = _scalar_loss(y.dtype, dev)
         fn = _fn("fl_mean_square", y.dtype)
         with kernel_timer.span("mean_square"):
             _lib.check(fn(ym.data_ptr(), rows, cols, pitch, loss.data_ptr(), _ms_scratch_for(dev).data_ptr(), _stream()),
@@ -2601,7 +2549,7 @@ class _MeanSquare(torch.autograd.Function):
         (ym,) = ctx.saved_tensors
         rows, cols, pitch = ctx.layout
         gy = torch.empty_strided(ym.shape, ym.stride(), dtype=ym.dtype, device=ym.device)
-        g = gloss.to(ym.dtype).contiguous()
+        g = _gloss_as(gloss, ym.dtype)
         fn = _fn("fl_mean_square_bwd", ym.dtype)
         with kernel_timer.span("mean_square_bwd"):
             _lib.check(fn(ym.data_ptr(), g.data_ptr(), gy.data_ptr(), rows, cols, pitch, _stream()), "mean_square_bwd")
@@ -2610,7 +2558,7 @@ class _MeanSquare(torch.autograd.Function):
 
 def _mean_square_final(parts, n, real, dev):
     """mean of n squares from the partial sums an inverse column pass left behind (fixed order: fl_mean_square_final_*)"""
-    loss = torch.empty((), dtype=real, device=dev)
+    loss = _scalar_loss(real, dev)
     fn = _fn("fl_mean_square_final", real)
     with kernel_timer.span("mean_square_final"):
         _lib.check(fn(parts.data_ptr(), parts.numel(), 1.0 / n, loss.data_ptr(), _stream()), "mean_square_final")
@@ -2632,16 +2580,19 @@ class _CAbs(torch.autograd.Function):
     """|z| of a complex tensor in one launch each way; the result has z's memory order (a bin-planar view stays one)"""
 
     @staticmethod
+    def _same_order(zm, dtype):
+        """uninitialised, zm's shape and memory order: contiguous where zm is, else a planar view's rows `pitch` apart"""
+        if zm.is_contiguous():
+            return torch.empty(zm.shape, dtype=dtype, device=zm.device)
+        return torch.empty_strided(zm.shape, zm.stride(), dtype=dtype, device=zm.device)
+
+    @staticmethod
     def forward(ctx, z):
-        dev = _require_gpu(z)
+        _require_gpu(z)
         z = z.resolve_conj()        # a lazily conjugated view: the kernels read the storage (the backward would return conj's gradient)
         zm, rows, cols, pitch = _rows_of(z)
         real = _rdtype(zm)
-        if zm.is_contiguous():
-            out = torch.empty(zm.shape, dtype=real, device=dev)
-        else:
-            mem = zm.movedim(1, -1)
-            out = torch.empty_strided(mem.shape, mem.stride(), dtype=real, device=dev).movedim(-1, 1)
+        out = _CAbs._same_order(zm, real)
         fn = _fn("fl_cabs", real, True)
         _lib.check(fn(zm.data_ptr(), out.data_ptr(), rows, cols, pitch, pitch, _stream()), "cabs")
         ctx.save_for_backward(zm)
@@ -2652,22 +2603,12 @@ class _CAbs(torch.autograd.Function):
     def backward(ctx, g):
         (zm,) = ctx.saved_tensors
         rows, cols, pitch = ctx.layout
-        # the cotangent in the output's own memory order (same strides: rows `pitch` apart), else through a copy of that shape
-        if zm.is_contiguous():
-            gm = g.contiguous()
-            gpitch = pitch
-        else:
-            mem = zm.movedim(1, -1)
-            gv = g.movedim(1, -1)
-            if tuple(gv.stride()) == tuple(mem.stride()):
-                gm = g
-            else:
-                gm = torch.empty_strided(mem.shape, mem.stride(), dtype=g.dtype, device=g.device).movedim(-1, 1)
-                gm.copy_(g)
-            gpitch = pitch
-        gz = torch.empty_strided(zm.shape, zm.stride(), dtype=zm.dtype, device=zm.device)
+        # the cotangent in the output's own memory order (same strides: rows `pitch` apart), else through a copy of that order
+        same = g.is_contiguous() if zm.is_contiguous() else tuple(g.stride()) == tuple(zm.stride())
+        gm = g if same else _CAbs._same_order(zm, g.dtype).copy_(g)
+        gz = torch.empty_strided(zm.shape, zm.stride(), dtype=zm.dtype, device=zm.device)      # (zm's strides also where a size is 1)
         fn = _fn("fl_cabs_bwd", _rdtype(zm), True)
-        _lib.check(fn(zm.data_ptr(), gm.data_ptr(), gz.data_ptr(), rows, cols, pitch, gpitch, _stream()), "cabs_bwd")
+        _lib.check(fn(zm.data_ptr(), gm.data_ptr(), gz.data_ptr(), rows, cols, pitch, pitch, _stream()), "cabs_bwd")
         return gz
 
 
@@ -2687,7 +2628,7 @@ class _Sparsity(torch.autograd.Function):
         dev = _require_gpu(A)
         Ac = A.contiguous()
         C, N = (1 if Ac.dim() == 2 else Ac.shape[0]), Ac.shape[-1]
-        loss = torch.empty((), dtype=A.dtype, device=dev)
+        loss = _scalar_loss(A.dtype, dev)
         fn = _fn("fl_sparsity", A.dtype)
         _lib.check(fn(Ac.data_ptr(), C, N, loss.data_ptr(), _stream()), "sparsity")
         ctx.save_for_backward(Ac)
@@ -2699,7 +2640,7 @@ class _Sparsity(torch.autograd.Function):
         (Ac,) = ctx.saved_tensors
         C, N = ctx.cn
         gA = torch.empty_like(Ac)
-        g = gloss.to(Ac.dtype).contiguous()
+        g = _gloss_as(gloss, Ac.dtype)
         fn = _fn("fl_sparsity_bwd", Ac.dtype)
         _lib.check(fn(Ac.data_ptr(), g.data_ptr(), C, N, gA.data_ptr(), _stream()), "sparsity_bwd")
         return gA
@@ -2721,7 +2662,7 @@ class _MSE(torch.autograd.Function):
         dev = _require_gpu(y, t)
         yc, tc = y.contiguous(), t.contiguous()
         rows = yc.numel() // ncols
-        loss = torch.empty((), dtype=y.dtype, device=dev)
+        loss = _scalar_loss(y.dtype, dev)
         fn = _fn("fl_mse", y.dtype)
         with kernel_timer.span("mse"):
             _lib.check(fn(yc.data_ptr(), tc.data_ptr(), rows, ncols, loss.data_ptr(), _ms_scratch_for(dev).data_ptr(), _stream()), "mse")
@@ -2734,7 +2675,7 @@ class _MSE(torch.autograd.Function):
         yc, tc = ctx.saved_tensors
         rows, ncols, shape = ctx.cfg
         gy = torch.empty_like(yc)
-        g = gloss.to(yc.dtype).contiguous()
+        g = _gloss_as(gloss, yc.dtype)
         fn = _fn("fl_mse_bwd", yc.dtype)
         with kernel_timer.span("mse_bwd"):
             _lib.check(fn(yc.data_ptr(), tc.data_ptr(), g.data_ptr(), gy.data_ptr(), rows, ncols, _stream()), "mse_bwd")
@@ -2790,43 +2731,52 @@ FUSE_OBJECTIVE = True      # mean_square(spectral_apply(...)) as one node (see _
 EXPM_MAX_N = 64
 
 
+def _expm_forward(X, skew, want_real, want_cplx):
+    """exp of one square parameter matrix as the real matrix E, the complex matrix (re, 0) Ec, or both from one launch
+    (fl_matrix_exp_* / _cplx_* / _both_*) -> (E | None, Ec | None, stash, cfg); stash and cfg are what _expm_backward takes."""
+    dev = _require_gpu(X)
+    form = "_both" if want_real and want_cplx else ("_cplx" if want_cplx else "")
+    square, known = X.dim() == 2 and X.shape[0] == X.shape[1], X.dtype in (torch.float32, torch.float64)
+    if form == "_both" and not (square and known):
+        raise ValueError("matrix_exp expects one square float32 / float64 matrix")
+    if not square:
+        raise ValueError("matrix_exp expects one square matrix")
+    if not known:
+        raise TypeError("matrix_exp expects a float32 / float64 matrix")
+    N = X.shape[0]
+    if N > EXPM_MAX_N:
+        raise ValueError(f"matrix_exp: N={N} exceeds the single-workgroup limit {EXPM_MAX_N}")
+    Xc = X.contiguous()
+    E = torch.empty((N, N), dtype=X.dtype, device=dev) if want_real else None
+    Ec = torch.empty((N, N), dtype=_cdtype(X.dtype), device=dev) if want_cplx else None
+    stash = torch.empty(_lib.lib().fl_matrix_exp_stash_elems(N), dtype=torch.float64, device=dev)
+    outs = [t.data_ptr() for t in (E, Ec) if t is not None]
+    _lib.check(_fn("fl_matrix_exp" + form, X.dtype)(Xc.data_ptr(), N, int(skew), *outs, stash.data_ptr(), _stream()), "matrix_exp")
+    return E, Ec, stash, (N, int(skew), X.dtype, form)
+
+
+def _expm_backward(g, gc, cfg, stash):
+    """gradient of X from the cotangents of E (g) and Ec (gc: the kernel takes its real part); None = that form has none"""
+    N, skew, dt, form = cfg
+    g = None if g is None else g.to(dt).contiguous()
+    gc = None if gc is None else gc.resolve_conj().to(_cdtype(dt)).contiguous()
+    gX = torch.empty((N, N), dtype=dt, device=stash.device)
+    grads = (_ptr(g), _ptr(gc)) if form == "_both" else (_ptr(gc if form == "_cplx" else g),)
+    _lib.check(_fn("fl_matrix_exp_bwd" + form, dt)(*grads, N, skew, stash.data_ptr(), gX.data_ptr(), _stream()), "matrix_exp_bwd")
+    return gX
+
+
 class _MatrixExp(torch.autograd.Function):
     @staticmethod
     def forward(ctx, X, skew, cplx=False):
-        dev = _require_gpu(X)
-        if X.dim() != 2 or X.shape[0] != X.shape[1]:
-            raise ValueError("matrix_exp expects one square matrix")
-        if X.dtype not in (torch.float32, torch.float64):
-            raise TypeError("matrix_exp expects a float32 / float64 matrix")
-        N = X.shape[0]
-        if N > EXPM_MAX_N:
-            raise ValueError(f"matrix_exp: N={N} exceeds the single-workgroup limit {EXPM_MAX_N}")
-        Xc = X.contiguous()
-        L = _lib.lib()
-        E = torch.empty((N, N), dtype=_cdtype(X.dtype) if cplx else X.dtype, device=dev)
-        stash = torch.empty(L.fl_matrix_exp_stash_elems(N), dtype=torch.float64, device=dev)
-        if cplx:
-            fn = _fn("fl_matrix_exp_cplx", X.dtype)
-        else:
-            fn = _fn("fl_matrix_exp", X.dtype)
-        _lib.check(fn(Xc.data_ptr(), N, int(skew), E.data_ptr(), stash.data_ptr(), _stream()), "matrix_exp")
+        E, Ec, stash, ctx.cfg = _expm_forward(X, skew, not cplx, cplx)
         ctx.save_for_backward(stash)
-        ctx.cfg = (N, int(skew), X.dtype, bool(cplx))
-        return E
+        return Ec if cplx else E
 
     @staticmethod
     def backward(ctx, gE):
-        (stash,) = ctx.saved_tensors
-        N, skew, dt, cplx = ctx.cfg
-        if cplx:      # the kernel takes the real part of the complex gradient
-            g = gE.resolve_conj().to(_cdtype(dt)).contiguous()
-            fn = _fn("fl_matrix_exp_bwd_cplx", dt)
-        else:
-            g = gE.to(dt).contiguous()
-            fn = _fn("fl_matrix_exp_bwd", dt)
-        gX = torch.empty((N, N), dtype=dt, device=g.device)
-        _lib.check(fn(g.data_ptr(), N, skew, stash.data_ptr(), gX.data_ptr(), _stream()), "matrix_exp_bwd")
-        return gX, None, None
+        cplx = ctx.cfg[3] == "_cplx"
+        return _expm_backward(None if cplx else gE, gE if cplx else None, ctx.cfg, *ctx.saved_tensors), None, None
 
 
 class _MatrixExpBoth(torch.autograd.Function):
@@ -2834,37 +2784,16 @@ class _MatrixExpBoth(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, X, skew):
-        dev = _require_gpu(X)
-        if X.dim() != 2 or X.shape[0] != X.shape[1] or X.dtype not in (torch.float32, torch.float64):
-            raise ValueError("matrix_exp expects one square float32 / float64 matrix")
-        N = X.shape[0]
-        if N > EXPM_MAX_N:
-            raise ValueError(f"matrix_exp: N={N} exceeds the single-workgroup limit {EXPM_MAX_N}")
-        Xc = X.contiguous()
-        L = _lib.lib()
-        E = torch.empty((N, N), dtype=X.dtype, device=dev)
-        Ec = torch.empty((N, N), dtype=_cdtype(X.dtype), device=dev)
-        stash = torch.empty(L.fl_matrix_exp_stash_elems(N), dtype=torch.float64, device=dev)
-        fn = _fn("fl_matrix_exp_both", X.dtype)
-        _lib.check(fn(Xc.data_ptr(), N, int(skew), E.data_ptr(), Ec.data_ptr(), stash.data_ptr(), _stream()), "matrix_exp")
+        E, Ec, stash, ctx.cfg = _expm_forward(X, skew, True, True)
         ctx.save_for_backward(stash)
-        ctx.cfg = (N, int(skew), X.dtype)
         ctx.set_materialize_grads(False)        # an unused form's gradient arrives as None, not as a zero-filled tensor
         return E, Ec
 
     @staticmethod
     def backward(ctx, gE, gEc):
-        (stash,) = ctx.saved_tensors
-        N, skew, dt = ctx.cfg
         if gE is None and gEc is None:
             return None, None
-        g = None if gE is None else gE.to(dt).contiguous()
-        gc = None if gEc is None else gEc.resolve_conj().to(_cdtype(dt)).contiguous()
-        gX = torch.empty((N, N), dtype=dt, device=stash.device)
-        fn = _fn("fl_matrix_exp_bwd_both", dt)
-        _lib.check(fn(None if g is None else g.data_ptr(), None if gc is None else gc.data_ptr(), N, skew, stash.data_ptr(),
-                      gX.data_ptr(), _stream()), "matrix_exp_bwd")
-        return gX, None
+        return _expm_backward(gE, gEc, ctx.cfg, *ctx.saved_tensors), None
 
 
 def matrix_exp_both(X: torch.Tensor, skew: bool = False):

@@ -46,6 +46,23 @@ def test_plan_queries_and_errors():
     assert L.fl_rfft_f32(None, 0, 0, None, 48032, None, None, 1, 96000, 1.0, 0.0, 0, None) == -1   # null pointers rejected
 
 
+def test_mimo_variant_hook_accepts_only_the_remaining_codes():
+    """fl_debug_set_mimo_variant: 0 / -1 / -14 and a non-negative gradw cap; the codes of the removed kernels (register-tile
+    variants, the streaming kernel, the larger gradient tiles, direct MFMA stores) are errors with a message."""
+    from flamo_amd import _lib
+    L = _lib.lib()
+    try:
+        for ok in ((0, 0), (-1, 0), (-14, 0), (0, 64)):
+            assert L.fl_debug_set_mimo_variant(*ok) == 0, ok
+        for bad in ((842, 0), (0, -16), (0, -1642), (0, -88), (0, -2)):
+            assert L.fl_debug_set_mimo_variant(*bad) == -1, bad
+            assert L.fl_last_error(), bad
+            assert L.fl_mimo_gradw_blocks(256 * 100) == 64, bad          # a refused call changes no state
+    finally:
+        assert L.fl_debug_set_mimo_variant(0, 0) == 0
+    assert L.fl_mimo_gradw_blocks(256 * 100) == 100
+
+
 def test_ops_fail_loudly_without_gpu_tensors():
     from flamo_amd import ops
     with pytest.raises(RuntimeError, match="no CPU fallback"):

@@ -21,6 +21,8 @@ def test_transpose_bit_exact(gpu, shape):
 
 @pytest.mark.parametrize("No,Ni,K,B", [(1, 1, 1, 1), (3, 2, 1, 5), (8, 8, 1, 32), (5, 7, 3, 2), (16, 16, 16, 1),
                                        (32, 32, 1, 3), (1, 16, 1, 4), (16, 1, 1, 4),
+                                       # the diagonal patterns with trailing columns and a batch
+                                       (3, 3, 3, 2), (8, 8, 1, 5),
                                        # matrix-valued signals on the MFMA kernels: full, ragged rows/columns/depth,
                                        # batched columns, both tile shapes (<= 16 and > 16 rows or columns)
                                        (32, 32, 32, 1), (20, 9, 11, 2), (16, 24, 8, 1), (33, 17, 5, 4), (40, 32, 36, 1)])
@@ -48,6 +50,18 @@ def test_mimo_shapes_against_einsum(gpu, No, Ni, K, B):
             h = torch.randn(M, Ni, dtype=cd, device=gpu)
             Yd = ops.mimo(h, X, diag=True)
             cc("Yd_cpu", Yd.cpu(), torch.einsum("fn,bfn...->bfn...", h.cpu(), X.cpu()), tol, max_tol=float("inf"))
+            # both diagonal patterns (per-bin and constant h), forward and gradients, against the float64 einsum
+            for hd, pat in ((h, "fn,bfn...->bfn..."), (torch.randn(Ni, dtype=cd, device=gpu), "n,bfn...->bfn...")):
+                hd = hd.clone().requires_grad_(True)
+                Yd = ops.mimo(hd, Xg, diag=True)
+                hr, Xr = (t.detach().cpu().to(torch.complex128).requires_grad_(True) for t in (hd, X))
+                Ydr = torch.einsum(pat, hr, Xr)
+                cc("Yd_wide_cpu", Yd.detach().cpu(), Ydr.detach(), tol, max_tol=float("inf"))
+                C = torch.randn_like(Yd)
+                gh, gX = torch.autograd.grad(torch.sum(torch.real(Yd * torch.conj(C))), [hd, Xg])
+                ghr, gXr = torch.autograd.grad(torch.sum(torch.real(Ydr * torch.conj(C.cpu().to(torch.complex128)))), [hr, Xr])
+                assert gh.shape == hd.shape and gX.shape == X.shape
+                assert relerr(gh.cpu(), ghr) < tol * 5 and relerr(gX.cpu(), gXr) < tol * 5
 
 
 def test_geq_design_kernel_matches_host_formulas(gpu):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Kernel-only time of the per-bin 32x32x32 (or NxNxN) complex product for the tuning variants of
-fl_debug_set_mimo_variant: -1 lane-per-bin, -(10*rb+depth) MFMA tiles.   python tools/dbg/mfma_sweep.py [N] [M]"""
+fl_debug_set_mimo_variant: -1 lane-per-bin, 0 default, -14 MFMA 16x16 tile.   python tools/dbg/mfma_sweep.py [N] [M]"""
 import os
 import sys
 
