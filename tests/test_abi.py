@@ -32,6 +32,104 @@ def test_library_exports_every_declared_symbol():
     assert L.fl_version() == 1
 
 
+_i, _l, _d, _sz, _vp = ctypes.c_int, ctypes.c_long, ctypes.c_double, ctypes.c_size_t, ctypes.c_void_p
+_ip = ctypes.POINTER(ctypes.c_int)
+
+_SYNTHETIC_HEADER = """\
+/* a header in the style of include/flamo_hip.h
+ * int fl_fake(int x);   -- inside a comment: not a declaration */
+#ifndef SYNTHETIC_H
+#define SYNTHETIC_H
+#include <stddef.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define FL_OK 0
+#define FL_ERR_BAD_ARG (-1)
+
+int fl_zero(void);
+const char* fl_message(void);
+/* every parameter kind */
+long fl_kinds(int a, long b, double c, size_t d, unsigned e, int* f, const char* g, void* h, const void* i,
+              int32_t* j, const int32_t *k);
+size_t fl_three_lines(const void* x,
+                      long x_stride, int n,   /* a comment between parameters */
+                      void* stream);
+%s
+#ifdef __cplusplus
+}
+#endif
+#endif /* SYNTHETIC_H */
+"""
+
+
+def test_header_parser_on_a_synthetic_header():
+    """_lib._parse_header: comments and preprocessor lines are skipped, declarations may span lines, (void) is no parameter,
+    names are dropped and every type goes through the one table -- the exact restype and argtypes of each declaration."""
+    from flamo_amd import _lib
+    sigs = _lib._parse_header(_SYNTHETIC_HEADER % "")
+    assert list(sigs) == ["fl_zero", "fl_message", "fl_kinds", "fl_three_lines"]          # fl_fake is in a comment
+    assert sigs["fl_zero"] == (_i, [])
+    assert sigs["fl_message"] == (ctypes.c_char_p, [])
+    assert sigs["fl_kinds"] == (_l, [_i, _l, _d, _sz, ctypes.c_uint, _ip, ctypes.c_char_p, _vp, _vp, _vp, _vp])
+    assert sigs["fl_three_lines"] == (_sz, [_vp, _l, _i, _vp])
+
+
+@pytest.mark.parametrize("decl", [
+    "int fl_bad(const void* x, float scale);",
+    "int fl_bad(const void* x, hipStream_t stream);",
+    "int fl_bad(struct foo v, int n);",
+    "float fl_bad(int n);",                                   # return types go through the same table
+    "int fl_bad(int n, int shape[3]);",
+    "int fl_bad(int n, void (*done)(int));",                   # not matched as a declaration: an error, not an unbound symbol
+    "int fl_bad(int n)",                                       # no semicolon
+])
+def test_header_parser_refuses_what_it_does_not_know(decl):
+    from flamo_amd import _lib
+    with pytest.raises(ValueError, match="fl_bad"):
+        _lib._parse_header(_SYNTHETIC_HEADER % decl)
+
+
+def test_signatures_of_the_real_header_pinned_rows():
+    """Rows written out by hand from the table flamo_amd/_lib.py used to carry: every return type (int, const char*, size_t,
+    long) and every pointer kind (int*, void*, const void*, const int32_t*) of the header, unsigned, size_t by value, and the
+    longest parameter list."""
+    from flamo_amd import _lib
+    S = _lib._SIGNATURES
+    assert len(S) == 188 and _lib.EXPORTS == tuple(S)
+    assert S["fl_version"] == (_i, [])
+    assert S["fl_last_error"] == (ctypes.c_char_p, [])
+    assert S["fl_fft_plan"] == (_i, [_i, _i, _ip, _ip])
+    assert S["fl_fft_scratch_elems"] == (_sz, [_i, _i, _i])
+    assert S["fl_solve_ws_bytes"] == (_l, [_i, _i, _i])
+    assert S["fl_rfft_f32"] == (_i, [_vp, _l, _i, _vp, _l, _vp, _vp, _i, _i, _d, _d, _i, _vp])
+    assert S["fl_spec_walk_partition"] == (_i, [_i, _i, _i, _ip])
+    assert S["fl_set_stream_policy"] == (_i, [ctypes.c_uint, _i])
+    assert S["fl_hbm_probe"] == (_i, [_i, _vp, _vp, _sz, _i, _i, _vp, _vp])
+    assert S["fl_delay_response_c64"] == (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _l, _vp])
+    assert S["fl_solve_dud2_grads_w_c64"] == (_i, [_vp, _l, _l, _vp, _l, _l, _vp, _vp, _l, _l, _vp, _l, _vp, _l, _vp, _l, _l, _l,
+                                                   _i, _i, _i, _vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _l, _vp, _l, _vp, _vp])
+    assert len(S["fl_solve_dud2_grads_w_c64"][1]) == 34
+
+
+def test_precision_pairs_have_one_signature():
+    """An entry point that exists in both precisions takes the same arguments in both -- with the exceptions listed here."""
+    from flamo_amd import _lib
+    S = _lib._SIGNATURES
+    # the single-precision Matrix-then-cascade responses choose between the float and the double evaluation of the cascade
+    # (int float_eval, in front of the stream); the complex128 forms always evaluate in double and have no such argument
+    float_eval = {"fl_sos_response_rc_c64", "fl_geq_response_rc_c64"}
+    pairs = [(n, n[:-len(lo)] + hi) for lo, hi in (("_f32", "_f64"), ("_c64", "_c128")) for n in S if n.endswith(lo)]
+    pairs = [(n, m) for n, m in pairs if m in S]
+    assert len(pairs) >= 60 and float_eval <= {n for n, _ in pairs}
+    for n, m in pairs:
+        res, args = S[n]
+        if n in float_eval:
+            assert args[-2] is _i
+            args = args[:-2] + args[-1:]
+        assert (res, args) == S[m], (n, m)
+
+
 def test_plan_queries_and_errors():
     from flamo_amd import _lib
     L = _lib.lib()
