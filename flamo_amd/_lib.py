@@ -1,5 +1,6 @@
-"""ctypes binding of libflamo_hip.so.  The C ABI is declared in include/flamo_hip.h, and the restype / argtypes of every
-entry point are read from that header at import (_parse_header): no signature is written a second time here.
+"""ctypes binding of libflamo_hip.so.  The C ABI is declared in include/flamo_hip.h (and, for the energy-decay-curve
+criterion, include/flamo_hip_edc.h), and the restype / argtypes of every entry point are read from those headers at import
+(_parse_header): no signature is written a second time here.
 
 The shared library is built in-tree (``flamo_amd/libflamo_hip.so``) by ``build()`` /
 ``make -C flamo_amd/csrc``.  There is NO fallback: if the library is missing or a tensor is
@@ -18,6 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FLAMO_HIP_LIB") or os.path.join(_HERE, "libflamo_hip.so")   # override: A/B builds
 CSRC = os.path.join(_HERE, "csrc")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "flamo_hip.h")
+HEADER_EDC_PATH = os.path.join(os.path.dirname(_HERE), "include", "flamo_hip_edc.h")      # the criterion of csrc/edc.hip
 
 _lock = threading.Lock()
 _lib = None
@@ -72,10 +74,10 @@ def _parse_header(text: str) -> dict:
     return sigs
 
 
-def _read_header() -> dict:
-    if not os.path.exists(HEADER_PATH):
-        raise RuntimeError(f"{HEADER_PATH} not found: the ctypes signatures of libflamo_hip.so are read from it.")
-    with open(HEADER_PATH) as f:
+def _read_header(path: str = HEADER_PATH) -> dict:
+    if not os.path.exists(path):
+        raise RuntimeError(f"{path} not found: the ctypes signatures of libflamo_hip.so are read from it.")
+    with open(path) as f:
         return _parse_header(f.read())
 
 
@@ -84,6 +86,9 @@ def _read_header() -> dict:
 _SIGNATURES = _read_header()
 
 EXPORTS = tuple(_SIGNATURES)
+
+# the entries of include/flamo_hip_edc.h, a table of their own: bound by lib() like the others
+_SIGNATURES_EDC = _read_header(HEADER_EDC_PATH)
 
 
 def build(force: bool = False) -> str:
@@ -122,7 +127,7 @@ def lib(pair_ok: bool = False) -> C.CDLL:
                         "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C flamo_amd/csrc`)."
                     )
                 handle = C.CDLL(LIB_PATH)
-                for name, (res, args) in _SIGNATURES.items():
+                for name, (res, args) in (*_SIGNATURES.items(), *_SIGNATURES_EDC.items()):
                     fn = getattr(handle, name)  # AttributeError if the symbol is missing
                     fn.restype = res
                     fn.argtypes = args

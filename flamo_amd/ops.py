@@ -18,6 +18,7 @@ import threading
 from collections import namedtuple
 from typing import NamedTuple, Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -2706,6 +2707,115 @@ def mse(y: torch.Tensor, target: torch.Tensor, sum_last: bool = False) -> torch.
     elif tuple(t.shape) != tuple(y.shape):
         raise ValueError(f"mse: prediction {tuple(y.shape)} and target {tuple(target.shape)} differ in shape")
     return _MSE.apply(y, t.to(dtype=y.dtype, device=y.device), int(ncols))
+
+
+EDC_DISCARD_PERCENT = 0.5      # the reference drops the last 5 permille of the signal (filtering artefacts, loss.py:742-747)
+
+
+def _edc_keep(T: int) -> int:
+    """samples of T the criterion keeps: the reference's own host expression"""
+    return int(np.round((1 - EDC_DISCARD_PERCENT / 100) * T))
+
+
+def _edc_mem(y: torch.Tensor):
+    """(tensor with the memory the kernels read, planar, pitch) of a (B, T, N) signal: contiguous channel-innermost memory and
+    the signal-planar views the transforms return are taken as they are, anything else is made contiguous once"""
+    if y.is_contiguous():
+        return y, 0, y.shape[1]
+    P = _lead_pitch(y.movedim(1, -1))
+    if P is not None:
+        return y, 1, P
+    return y.contiguous(), 0, y.shape[1]
+
+
+def _edc_check(y: torch.Tensor, what: str):
+    if y.dim() != 3 or y.dtype not in (torch.float32, torch.float64) or y.numel() == 0:
+        raise ValueError(f"{what}: a non-empty real float32 / float64 (B, T, N) signal, got {tuple(y.shape)} {y.dtype}")
+    if _edc_keep(y.shape[1]) < 1:
+        raise ValueError(f"{what}: no sample left of T = {y.shape[1]}")
+
+
+def _edc_curve(y, energy_norm, clip, want_den, dev):
+    """tile sums and the curve in dB of y (no gradient): (edb (B, T', N), tile sums, mean square of the clipped curve or None)"""
+    B, T, N = y.shape
+    Tk = _edc_keep(T)
+    ym, planar, pitch = _edc_mem(y)
+    nt = -(-Tk // _lib.lib().fl_edc_tile())
+    tsum = torch.empty((B * N, nt), dtype=torch.float64, device=dev)
+    edb = torch.empty((B, Tk, N), dtype=y.dtype, device=dev)
+    den = _scalar_loss(y.dtype, dev) if want_den else None
+    _lib.check(_fn("fl_edc_tile_sums", y.dtype)(ym.data_ptr(), planar, B, T, Tk, N, pitch, tsum.data_ptr(), _stream()), "edc_tile_sums")
+    _lib.check(_fn("fl_edc_curve", y.dtype)(ym.data_ptr(), planar, B, T, Tk, N, pitch, tsum.data_ptr(), int(energy_norm), int(clip),
+                                            edb.data_ptr(), _ptr(den), _ms_scratch_for(dev).data_ptr() if want_den else None,
+                                            _stream()), "edc_curve")
+    return edb, tsum, den
+
+
+class _EDCLoss(torch.autograd.Function):
+    """the broadband energy-decay-curve criterion, one node over the prediction: tile sums, the target's curve, the loss pass
+    (which leaves w = m (e - e*) / E and its tile sums behind) forward; one scan of w backward"""
+
+    @staticmethod
+    def forward(ctx, y, t, energy_norm, convergence, clip):
+        dev = _require_gpu(y, t)
+        B, T, N = y.shape
+        Tk = _edc_keep(T)
+        with kernel_timer.span("edc_target"):
+            edb_t, tsum_t, den = _edc_curve(t, energy_norm, clip, convergence, dev)
+        ym, planar, pitch = _edc_mem(y)
+        sums = torch.empty((3, B * N, tsum_t.shape[1]), dtype=torch.float64, device=dev)      # of y^2, of w, of m (e - e*)
+        want_w = ctx.needs_input_grad[0]
+        w = torch.empty_strided(ym.shape, ym.stride(), dtype=ym.dtype, device=dev) if want_w else None
+        loss = _scalar_loss(y.dtype, dev)
+        with kernel_timer.span("edc_loss"):
+            _lib.check(_fn("fl_edc_tile_sums", y.dtype)(ym.data_ptr(), planar, B, T, Tk, N, pitch, sums[0].data_ptr(), _stream()),
+                       "edc_tile_sums")
+            _lib.check(_fn("fl_edc_loss", y.dtype)(ym.data_ptr(), planar, B, T, Tk, N, pitch, sums[0].data_ptr(), edb_t.data_ptr(),
+                                                   tsum_t.data_ptr(), int(energy_norm), int(clip), _ptr(den), _ptr(w),
+                                                   sums[1].data_ptr(), sums[2].data_ptr(), loss.data_ptr(),
+                                                   _ms_scratch_for(dev).data_ptr(), _stream()), "edc_loss")
+        if want_w:
+            ctx.save_for_backward(ym, w, sums, den)
+            ctx.cfg = (planar, pitch, B, T, Tk, N, bool(energy_norm))
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        ym, w, sums, den = ctx.saved_tensors
+        planar, pitch, B, T, Tk, N, energy_norm = ctx.cfg
+        gy = torch.empty_strided(ym.shape, ym.stride(), dtype=ym.dtype, device=ym.device)
+        g = _gloss_as(gloss, ym.dtype)
+        with kernel_timer.span("edc_bwd"):
+            _lib.check(_fn("fl_edc_bwd", ym.dtype)(ym.data_ptr(), planar, B, T, Tk, N, pitch, sums[0].data_ptr(), w.data_ptr(),
+                                                  sums[1].data_ptr(), sums[2].data_ptr(), g.data_ptr(), _ptr(den), int(energy_norm),
+                                                  gy.data_ptr(), _stream()), "edc_bwd")
+        return gy, None, None, None, None
+
+
+def edc_db(y: torch.Tensor, energy_norm: bool = False) -> torch.Tensor:
+    """The energy decay curve of a (B, T, N) signal in dB, (B, T', N) with T' = round(0.995 T): Schroeder's backward integral
+    E[b, s, c] = sum_{t >= s} y[b, t, c]^2 over the kept samples, 10 log10(E / E[b, 0, c]) with ``energy_norm`` and
+    10 log10(E) without -- flamo/optimize/loss.py:742-777 (`edc_loss.get_edc`, broadband) in two launches.  No gradient."""
+    dev = _require_gpu(y)
+    y = y.detach()
+    _edc_check(y, "edc_db")
+    with kernel_timer.span("edc_db"):
+        return _edc_curve(y, energy_norm, False, False, dev)[0]
+
+
+def edc_loss(y_pred: torch.Tensor, y_true: torch.Tensor, energy_norm: bool = False, convergence: bool = False,
+             clip: bool = False) -> torch.Tensor:
+    """The reference's broadband energy-decay-curve criterion (flamo/optimize/loss.py:779-809) of (B, T, N) signals: the mean
+    squared difference of the two curves in dB (``edc_db``), with ``clip`` only where the TARGET's curve is within 60 dB of its
+    start, with ``convergence`` divided by the mean square of the target's curve.  One autograd node over the prediction (a
+    reverse scan forward, a forward scan of the weighted differences backward); the target takes no gradient and its curve is
+    computed on every call.  A column whose kept tail is exactly zero gives a non-finite loss, as it does in the reference."""
+    _require_gpu(y_pred, y_true)
+    t = y_true.detach()
+    _edc_check(y_pred, "edc_loss")
+    if tuple(t.shape) != tuple(y_pred.shape) or t.dtype != y_pred.dtype:
+        raise ValueError(f"edc_loss: prediction {tuple(y_pred.shape)} {y_pred.dtype} and target {tuple(t.shape)} {t.dtype} differ")
+    return _EDCLoss.apply(y_pred, t, bool(energy_norm), bool(convergence), bool(clip))
 
 
 def mean_square(y: torch.Tensor) -> torch.Tensor:

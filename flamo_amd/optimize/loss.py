@@ -1,9 +1,11 @@
 """``mse_loss`` and ``sparsity_loss`` of the reference (flamo/optimize/loss.py:12-103) on the library's kernels -- the two
-criteria of the colorless-FDN training (examples/e8_colorless_fdn.py:137-138).
+criteria of the colorless-FDN training (examples/e8_colorless_fdn.py:137-138) -- and its broadband ``edc_loss``
+(loss.py:674-809), the criterion of a fit to a measured room impulse response.
 
 The reference's training loop calls ``criterion(estimations, targets)`` (flamo/optimize/trainer.py:179-189); with
 ``flamo_amd.optimize.mse_loss`` in that list the loop runs unedited and the criterion costs one streaming pass over the
 prediction each way (``ops.mse``) instead of torch's sum / sub / pow / mean kernels and their backward."""
+import numpy as np
 import torch
 from torch import nn
 
@@ -31,6 +33,85 @@ class mse_loss(nn.Module):
         # summed columns than the kernel takes): the reference's own lines
         y_pred_sum = torch.sum(y_pred, dim=-1)
         return self.mse_loss(y_pred_sum, y_true.squeeze(-1))
+
+
+class edc_loss(nn.Module):
+    """Energy decay curve criterion, flamo/optimize/loss.py:674-809 in its broadband form: the mean squared difference, in dB,
+    of the Schroeder backward integrals of prediction and target (B, T, N), after the last ``discard_n`` = 0.5 % of the samples
+    are dropped.  ``energy_norm`` refers every curve to its own start, ``clip`` sets both curves to -180 dB where the TARGET's
+    is more than 60 dB under its maximum, ``convergence`` divides by the mean square of the target's curve.  Same constructor,
+    defaults, attributes and methods as the reference's class; the subband form (``is_broadband=False``, the reference's
+    default) needs pyfar's fractional-octave filter bank and is refused at construction.
+
+    Device float32 / float64 predictions against a gradient-free target of the same shape and dtype run on ``ops.edc_loss``
+    (a tiled scan each way); host tensors, a target that takes a gradient and other dtypes take the torch lines below."""
+
+    def __init__(self, sample_rate: int = 48000, is_broadband: bool = False, n_fractions: int = 1, energy_norm: bool = False,
+                 convergence: bool = False, clip: bool = False, name: str = "EDC", device: str = "cpu"):
+        super().__init__()
+        if not is_broadband:
+            raise NotImplementedError("edc_loss(is_broadband=False): the subband form needs pyfar's fractional-octave filter bank "
+                                      "(pyfar.dsp.filter.fractional_octave_bands), which this package does not carry; "
+                                      "construct it with is_broadband=True")
+        self.sample_rate = sample_rate
+        self.is_broadband = is_broadband
+        self.n_fractions = n_fractions
+        self.energy_norm = energy_norm
+        self.convergence = convergence
+        self.clip = clip
+        self.name = name
+        self.device = device
+        self.discard_n = 0.5
+        self.mse = nn.MSELoss(reduction="mean")
+
+    @staticmethod
+    def _on_kernels(x):
+        return torch.is_tensor(x) and x.is_cuda and x.dim() == 3 and x.dtype in (torch.float32, torch.float64) and x.numel() > 0
+
+    def discard_last_n_percent(self, x, n_percent):
+        """x (B, T, N) without its last n_percent of samples"""
+        keep = int(np.round((1 - n_percent / 100) * x.shape[1]))
+        return x[:, :keep, :]
+
+    def schroeder_backward_int(self, x):
+        """(E, Z): E[b, s, c] = sum_{t >= s} x[b, t, c]^2 divided by Z, Z = its per-column maximum (``energy_norm``) or ones"""
+        energy = x.square().flip(1).cumsum(1).flip(1)
+        if self.energy_norm:
+            norm_vals = energy.amax(dim=1, keepdim=True)
+        else:
+            norm_vals = torch.ones_like(energy)
+        return energy / norm_vals, norm_vals
+
+    def get_edc(self, x):
+        """the curve in dB, (B, T', N)"""
+        if self._on_kernels(x) and self.discard_n == ops.EDC_DISCARD_PERCENT:
+            return ops.edc_db(x, energy_norm=self.energy_norm)
+        return self._torch_edc(x)
+
+    def _torch_edc(self, x):
+        return 10 * torch.log10(self.schroeder_backward_int(self.discard_last_n_percent(x, self.discard_n))[0])
+
+    def _torch_forward(self, y_pred, y_true):
+        """the criterion in plain torch, on whatever device the tensors live"""
+        e_pred, e_true = self._torch_edc(y_pred), self._torch_edc(y_true)
+        if self.clip:
+            below = e_true < e_true.amax(dim=1, keepdim=True) - 60
+            floor = torch.full_like(e_true, -180.0)
+            e_pred, e_true = torch.where(below, floor, e_pred), torch.where(below, floor, e_true)
+        num = self.mse(e_pred, e_true)
+        if self.convergence:
+            return num / torch.mean(e_true ** 2)
+        return num
+
+    def forward(self, y_pred, y_true):
+        if y_pred.dim() == 1:
+            y_pred, y_true = y_pred[None, :, None], y_true[None, :, None]
+        assert y_pred.shape == y_true.shape and y_true.dim() == 3, \
+            "y_pred and y_true must have the same shape (n_batch, n_samples, n_channels)"
+        if (self._on_kernels(y_pred) and y_true.is_cuda and y_true.dtype == y_pred.dtype and not y_true.requires_grad
+                and self.discard_n == ops.EDC_DISCARD_PERCENT):
+            return ops.edc_loss(y_pred, y_true, energy_norm=self.energy_norm, convergence=self.convergence, clip=self.clip)
+        return self._torch_forward(y_pred, y_true)
 
 
 class masked_mse_loss(nn.Module):

@@ -578,6 +578,47 @@ def gen_householder_sparsity(dsp, system):
     save("householder_sparsity", dict(kind="householder_sparsity", N=N, nfft=nfft), u=mix.param, loss=loss, g_u=g)
 
 
+# ----------------------------------------------------------------------------- broadband energy-decay-curve criterion
+EDC_OPTION_SETS = ({}, dict(energy_norm=True), dict(clip=True), dict(convergence=True),
+                   dict(energy_norm=True, clip=True, convergence=True))
+
+
+def edc_signals(shape, seed):
+    """(prediction, target) for the EDC criterion: seeded Gaussian noise under an exponential envelope whose rate differs per
+    channel -- the prediction's first channel ends at -80 dB, the target's at -70 dB, each further channel 1.5 dB lower --
+    as float64 values that float32 represents exactly, without an exact zero.  They are rounded to eight significant bits
+    (bfloat16's), which halves what the signals add to the fixture; the recorded gradients are full float64 numbers."""
+    B, T, N = shape
+    gen = torch.Generator().manual_seed(seed)
+    ramp = torch.arange(T, dtype=F64)[None, :, None] / (T - 1)
+    out = []
+    for end_db in (-80.0, -70.0):
+        ends = end_db - 1.5 * torch.arange(N, dtype=F64)[None, None, :]
+        y = (torch.randn(B, T, N, dtype=F64, generator=gen) * 10 ** (ends * ramp / 20)).bfloat16().double()
+        assert (y != 0).all()
+        out.append(y)
+    return out
+
+
+def gen_edc_loss(dsp, system):
+    """flamo/optimize/loss.py:674-809 with is_broadband=True, float64: loss and gradient under the cotangent 3.0 of every option
+    set of EDC_OPTION_SETS on (2, 1500, 3), of the first and the last on (3, 777, 5)."""
+    from flamo.optimize.loss import edc_loss
+    arrays, cases = {}, []
+    for si, (shape, seed, sets) in enumerate((((2, 1500, 3), 20261019, EDC_OPTION_SETS),
+                                              ((3, 777, 5), 20261020, (EDC_OPTION_SETS[0], EDC_OPTION_SETS[-1])))):
+        y_pred, y_true = edc_signals(shape, seed)
+        arrays[f"s{si}_y_pred"], arrays[f"s{si}_y_true"] = y_pred.float(), y_true.float()
+        for opts in sets:
+            yp = y_pred.clone().requires_grad_(True)
+            loss = edc_loss(is_broadband=True, **opts)(yp, y_true.clone())
+            (g,) = torch.autograd.grad(3.0 * loss, [yp])
+            k = len(cases)
+            arrays[f"c{k}_loss"], arrays[f"c{k}_grad"] = loss.detach(), g
+            cases.append(dict(signals=si, shape=list(shape), options=opts))
+    save("edc_loss", dict(kind="edc_loss", cotangent=3.0, cases=cases), **arrays)
+
+
 def main():
     torch.set_default_dtype(torch.float32)
     dsp, system = refimport.load()
@@ -602,6 +643,9 @@ def main():
     if "--householder-only" in sys.argv:
         gen_householder_sparsity(dsp, system)
         return
+    if "--edc-only" in sys.argv:
+        gen_edc_loss(dsp, system)
+        return
     if "--biquad-only" in sys.argv:
         gen_biquad_training(dsp, system)
         return
@@ -616,6 +660,7 @@ def main():
     gen_biquad_training(dsp, system)
     gen_householder_sparsity(dsp, system)
     gen_round2(dsp, system)
+    gen_edc_loss(dsp, system)
     total = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT) if f.endswith(".npz"))
     print(f"total {total/1024:.1f} KiB")
 
