@@ -228,45 +228,49 @@ struct MidArgs {
     long long* dbg_times; // tuning: per-workgroup cycle stamps at the phase boundaries (8 per workgroup), or null
 };
 
-// BG batch items per workgroup (256*BG threads): a response row fetched for a bin pair is applied to the BG spectra in
-// registers, so the response's trips through the TA/L2 shrink by BG (at one item per workgroup they are 8x the
-// signal's bytes).  Streaming data (scratch, stored spectrum) is non-temporal so that it does not evict the response
-// slice that the batch items of a row pair share in their XCD's L2.
-template <int A, int B, int NI, int NO, bool HAS_H, bool DO_INV, int BG, int MS, int PFD = 0, int NTH = MS, int P3V = 0>
-__global__ void __launch_bounds__(256 * NTH, ((NTH == 2 && MS == 1) || P3V == 1 ? 4 : 1)) spec_mid(MidArgs a) {
+// One workgroup of 256 threads per (row pair, batch item): the two mirrored rows of all channels stay in LDS from the
+// forward row FFTs to the inverse ones, and each thread takes whole bin pairs (k, L-k) through the split step, the
+// product and the Hermitian pre-step in registers.  Streaming data (scratch, stored spectrum) is non-temporal so that
+// it does not evict the response slice that the batch items of a row pair share in their XCD's L2.
+// PINNED: the kernel once took several batch items per workgroup and split a bin pair over threads.  Those forms are gone,
+// and every instantiation compiles to the instructions and registers it had with them.  A few expressions that are
+// constant in a 256-thread workgroup of one item (marked PINNED below: nb, `over`, w256, two one-trip loops) are not
+// constant to the compiler -- it assumes up to 1024 threads -- and folding them by hand changes the generated code of every
+// instantiation (92 -> 114 registers at 8 -> 8 channels, scratch where an array is then indexed dynamically).  They go with
+// the next change of this kernel that is measured on the device.
+template <int A, int B, int NI, int NO, bool HAS_H, bool DO_INV>
+__global__ void __launch_bounds__(256, 1) spec_mid(MidArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int LEN = A * B, LENP = LEN | 1, NCH = NI > NO ? NI : NO, NT = 256 * NTH;
+    constexpr int LEN = A * B, LENP = LEN | 1, NCH = NI > NO ? NI : NO, NT = 256;
     constexpr int RPR = NT / A;              // rows per stage-2 round (every k_a of a row in the same round)
-    // MS: the product of a bin pair is split over MS threads (output channels); 256*NTH threads in the workgroup
-    // (NTH > MS: the extra threads take part in the FFT phases only)
-    static_assert(NT % A == 0 && NO % MS == 0 && NI % MS == 0, "tile shape");
-    cf* U = reinterpret_cast<cf*>(smem);     // [BG][2][NCH][LENP]
-    cf* tw = U + BG * 2 * NCH * LENP;        // W_LEN^m
+    static_assert(NT % A == 0, "tile shape");
+    static_assert(HAS_H || NI == NO, "without a response the channels pass through");
+    cf* U = reinterpret_cast<cf*>(smem);     // [2][NCH][LENP]
+    cf* tw = U + 2 * NCH * LENP;             // W_LEN^m
     cf* ws = tw + LEN;                       // W_n^(L1*k2)
     cf* wi2 = ws + LEN;                      // [2][B]: W_L^(row * A * kb)
-    cf* nyq = wi2 + 2 * B;                   // [BG][NCH]: the Nyquist bin of row pair 0 (P3V == 1)
-    // XCD-aware order: the batch groups of one row pair run back to back on the same XCD (block q runs on XCD
+    // XCD-aware order: the batch items of one row pair run back to back on the same XCD (block q runs on XCD
     // q % 8), so that pair's slice of H is fetched from HBM once and from that L2 afterwards
     const int P = a.L1 / 2 + 1;
-    const int nbq = (a.Bn + BG - 1) / BG;
     const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
-    const int r = (q / nbq) * 8 + xcd, b0 = (q % nbq) * BG;
+    const int r = (q / a.Bn) * 8 + xcd, b = q % a.Bn;
     if (r >= P) return;
-    const int nb = min(BG, a.Bn - b0);
+    const int nb = min(1, a.Bn - b);         // PINNED: batch items of this workgroup, 1 (b < Bn); tested as 0 < nb below
     const int rm = (a.L1 - r) % a.L1;
     const bool selfm = rm == r;
     const int tid = threadIdx.x;
     const unsigned bstride_i = (unsigned)a.L1 * (unsigned)a.L2 * NI, bstride_o = (unsigned)a.L1 * (unsigned)a.L2 * NO;
-    // ---- P1: load + first stage of the forward row FFTs.  item = (batch item, slot, tb, n), n fastest: the loads of
+    // ---- P1: load + first stage of the forward row FFTs.  item = (slot, tb, n), n fastest: the loads of
     // a wavefront cover contiguous (tb, n) runs of a scratch row.  The first item's samples are requested before the
     // twiddle tables (whose round trip would otherwise sit in front of the data's).
-    const cf* Sb = a.S + (size_t)b0 * bstride_i;
+    const cf* Sb = a.S + (size_t)b * bstride_i;
     cf v0[A];
     auto p1_load = [&](int item, cf* v) {
+        // PINNED: bs = slot + 2 * (row pairs past the workgroup's own: `over`, 0 for every item that passes the first test)
         const int nn = item % NI, tb = (item / NI) % B, bs = item / (NI * B);
-        const int slot = bs & 1, bb = bs >> 1;
-        if (item >= BG * 2 * B * NI || (slot && selfm) || bb >= nb) return false;
-        const unsigned src0 = (unsigned)bb * bstride_i + (unsigned)(slot ? rm : r) * (unsigned)a.L2 * NI + nn;
+        const int slot = bs & 1, over = bs >> 1;
+        if (item >= 2 * B * NI || (slot && selfm) || over >= nb) return false;
+        const unsigned src0 = (unsigned)over * bstride_i + (unsigned)(slot ? rm : r) * (unsigned)a.L2 * NI + nn;
 #pragma unroll
         for (int ta = 0; ta < A; ++ta) v[ta] = ld_nt(Sb, ESZ * (src0 + (unsigned)(ta * B + tb) * NI));
         return true;
@@ -283,8 +287,8 @@ __global__ void __launch_bounds__(256 * NTH, ((NTH == 2 && MS == 1) || P3V == 1 
     __syncthreads();
     if (a.dbg_times && tid == 0) a.dbg_times[(size_t)blockIdx.x * 8 + 0] = clock64();
     {
-        for (int item = tid; item < BG * 2 * B * NI; item += NT) {
-            const int nn = item % NI, tb = (item / NI) % B, bs = item / (NI * B);
+        for (int item = tid; item < 2 * B * NI; item += NT) {
+            const int nn = item % NI, tb = (item / NI) % B, slot = item / (NI * B);
             cf v[A];
             bool have;
             if (item == tid) {
@@ -296,7 +300,7 @@ __global__ void __launch_bounds__(256 * NTH, ((NTH == 2 && MS == 1) || P3V == 1 
             }
             if (!have) continue;
             RegFFT<real_t, A, false>::run(v);
-            cf* u = U + (bs * NCH + nn) * LENP + tb;
+            cf* u = U + (slot * NCH + nn) * LENP + tb;
             u[0] = v[0];
 #pragma unroll
             for (int ka = 1; ka < A; ++ka) u[ka * B] = v[ka] * tw[ka * tb];
@@ -305,12 +309,12 @@ __global__ void __launch_bounds__(256 * NTH, ((NTH == 2 && MS == 1) || P3V == 1 
     __syncthreads();
     if (a.dbg_times && tid == 0) a.dbg_times[(size_t)blockIdx.x * 8 + 1] = clock64();
     // ---- P2: second stage, natural order written back in place (read all, barrier, write all per round)
-    for (int row0 = 0; row0 < BG * 2 * NI; row0 += RPR) {
+    for (int row0 = 0; row0 < 2 * NI; row0 += RPR) {
         const int rl = row0 + tid % RPR, ka = tid / RPR;
-        const int bs = rl / NI, nn = rl % NI;
-        const bool act = rl < BG * 2 * NI && !((bs & 1) && selfm) && (bs >> 1) < nb;
+        const int slot = rl / NI, nn = rl % NI;
+        const bool act = rl < 2 * NI && !(slot && selfm) && 0 < nb;
         cf v[B];
-        cf* urow = U + (bs * NCH + nn) * LENP;
+        cf* urow = U + (slot * NCH + nn) * LENP;
         if (act) {
 #pragma unroll
             for (int tb = 0; tb < B; ++tb) v[tb] = urow[ka * B + tb];
@@ -324,58 +328,56 @@ __global__ void __launch_bounds__(256 * NTH, ((NTH == 2 && MS == 1) || P3V == 1 
         __syncthreads();
     }
     if (a.dbg_times && tid == 0) a.dbg_times[(size_t)blockIdx.x * 8 + 2] = clock64();
-    if constexpr (P3V == 0) {
-    // ---- P3: split step, spectrum store, product, Hermitian pre-step.  Thread (p, ms): bin pair (k, L-k) number p, output
-    // channels [ms NO/MS, (ms+1) NO/MS), all BG batch items.  The MS threads of a pair read the same two columns of U
-    // (all input channels) and write their own output channels back into them: one barrier between the two.
+    // ---- P3: split step, spectrum store, product, Hermitian pre-step.  Thread p: bin pair (k, L-k) number p, all
+    // channels.  It reads its two columns of U (all input channels) and writes the output channels back into them.
+    // PINNED (see the note above the kernel): w256 = tid / 256 is 0, and what is written in terms of it -- `valid`, the
+    // channel indices w256 N + n picked by compare-and-select, the row index made scalar by readfirstlane -- and the two
+    // one-trip `only` loops stay in the shape the generated code depends on.
     {
         const cf wr = a.W[r];
         const real_t hs = (real_t)0.5 * a.spec_scale, wi = a.spec_interior2 ? (real_t)2 : (real_t)1;
         const real_t ph = a.pre_half ? (real_t)0.5 : (real_t)1;
-        const int ms = tid / 256;
+        const int w256 = tid / 256;
         for (int p0 = 0; p0 < LEN; p0 += 256) {
             const int p = p0 + (tid & 255);
             int slotB = 0, colB = 0;
             bool dc = false;
-            const bool valid = ms < MS && p < LEN && pair_of(r, selfm, p, LEN, slotB, colB, dc);
+            const bool valid = w256 < 1 && p < LEN && pair_of(r, selfm, p, LEN, slotB, colB, dc);
             const unsigned ik = (unsigned)r * LEN + p;
             const unsigned im = dc ? (unsigned)a.L : (unsigned)(slotB ? rm : r) * LEN + colB;
-            cf xk[BG][NI], xm[BG][NI];
+            cf xk[NI], xm[NI];
             cf wk(1, 0);
             if (valid) {
                 wk = wr * ws[p];
 #pragma unroll
-                for (int bb = 0; bb < BG; ++bb) {
-#pragma unroll
-                    for (int nn = 0; nn < NI; ++nn) {
-                        const cf zk = U[((2 * bb) * NCH + nn) * LENP + p];
-                        const cf zm = U[((2 * bb + slotB) * NCH + nn) * LENP + colB];
-                        if (dc) {
-                            xk[bb][nn] = cf(a.spec_scale * (zk.x + zk.y), 0);     // X[0]
-                            xm[bb][nn] = cf(a.spec_scale * (zk.x - zk.y), 0);     // X[L]
-                        } else {
-                            const cf pk = zk + conj(zm), dk = zk - conj(zm);
-                            const cf ok = pk + mul_mi(wk * dk);
-                            const cf pm = zm + conj(zk), dm = zm - conj(zk);
-                            const cf wm(-wk.x, wk.y);                               // W_n^(L-k) = -conj(W_n^k)
-                            const cf om = pm + mul_mi(wm * dm);
-                            xk[bb][nn] = cf(hs * wi * ok.x, hs * wi * ok.y);
-                            xm[bb][nn] = cf(hs * wi * om.x, hs * wi * om.y);
-                        }
+                for (int nn = 0; nn < NI; ++nn) {
+                    const cf zk = U[nn * LENP + p];
+                    const cf zm = U[(slotB * NCH + nn) * LENP + colB];
+                    if (dc) {
+                        xk[nn] = cf(a.spec_scale * (zk.x + zk.y), 0);     // X[0]
+                        xm[nn] = cf(a.spec_scale * (zk.x - zk.y), 0);     // X[L]
+                    } else {
+                        const cf pk = zk + conj(zm), dk = zk - conj(zm);
+                        const cf ok = pk + mul_mi(wk * dk);
+                        const cf pm = zm + conj(zk), dm = zm - conj(zk);
+                        const cf wm(-wk.x, wk.y);                               // W_n^(L-k) = -conj(W_n^k)
+                        const cf om = pm + mul_mi(wm * dm);
+                        xk[nn] = cf(hs * wi * ok.x, hs * wi * ok.y);
+                        xm[nn] = cf(hs * wi * om.x, hs * wi * om.y);
                     }
                 }
-                if (a.Xs) {     // the MS threads of a pair share the stores: input channels [ms NI/MS, (ms+1) NI/MS)
+                if (a.Xs) {
 #pragma unroll
-                    for (int bb = 0; bb < BG; ++bb) {
-                        if (bb >= nb) break;
-                        cf* xo = a.Xs + (size_t)(b0 + bb) * a.xs_b;
+                    for (int only = 0; only < 1; ++only) {
+                        if (0 >= nb) break;
+                        cf* xo = a.Xs + (size_t)(b + only) * a.xs_b;
 #pragma unroll
-                        for (int n2 = 0; n2 < NI / MS; ++n2) {
-                            const int nn = ms * (NI / MS) + n2;
-                            cf vk = xk[bb][0], vm = xm[bb][0];
+                        for (int n2 = 0; n2 < NI; ++n2) {
+                            const int nn = w256 * NI + n2;
+                            cf vk = xk[0], vm = xm[0];
 #pragma unroll
                             for (int e = 1; e < NI; ++e)
-                                if (e == nn) { vk = xk[bb][e]; vm = xm[bb][e]; }
+                                if (e == nn) { vk = xk[e]; vm = xm[e]; }
                             st_nt(xo, ESZ * ((unsigned)nn * (unsigned)a.xs_n + ik), vk);
                             if (im != ik) st_nt(xo, ESZ * ((unsigned)nn * (unsigned)a.xs_n + im), vm);
                         }
@@ -384,37 +386,31 @@ __global__ void __launch_bounds__(256 * NTH, ((NTH == 2 && MS == 1) || P3V == 1 
             }
             if (!DO_INV) continue;
             if (a.dbg_times && tid == 0) a.dbg_times[(size_t)blockIdx.x * 8 + 6] = clock64();
-            if (MS > 1) __syncthreads();
             if (!valid) continue;
             const cf cwk = conj(wk);
-            // response rows: row m2 + PFD is requested before row m2 is used (PFD + 1 rows of 2 NI values in registers);
-            // plane (m, n) is a workgroup-uniform base (scalar arithmetic), the bin the lane's 32-bit offset
-            constexpr int NB = PFD + 1;
-            cf hrows[NB][2 * NI];
+            // response row m: 2 NI values in registers, loaded and then used; plane (m, n) is a workgroup-uniform base
+            // (scalar arithmetic: the row index goes through readfirstlane, which also keeps the compiler from forming all
+            // NO x NI plane bases ahead of the loop -- 198 -> 235 registers at 16 channels), the bin the lane's 32-bit offset
+            cf hrow[2 * NI];
             const unsigned hoff_k = a.dbg_hfake ? ESZ * (ik & 63u) : ESZ * ik, hoff_m = a.dbg_hfake ? ESZ * (im & 63u) : ESZ * im;
             auto load_row = [&](int m2, cf* dst) {
-                const cf* Hm = a.H + (size_t)__builtin_amdgcn_readfirstlane(ms * (NO / MS) + m2) * a.hs_m;
+                const cf* Hm = a.H + (size_t)__builtin_amdgcn_readfirstlane(w256 * NO + m2) * a.hs_m;
 #pragma unroll
                 for (int nn = 0; nn < NI; ++nn) {
                     dst[nn] = at(Hm + (size_t)nn * a.hs_n, hoff_k);
                     dst[NI + nn] = at(Hm + (size_t)nn * a.hs_n, hoff_m);
                 }
             };
-            if (HAS_H) {
 #pragma unroll
-                for (int i = 0; i < PFD; ++i)
-                    if (i < NO / MS) load_row(i, hrows[i]);
-            }
-#pragma unroll
-            for (int m2 = 0; m2 < NO / MS; ++m2) {
-                const int m = ms * (NO / MS) + m2;
+            for (int m2 = 0; m2 < NO; ++m2) {
+                const int m = w256 * NO + m2;
                 cf hkv[NI], hmv[NI];
                 if (HAS_H) {
-                    if (m2 + PFD < NO / MS) load_row(m2 + PFD, hrows[(m2 + PFD) % NB]);
+                    load_row(m2, hrow);
 #pragma unroll
                     for (int nn = 0; nn < NI; ++nn) {
-                        hkv[nn] = hrows[m2 % NB][nn];
-                        hmv[nn] = hrows[m2 % NB][NI + nn];
+                        hkv[nn] = hrow[nn];
+                        hmv[nn] = hrow[NI + nn];
                         if (a.conj_h) {
                             hkv[nn].y = -hkv[nn].y;
                             hmv[nn].y = -hmv[nn].y;
@@ -422,22 +418,22 @@ __global__ void __launch_bounds__(256 * NTH, ((NTH == 2 && MS == 1) || P3V == 1 
                     }
                 }
 #pragma unroll
-                for (int bb = 0; bb < BG; ++bb) {
+                for (int only = 0; only < 1; ++only) {
                     cf yk, ym;
                     if (HAS_H) {
                         yk = cf(0, 0);
                         ym = cf(0, 0);
 #pragma unroll
                         for (int nn = 0; nn < NI; ++nn) {
-                            fma_cx(yk, hkv[nn], xk[bb][nn]);
-                            fma_cx(ym, hmv[nn], xm[bb][nn]);
+                            fma_cx(yk, hkv[nn], xk[nn]);
+                            fma_cx(ym, hmv[nn], xm[nn]);
                         }
                     } else {
-                        yk = xk[bb][0];
-                        ym = xm[bb][0];
+                        yk = xk[0];
+                        ym = xm[0];
 #pragma unroll
                         for (int e = 1; e < NI; ++e)
-                            if (e == m) { yk = xk[bb][e]; ym = xm[bb][e]; }
+                            if (e == m) { yk = xk[e]; ym = xm[e]; }
                     }
                     cf zk, zm;
                     if (dc) {      // Zf[0] from the real parts of Y[0] and Y[L] (C2R semantics)
@@ -449,127 +445,8 @@ __global__ void __launch_bounds__(256 * NTH, ((NTH == 2 && MS == 1) || P3V == 1 
                         zk = s_ + t_;
                         zm = conj(s_ - t_);
                     }
-                    U[((2 * bb) * NCH + m) * LENP + p] = zk;
-                    if (im != ik && !dc) U[((2 * bb + slotB) * NCH + m) * LENP + colB] = zm;
-                }
-            }
-        }
-    }
-    }
-    if constexpr (P3V == 1) {
-        // ---- P3 in three sweeps (BG batch items per workgroup, 256*BG threads), so that a response row fetched for a
-        // bin serves the BG spectra the workgroup holds -- the response's trips through the L2 -> L1 path (measured
-        // 31 B/clk/CU for 8-byte loads: 245 KB per row pair = 8k cycles, the largest single cost of the one-item form)
-        // shrink by BG, and the product runs one thread per BIN (not per pair) with 2 NI + 2 NI values in registers:
-        //   a) split step per (item, pair): spectrum written back in place (and to global memory for the backward pass)
-        //   b) product per bin: Y[item][:, bin] = H[:, :, bin] X[item][:, bin], in place
-        //   c) Hermitian pre-step per (item, pair), in place
-        static_assert(HAS_H && DO_INV && NTH == BG, "three-sweep product: response + inverse half, 256 threads per item");
-        const cf wr = a.W[r];
-        const real_t hs = (real_t)0.5 * a.spec_scale, wi = a.spec_interior2 ? (real_t)2 : (real_t)1;
-        const real_t ph = a.pre_half ? (real_t)0.5 : (real_t)1;
-        const int bbt = tid / 256;                      // the batch item this thread serves in sweeps a and c
-        for (int p0 = 0; p0 < LEN; p0 += 256) {        // ---- a
-            const int p = p0 + (tid & 255);
-            int slotB = 0, colB = 0;
-            bool dc = false;
-            if (!(p < LEN && bbt < nb && pair_of(r, selfm, p, LEN, slotB, colB, dc))) continue;
-            const unsigned ik = (unsigned)r * LEN + p;
-            const unsigned im = dc ? (unsigned)a.L : (unsigned)(slotB ? rm : r) * LEN + colB;
-            const cf wk = wr * ws[p];
-            cf* xo = a.Xs ? a.Xs + (size_t)(b0 + bbt) * a.xs_b : nullptr;
-#pragma unroll
-            for (int nn = 0; nn < NI; ++nn) {
-                cf* pk = U + ((2 * bbt) * NCH + nn) * LENP + p;
-                cf* pm = U + ((2 * bbt + slotB) * NCH + nn) * LENP + colB;
-                const cf zk = *pk, zm = *pm;
-                cf xk, xm;
-                if (dc) {
-                    xk = cf(a.spec_scale * (zk.x + zk.y), 0);     // X[0]
-                    xm = cf(a.spec_scale * (zk.x - zk.y), 0);     // X[L]
-                    nyq[bbt * NCH + nn] = xm;
-                } else {
-                    const cf pk_ = zk + conj(zm), dk = zk - conj(zm);
-                    const cf ok = pk_ + mul_mi(wk * dk);
-                    const cf pm_ = zm + conj(zk), dm = zm - conj(zk);
-                    const cf wm(-wk.x, wk.y);
-                    const cf om = pm_ + mul_mi(wm * dm);
-                    xk = cf(hs * wi * ok.x, hs * wi * ok.y);
-                    xm = cf(hs * wi * om.x, hs * wi * om.y);
-                    if (im != ik) *pm = xm;
-                }
-                *pk = xk;
-                if (xo) {
-                    st_nt(xo, ESZ * ((unsigned)nn * (unsigned)a.xs_n + ik), xk);
-                    if (im != ik) st_nt(xo, ESZ * ((unsigned)nn * (unsigned)a.xs_n + im), xm);
-                }
-            }
-        }
-        __syncthreads();
-        {                                                // ---- b: one thread per bin held by the workgroup
-            const int nbins = (selfm ? 1 : 2) * LEN + (r == 0 ? 1 : 0);
-            for (int j = tid; j < nbins; j += NT) {
-                const bool isnyq = j == (selfm ? 1 : 2) * LEN;
-                const int slot = isnyq ? 0 : j / LEN, col = isnyq ? 0 : j - slot * LEN;
-                const unsigned ib = isnyq ? (unsigned)a.L : (unsigned)(slot ? rm : r) * LEN + col;
-                cf x[BG][NI];
-#pragma unroll
-                for (int bb = 0; bb < BG; ++bb)
-#pragma unroll
-                    for (int nn = 0; nn < NI; ++nn)
-                        x[bb][nn] = isnyq ? nyq[bb * NCH + nn] : U[((2 * bb + slot) * NCH + nn) * LENP + col];
-                const unsigned hoff = ESZ * ib;
-                // MC response rows requested together (MC*NI loads in flight per thread): the sweep is a chain of
-                // NO/MC load round trips, each ~3.5k cycles under the kernel's own traffic -- not NO of them
-                // (MC = 4 rows in flight spills under the 128-register cap of this form and measured slower: 109 us against 95)
-                constexpr int MC = 1;
-#pragma unroll
-                for (int m0 = 0; m0 < NO; m0 += MC) {
-                    cf h[MC][NI];
-#pragma unroll
-                    for (int mc = 0; mc < MC; ++mc) {
-                        const cf* Hm = a.H + (size_t)(m0 + mc) * a.hs_m;
-#pragma unroll
-                        for (int nn = 0; nn < NI; ++nn) h[mc][nn] = at(Hm + (size_t)nn * a.hs_n, hoff);
-                    }
-#pragma unroll
-                    for (int mc = 0; mc < MC; ++mc) {
-                        if (a.conj_h) {
-#pragma unroll
-                            for (int nn = 0; nn < NI; ++nn) h[mc][nn].y = -h[mc][nn].y;
-                        }
-#pragma unroll
-                        for (int bb = 0; bb < BG; ++bb) {
-                            cf y(0, 0);
-#pragma unroll
-                            for (int nn = 0; nn < NI; ++nn) fma_cx(y, h[mc][nn], x[bb][nn]);
-                            if (isnyq) nyq[bb * NCH + m0 + mc] = y;
-                            else U[((2 * bb + slot) * NCH + m0 + mc) * LENP + col] = y;
-                        }
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        for (int p0 = 0; p0 < LEN; p0 += 256) {        // ---- c
-            const int p = p0 + (tid & 255);
-            int slotB = 0, colB = 0;
-            bool dc = false;
-            if (!(p < LEN && bbt < nb && pair_of(r, selfm, p, LEN, slotB, colB, dc))) continue;
-            const bool self = !dc && slotB == 0 && colB == p;
-            const cf cwk = conj(wr * ws[p]);
-#pragma unroll
-            for (int m = 0; m < NO; ++m) {
-                cf* pk = U + ((2 * bbt) * NCH + m) * LENP + p;
-                cf* pm = U + ((2 * bbt + slotB) * NCH + m) * LENP + colB;
-                const cf yk = *pk, ym = dc ? nyq[bbt * NCH + m] : *pm;
-                if (dc) {      // Zf[0] from the real parts of Y[0] and Y[L] (C2R semantics)
-                    *pk = cf(yk.x + ym.x, yk.x - ym.x);
-                } else {
-                    const cf xa(ph * yk.x, ph * yk.y), xb(ph * ym.x, ph * ym.y);
-                    const cf s_ = xa + conj(xb), t_ = mul_i(cwk * (xa - conj(xb)));
-                    *pk = s_ + t_;
-                    if (!self) *pm = conj(s_ - t_);
+                    U[((2 * only) * NCH + m) * LENP + p] = zk;
+                    if (im != ik && !dc) U[((2 * only + slotB) * NCH + m) * LENP + colB] = zm;
                 }
             }
         }
@@ -578,10 +455,10 @@ __global__ void __launch_bounds__(256 * NTH, ((NTH == 2 && MS == 1) || P3V == 1 
     __syncthreads();
     if (a.dbg_times && tid == 0) a.dbg_times[(size_t)blockIdx.x * 8 + 3] = clock64();
     // ---- P4: first stage of the inverse row FFTs, in place (a thread owns positions tb + B*i of its row)
-    for (int item = tid; item < BG * 2 * B * NO; item += NT) {
-        const int m = item % NO, tb = (item / NO) % B, bs = item / (NO * B);
-        if (((bs & 1) && selfm) || (bs >> 1) >= nb) continue;
-        cf* u = U + (bs * NCH + m) * LENP + tb;
+    for (int item = tid; item < 2 * B * NO; item += NT) {
+        const int m = item % NO, tb = (item / NO) % B, slot = item / (NO * B);
+        if ((slot && selfm) || 0 >= nb) continue;
+        cf* u = U + (slot * NCH + m) * LENP + tb;
         cf v[A];
 #pragma unroll
         for (int ta = 0; ta < A; ++ta) v[ta] = u[ta * B];
@@ -594,12 +471,13 @@ __global__ void __launch_bounds__(256 * NTH, ((NTH == 2 && MS == 1) || P3V == 1 
     if (a.dbg_times && tid == 0) a.dbg_times[(size_t)blockIdx.x * 8 + 4] = clock64();
     // ---- P5: second stage, inter-pass twiddle conj(W_L^(row*c)), store
     {
-        cf* S2b = a.S2 + (size_t)b0 * bstride_o;
-        for (int row0 = 0; row0 < BG * 2 * NO; row0 += RPR) {
+        cf* S2b = a.S2 + (size_t)b * bstride_o;
+        for (int row0 = 0; row0 < 2 * NO; row0 += RPR) {
             const int rl = row0 + tid % RPR, ka = tid / RPR;
+            // PINNED, as in P1: bs = slot + 2 * over, over = 0 for every row that passes the first test
             const int bs = rl / NO, m = rl % NO;
-            const int slot = bs & 1, bb = bs >> 1;
-            if (rl >= BG * 2 * NO || (slot && selfm) || bb >= nb) continue;
+            const int slot = bs & 1, over = bs >> 1;
+            if (rl >= 2 * NO || (slot && selfm) || over >= nb) continue;
             const int row = slot ? rm : r;
             cf v[B];
             const cf* u = U + (bs * NCH + m) * LENP + ka * B;
@@ -607,7 +485,7 @@ __global__ void __launch_bounds__(256 * NTH, ((NTH == 2 && MS == 1) || P3V == 1 
             for (int tb = 0; tb < B; ++tb) v[tb] = u[tb];
             RegFFT<real_t, B, true>::run(v);
             const cf w1 = a.W[2 * row * ka];
-            const unsigned dst0 = (unsigned)bb * bstride_o + (unsigned)row * (unsigned)a.L2 * NO + m;
+            const unsigned dst0 = (unsigned)over * bstride_o + (unsigned)row * (unsigned)a.L2 * NO + m;
 #pragma unroll
             for (int kb = 0; kb < B; ++kb) {
                 const int c = ka + A * kb;
@@ -978,7 +856,6 @@ int spec_plan_lean(int nfft) {
 namespace FL_SPEC_NS {
 
 static int g_spec_vt = 0, g_spec_rg = 0;      // 0 = pick per shape (below); fl_debug_set_spec overrides
-static size_t g_cols_inv_min_lds = [] { const char* e = getenv("FLAMO_COLS_INV_LDS"); return e ? (size_t)atol(e) : (size_t)0; }();
 
 // Column-pass tile: virtual columns per workgroup and loads in flight per thread group. Measured under graph replay on
 // the whole training step (tools/dbg/graph_ab.py): 16 virtual columns (27 KB of LDS, five workgroups per CU) win for
@@ -1020,8 +897,7 @@ static void launch_cols(bool inverse, const ColsArgs& a, unsigned nblk, hipStrea
     constexpr int LEN = A * B, LENP = LEN | 1;
 #define FL_COLS(VT_, RG_)                                                                                        \
     {                                                                                                            \
-        size_t lds = ((size_t)VT_ * LENP + LEN + (size_t)VT_ * B) * sizeof(cf);                                  \
-        if (inverse && g_cols_inv_min_lds > lds) lds = g_cols_inv_min_lds;                                       \
+        const size_t lds = ((size_t)VT_ * LENP + LEN + (size_t)VT_ * B) * sizeof(cf);                            \
         if constexpr (A * VT_ <= 256) {                                                                          \
             if (inverse && a.Sg) {                                                                               \
                 hipLaunchKernelGGL((spec_cols_inv<A, B, VT_, RG_, true, true>), dim3(nblk), dim3(256), lds, st, a); \
@@ -1093,7 +969,7 @@ static int cols_launch(bool inverse, const ColsArgs& a, int Bn, hipStream_t st) 
     return FL_OK;
 }
 
-static int g_mid_bg = 1, g_mid_hfake = 0, g_mid_pfd = 0;
+static int g_mid_hfake = 0;
 static long long* g_mid_times = nullptr;
 }  // namespace FL_SPEC_NS
 // tuning: cycle sums per phase of spec_gradh_loop (8 per workgroup), shared by the float32 and float64 builds
@@ -1104,101 +980,33 @@ extern long long* g_gradloop_times;
 #endif
 namespace FL_SPEC_NS {
 
-template <int A, int B, int NI, int NO, int BG, int MS>
-static void launch_mid_bg(const MidArgs& a, hipStream_t st) {
-    constexpr int LEN = A * B, LENP = LEN | 1, NCH = NI > NO ? NI : NO;
-    const size_t lds = ((size_t)BG * 2 * NCH * LENP + 2 * LEN + 2 * B + BG * NCH) * sizeof(cf);
-    const int P = a.L1 / 2 + 1;
-    const unsigned nblk = (unsigned)(cdiv_i(P, 8) * 8 * cdiv_i(a.Bn, BG));
-    if (a.S2) {
-        if (a.H) {
-            if (g_mid_pfd == 1) hipLaunchKernelGGL((spec_mid<A, B, NI, NO, true, true, BG, MS, 1>), dim3(nblk), dim3(256 * MS), lds, st, a);
-            else if (g_mid_pfd == 2) hipLaunchKernelGGL((spec_mid<A, B, NI, NO, true, true, BG, MS, 2>), dim3(nblk), dim3(256 * MS), lds, st, a);
-            else hipLaunchKernelGGL((spec_mid<A, B, NI, NO, true, true, BG, MS, 0>), dim3(nblk), dim3(256 * MS), lds, st, a);
-        }
-        else if constexpr (NI == NO) hipLaunchKernelGGL((spec_mid<A, B, NI, NO, false, true, BG, MS>), dim3(nblk), dim3(256 * MS), lds, st, a);
-    } else {
-        if constexpr (NI == NO) hipLaunchKernelGGL((spec_mid<A, B, NI, NO, false, false, BG, MS>), dim3(nblk), dim3(256 * MS), lds, st, a);
-    }
-}
-
-template <int A, int B, int NI, int NO>
-static void launch_mid_n(const MidArgs& a, unsigned, hipStream_t st) {
-    // (two batch items per workgroup -- the response row applied to two spectra -- measured slower at config 2:
-    // 104 us with 256 threads, 118 us with 512, against 98 us; the kernel keeps the BG/MS parameters for that experiment)
-    // response present + inverse half: BG batch items per workgroup with the three-sweep product (the response row of a bin
-    // is fetched once per BG items)
-    if (a.H && a.S2 && g_mid_bg == 5) {       // one item per workgroup, three-sweep product
-        constexpr int LEN = A * B, LENP = LEN | 1, NCH = NI > NO ? NI : NO;
-        const int P = a.L1 / 2 + 1;
-        const size_t lds = ((size_t)2 * NCH * LENP + 2 * LEN + 2 * B + NCH) * sizeof(cf);
-        const unsigned nblk = (unsigned)(cdiv_i(P, 8) * 8 * a.Bn);
-        hipLaunchKernelGGL((spec_mid<A, B, NI, NO, true, true, 1, 1, 0, 1, 1>), dim3(nblk), dim3(256), lds, st, a);
-        return;
-    }
-    if (a.H && a.S2 && a.Bn > 1 && g_mid_bg >= 2) {
-        constexpr int LEN = A * B, LENP = LEN | 1, NCH = NI > NO ? NI : NO;
-        const int P = a.L1 / 2 + 1;
-        if constexpr ((size_t)2 * 2 * NCH * LENP * sizeof(cf) <= 70 * 1024) {
-            if (g_mid_bg == 2 || a.Bn < 4 || (size_t)4 * 2 * NCH * LENP * sizeof(cf) > 150 * 1024) {
-                const size_t lds = ((size_t)2 * 2 * NCH * LENP + 2 * LEN + 2 * B + 2 * NCH) * sizeof(cf);
-                const unsigned nblk = (unsigned)(cdiv_i(P, 8) * 8 * cdiv_i(a.Bn, 2));
-                hipLaunchKernelGGL((spec_mid<A, B, NI, NO, true, true, 2, 1, 0, 2, 1>), dim3(nblk), dim3(512), lds, st, a);
-                return;
-            }
-        }
-        if constexpr ((size_t)4 * 2 * NCH * LENP * sizeof(cf) <= 150 * 1024) {
-            if (g_mid_bg == 4 && a.Bn >= 4) {
-                const size_t lds = ((size_t)4 * 2 * NCH * LENP + 2 * LEN + 2 * B + 4 * NCH) * sizeof(cf);
-                const unsigned nblk = (unsigned)(cdiv_i(P, 8) * 8 * cdiv_i(a.Bn, 4));
-                hipLaunchKernelGGL((spec_mid<A, B, NI, NO, true, true, 4, 1, 0, 4, 1>), dim3(nblk), dim3(1024), lds, st, a);
-                return;
-            }
-        }
-    }
-    launch_mid_bg<A, B, NI, NO, 1, 1>(a, st);
-}
-
-// equal channel counts, one batch item per workgroup, no tuning variants (the lengths beyond the three BASELINE ones)
-template <int A, int B, int N>
-static void launch_mid_lean_n(const MidArgs& a, hipStream_t st) {
+// The row kernel for NI -> NO channels: with the response and the inverse half, the inverse half alone, or the spectrum alone
+// (the last two: equal channel counts).  EQUAL_ONLY: equal channel counts of 2 / 4 / 8 / 16 (float64, and the lengths beyond
+// the three BASELINE ones); otherwise also the unequal pairs up to 8 channels.
+template <int A, int B, bool EQUAL_ONLY>
+static int launch_mid(const MidArgs& a, int NI, int NO, hipStream_t st) {
     constexpr int LEN = A * B, LENP = LEN | 1;
-    const size_t lds = ((size_t)2 * N * LENP + 2 * LEN + 2 * B + N) * sizeof(cf);
-    const int P = a.L1 / 2 + 1;
-    const unsigned nblk = (unsigned)(cdiv_i(P, 8) * 8 * a.Bn);
-    if (a.S2) {
-        if (a.H) hipLaunchKernelGGL((spec_mid<A, B, N, N, true, true, 1, 1, 0>), dim3(nblk), dim3(256), lds, st, a);
-        else hipLaunchKernelGGL((spec_mid<A, B, N, N, false, true, 1, 1>), dim3(nblk), dim3(256), lds, st, a);
-    } else {
-        hipLaunchKernelGGL((spec_mid<A, B, N, N, false, false, 1, 1>), dim3(nblk), dim3(256), lds, st, a);
-    }
-}
-
-template <int A, int B>
-static int launch_mid_lean(const MidArgs& a, int NI, int NO, hipStream_t st) {
-    if (NI == NO) {
-        switch (NI) {
-            case 2: launch_mid_lean_n<A, B, 2>(a, st); return FL_OK;
-            case 4: launch_mid_lean_n<A, B, 4>(a, st); return FL_OK;
-            case 8: launch_mid_lean_n<A, B, 8>(a, st); return FL_OK;
-            case 16: launch_mid_lean_n<A, B, 16>(a, st); return FL_OK;
-        }
-    }
-    set_error("spectral mid: no kernel for %d -> %d channels at this transform length (2, 4, 8 or 16 channels, equal in and out)", NI, NO);
-    return FL_ERR_UNSUPPORTED;
-}
-
-template <int A, int B>
-static int launch_mid(const MidArgs& a, int NI, int NO, unsigned nblk, hipStream_t st) {
-#define FL_MID(NI_, NO_)                              \
-    if (NI == NI_ && NO == NO_) {                     \
-        launch_mid_n<A, B, NI_, NO_>(a, nblk, st);    \
-        return FL_OK;                                 \
+    const unsigned nblk = (unsigned)(cdiv_i(a.L1 / 2 + 1, 8) * 8 * a.Bn);
+    // (the last NCH values are the slot of a retired form of the product: nothing reads them, and they stay in the request
+    // so that every launch asks for the LDS it always has)
+#define FL_MID(NI_, NO_)                                                                                             \
+    if (NI == NI_ && NO == NO_) {                                                                                    \
+        constexpr int NCH = NI_ > NO_ ? NI_ : NO_;                                                                   \
+        const size_t lds = ((size_t)2 * NCH * LENP + 2 * LEN + 2 * B + NCH) * sizeof(cf);                            \
+        if (a.S2 && a.H) hipLaunchKernelGGL((spec_mid<A, B, NI_, NO_, true, true>), dim3(nblk), dim3(256), lds, st, a); \
+        else if constexpr (NI_ == NO_) {                                                                             \
+            if (a.S2) hipLaunchKernelGGL((spec_mid<A, B, NI_, NO_, false, true>), dim3(nblk), dim3(256), lds, st, a); \
+            else hipLaunchKernelGGL((spec_mid<A, B, NI_, NO_, false, false>), dim3(nblk), dim3(256), lds, st, a);    \
+        }                                                                                                            \
+        return FL_OK;                                                                                                \
     }
     FL_MID(2, 2) FL_MID(4, 4) FL_MID(8, 8) FL_MID(16, 16)
-    FL_MID(2, 4) FL_MID(4, 2) FL_MID(2, 8) FL_MID(8, 2) FL_MID(4, 8) FL_MID(8, 4)
+    if constexpr (!EQUAL_ONLY) {
+        FL_MID(2, 4) FL_MID(4, 2) FL_MID(2, 8) FL_MID(8, 2) FL_MID(4, 8) FL_MID(8, 4)
+    }
 #undef FL_MID
-    set_error("spectral mid: no kernel for %d -> %d channels", NI, NO);
+    if (EQUAL_ONLY) set_error("spectral mid: no kernel for %d -> %d channels at this transform length (2, 4, 8 or 16 channels, equal in and out)", NI, NO);
+    else set_error("spectral mid: no kernel for %d -> %d channels", NI, NO);
     return FL_ERR_UNSUPPORTED;
 }
 
@@ -1349,11 +1157,16 @@ int fl_debug_set_spec_times(void* buf) {
 }
 
 int fl_debug_set_spec(int vt, int rg) {
-    g_spec_vt = (vt == 16 || vt == 32) ? vt : 0;
-    g_spec_rg = (rg % 100 == 1 || rg % 100 == 4 || rg % 100 == 2) ? rg % 100 : 0;
-    g_mid_bg = (rg >= 100) ? (rg / 100) % 10 : 1;
-    g_mid_hfake = (rg / 1000) % 10 == 1;
-    g_mid_pfd = (rg / 10000) % 10;       // rg = 10000*prefetch depth + 1000*fake + 100*bg + load group
+    // rg = 1000*fake + load group; the other digits selected row-kernel variants that no longer exist
+    const int group = rg % 100, fake = rg / 1000;
+    const bool rg_ok = rg >= 0 && (group == 0 || group == 1 || group == 2 || group == 4) && rg - group - 1000 * fake == 0 && fake <= 1;
+    if (!((vt == 0 || vt == 16 || vt == 32) && rg_ok)) {
+        set_error("debug_set_spec: vt=%d rg=%d is not a code (vt 0 / 16 / 32; rg = 1000*fake + load group, fake 0 / 1, group 0 / 1 / 2 / 4)", vt, rg);
+        return FL_ERR_BAD_ARG;
+    }
+    g_spec_vt = vt;
+    g_spec_rg = group;
+    g_mid_hfake = fake;
     return FL_OK;
 }
 #endif
@@ -1452,25 +1265,20 @@ int FL_SPEC_FN(fl_spec_mid)(const void* S, void* S2, void* Xs, long xs_b, long x
     const size_t nblk = (size_t)cdiv_i(P, 8) * 8 * Bn;
     FL_REQUIRE(nblk < (1ull << 31), "spec_mid: grid too large");
     hipStream_t st = (hipStream_t)stream;
+    constexpr bool F64 = sizeof(real_t) == 8;      // float64: equal channel counts at every plan length
     switch (a.L2) {
-#ifdef FL_F64       // float64: one workgroup per (row pair, batch item), equal channel counts, at every plan length
-        case 240: rc = launch_mid_lean<16, 15>(a, NI, NO, st); break;
-        case 320: rc = launch_mid_lean<16, 20>(a, NI, NO, st); break;
-        case 480: rc = launch_mid_lean<32, 15>(a, NI, NO, st); break;
-#else
-        case 240: rc = launch_mid<16, 15>(a, NI, NO, (unsigned)nblk, st); break;
-        case 320: rc = launch_mid<16, 20>(a, NI, NO, (unsigned)nblk, st); break;
-        case 480: rc = launch_mid<32, 15>(a, NI, NO, (unsigned)nblk, st); break;
-#endif
-        case 32: rc = launch_mid_lean<8, 4>(a, NI, NO, st); break;
-        case 64: rc = launch_mid_lean<8, 8>(a, NI, NO, st); break;
-        case 128: rc = launch_mid_lean<16, 8>(a, NI, NO, st); break;
-        case 160: rc = launch_mid_lean<16, 10>(a, NI, NO, st); break;
-        case 256: rc = launch_mid_lean<16, 16>(a, NI, NO, st); break;
-        case 50: rc = launch_mid_lean<2, 25>(a, NI, NO, st); break;
-        case 100: rc = launch_mid_lean<4, 25>(a, NI, NO, st); break;
-        case 200: rc = launch_mid_lean<8, 25>(a, NI, NO, st); break;
-        case 400: rc = launch_mid_lean<16, 25>(a, NI, NO, st); break;
+        case 240: rc = launch_mid<16, 15, F64>(a, NI, NO, st); break;
+        case 320: rc = launch_mid<16, 20, F64>(a, NI, NO, st); break;
+        case 480: rc = launch_mid<32, 15, F64>(a, NI, NO, st); break;
+        case 32: rc = launch_mid<8, 4, true>(a, NI, NO, st); break;
+        case 64: rc = launch_mid<8, 8, true>(a, NI, NO, st); break;
+        case 128: rc = launch_mid<16, 8, true>(a, NI, NO, st); break;
+        case 160: rc = launch_mid<16, 10, true>(a, NI, NO, st); break;
+        case 256: rc = launch_mid<16, 16, true>(a, NI, NO, st); break;
+        case 50: rc = launch_mid<2, 25, true>(a, NI, NO, st); break;
+        case 100: rc = launch_mid<4, 25, true>(a, NI, NO, st); break;
+        case 200: rc = launch_mid<8, 25, true>(a, NI, NO, st); break;
+        case 400: rc = launch_mid<16, 25, true>(a, NI, NO, st); break;
         default: set_error("spec_mid: unsupported row length %d", a.L2); return FL_ERR_UNSUPPORTED;
     }
     if (rc) return rc;

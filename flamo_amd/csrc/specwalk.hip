@@ -851,10 +851,7 @@ static int g_walk_wgs = 0;        // workgroups of the forward walking kernel (0
 static int g_walk_slices = 0;     // batch slices of the backward walking kernel (0: CUs / row pairs)
 static long long* g_walk_times = nullptr;
 static long long* g_walk_stamps = nullptr;      // fl_debug_set_walk_stamps
-static int g_walk_nsc = 2;        // output-channel groups of the backward kernel (tuning: fl_debug_set_walk mode 14 -> 4)
-static int g_walk_fc = [] { const char* e = getenv("FLAMO_WALK_FC"); return e ? atoi(e) : 38; }();      // cost of a workgroup's first row pair, in twentieths of a unit
-static int g_walk_fc2 = [] { const char* e = getenv("FLAMO_WALK_FC2"); return e ? atoi(e) : 38; }();    // ... of changing to the next one
-static int g_walk_us = [] { const char* e = getenv("FLAMO_WALK_US"); return e ? atoi(e) : 16; }();      // a unit of a self-mirrored row pair
+static int g_walk_nsc = 2;        // output-channel groups of the backward kernel (tuning: fl_debug_set_walk mode 15 -> 1)
 
 long long* walk_successor_stamp() { return g_walk_stamps ? g_walk_stamps + 2 * kMaxWalkWgs : nullptr; }
 
@@ -912,7 +909,11 @@ int fl_wall_clock_khz(void) {
 }
 
 int fl_debug_set_walk(int mode, int wgs, int slices, void* times) {
-    g_walk_nsc = mode == 14 ? 4 : mode == 15 ? 1 : 2;
+    if (mode != 0 && mode != 1 && mode != 15) {
+        set_error("debug_set_walk: mode %d is not a code (0: off, 1: on, 15: on, all output channels per workgroup at 8 -> 8 channels)", mode);
+        return FL_ERR_BAD_ARG;
+    }
+    g_walk_nsc = mode == 15 ? 1 : 2;
     g_walk = mode;
     g_walk_wgs = wgs;
     g_walk_slices = slices;
@@ -945,7 +946,6 @@ int fl_spec_gradh_slices(int nfft, int Bn) {
     // partial sums); batch slices only beyond that
     const int P = l1 / 2 + 1;
     int ns = device_cus() / (2 * P);
-    if (g_walk_nsc == 4) ns = 1;
     if (g_walk_nsc == 1) ns = device_cus() / P;
     if (ns < 1) ns = 1;
     return ns < Bn ? ns : Bn;
@@ -986,16 +986,15 @@ int fl_spec_gradh_walk_f32(const void* Sg, const void* Xp, void* dH_parts, long 
             else hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), lds, st, a);                                                    \
         }                                                                                                                        \
     }
-    // output channels of a row pair over 2 workgroups (one per CU) -- or one for 2 output channels; tuning: over 4 (two per CU);
+    // output channels of a row pair over 2 workgroups (one per CU) -- or one for 2 output channels (and, tuning: mode 15, for
+    // 8 -> 8 channels at 240-bin rows);
     // 8 -> 8 channels: two staging regions per kind, transfers issued by the wavefronts without a stage of their own (DEPTH 2).
     // Round 3 measured that form no faster than owner-wave transfers (69.5 against 68.7 us); since the second stage moved to
     // SIMD 2 and 3 the first stage is the longest path of the FFT step and the eight transfer issues in front of its
-    // arithmetic count: 54.2 against 56.5 us replayed at config 2.  (Mode 17, tuning: the owner-wave form, DEPTH 1.)
+    // arithmetic count: 54.2 against 56.5 us replayed at config 2.
 #define FL_GRADH_ROWS(A_, B_)                                                                                                    \
     if (NI == 8 && NO == 8) {                                                                                                    \
-        if (A_ == 16 && B_ == 15 && g_walk_nsc == 4) FL_GRADH(16, 15, 8, 8, 4, 4, 1)                                             \
-        else if (A_ == 16 && B_ == 15 && g_walk_nsc == 1) FL_GRADH(16, 15, 8, 8, 1, 2, 1)                                        \
-        else if (A_ == 16 && B_ == 15 && g_walk == 17) FL_GRADH(16, 15, 8, 8, 2, 2, 1)                                           \
+        if (A_ == 16 && B_ == 15 && g_walk_nsc == 1) FL_GRADH(16, 15, 8, 8, 1, 2, 1)                                             \
         else FL_GRADH(A_, B_, 8, 8, 2, 2, 2)                                                                                     \
     }                                                                                                                            \
     else if (NI == 4 && NO == 8) FL_GRADH(A_, B_, 4, 8, 2, 2, 1)                                                                 \
@@ -1049,7 +1048,9 @@ int fl_spec_walk_partition(int nfft, int Bn, int n_wg, int* bounds) {
     // round 3: with the earlier 1.55 units per entry the workgroups that enter two row pairs finished 6 % behind the rest).
     // Equal unit COUNTS left the slowest workgroup 13-19 % above the mean.  Costs in twentieths of a unit; the smallest cap for which a greedy sweep needs no more than
     // n_wg ranges (binary search), then the sweep's cuts.
-    const int P = L1 / 2 + 1, U = P * Bn, UC = 20, US = g_walk_us, FC = g_walk_fc, FC2 = g_walk_fc2;
+    constexpr int UC = 20, US = 16;       // a unit, and a unit of a self-mirrored row pair
+    constexpr int FC = 38, FC2 = 38;      // a workgroup's first row pair, and changing to the next one
+    const int P = L1 / 2 + 1, U = P * Bn;
     auto ucost = [&](int u) { const int r = u / Bn; return (r == 0 || 2 * r == L1) ? US : UC; };
     auto sweep = [&](long cap, int* out) {       // number of ranges used; out[i] = first unit of range i
         int n = 0, u = 0;

@@ -126,7 +126,9 @@ size_t fl_spec_aux_elems(int nfft);
 int fl_spec_aux_fill_f32(void* W, int nfft, void* stream);
 /* 1 when (nfft, input channels, output channels) has a fused kernel */
 int fl_spec_supports(int nfft, int n_in, int n_out);
-/* tuning hook: virtual columns per workgroup of the column passes (16 | 32; 0 = per-shape choice), load group (1 | 2 | 4; 0 = auto) */
+/* tuning hook: vt = virtual columns per workgroup of the column passes (16 | 32; 0 = per-shape choice); rg = their load group
+ * (1 | 2 | 4; 0 = auto), plus 1000 to make every bin of fl_spec_mid_* read the first 64 bins' response (isolates the fetch
+ * cost).  Any other value is FL_ERR_BAD_ARG and changes nothing. */
 int fl_debug_set_spec(int vt, int rg);
 /* tuning hook: device buffer of 8 int64 per workgroup of fl_spec_mid_f32 for cycle stamps at its phase boundaries (null: off) */
 int fl_debug_set_spec_times(void* buf);
@@ -175,8 +177,10 @@ int fl_spec_gradh_walk_f32(const void* Sg, const void* Xp, void* dH_parts, long 
                            int nfft, int Bn, int NI, int NO, double scale_g, int interior2_g, const void* out_scale, void* stream);
 /* out[j] = sum_{s < n_parts} parts[s*part_stride + j], j < n complex values (16-byte aligned, n and part_stride even) */
 int fl_sum_parts_c64(const void* parts, long part_stride, int n_parts, void* out, long n, void* stream);
-/* tuning hook: mode 0 switches the walking kernels off (fl_spec_walk_supports -> 0); wgs / slices override the forward
- * kernel's workgroup count and the backward kernel's slice count (0 = per device); times: 8 int64 per workgroup or null */
+/* tuning hook: mode 0 switches the walking kernels off (fl_spec_walk_supports -> 0), 1 is the default, 15 gives a backward
+ * workgroup all output channels at 8 -> 8 channels and 240-bin rows; wgs / slices override the forward kernel's workgroup
+ * count and the backward kernel's slice count (0 = per device); times: 8 int64 per workgroup or null.  Any other mode is
+ * FL_ERR_BAD_ARG and changes nothing. */
 int fl_debug_set_walk(int mode, int wgs, int slices, void* times);
 /* Measurement: with a device buffer of 2 x 1024 + 1 int64 set, every launch of fl_spec_mid_walk_f32 issued (or captured)
  * afterwards stamps the constant-rate device clock (s_memrealtime, fl_wall_clock_khz) when each workgroup w starts and ends

@@ -161,6 +161,44 @@ def test_mimo_variant_hook_accepts_only_the_remaining_codes():
     assert L.fl_mimo_gradw_blocks(256 * 100) == 100
 
 
+def test_spec_hook_accepts_only_the_remaining_codes():
+    """fl_debug_set_spec: tile width 0 / 16 / 32, load group 0 / 1 / 2 / 4, plus 1000 for the fake-response switch; the codes of
+    the removed row-kernel variants (batch groups, three-sweep product, response-row prefetch) and an unknown tile width are
+    errors with a message."""
+    from flamo_amd import _lib
+    L = _lib.lib()
+    try:
+        for ok in ((0, 0), (16, 1), (32, 4), (0, 1000), (16, 1002), (32, 2)):
+            assert L.fl_debug_set_spec(*ok) == 0, ok
+        assert L.fl_spec_cols_blocks_f32(96000, 1, 8) == 60              # 32 virtual columns: four of the 240 columns of 8 channels per workgroup
+        for bad in ((0, 200), (0, 400), (0, 500), (0, 10000), (0, 20002), (8, 0), (0, 3), (0, -1)):
+            assert L.fl_debug_set_spec(*bad) == -1, bad
+            assert L.fl_last_error(), bad
+            assert L.fl_spec_cols_blocks_f32(96000, 1, 8) == 60, bad     # a refused call changes no state
+    finally:
+        assert L.fl_debug_set_spec(0, 0) == 0
+    assert L.fl_spec_cols_blocks_f32(96000, 1, 8) == 120
+
+
+def test_walk_hook_accepts_only_the_remaining_modes():
+    """fl_debug_set_walk: modes 0 (off), 1 (on) and 15 (all output channels per workgroup); the modes of the removed
+    spec_gradh_walk instantiations (14: four channel groups, 17: owner-wave transfers at 8 -> 8 channels) are errors with a
+    message."""
+    from flamo_amd import _lib
+    L = _lib.lib()
+    try:
+        for ok in (0, 15, 1):
+            assert L.fl_debug_set_walk(ok, 0, 0, None) == 0, ok
+        assert L.fl_debug_set_walk(1, 0, 3, None) == 0
+        assert L.fl_spec_gradh_slices(96000, 8) == 3
+        for bad in (14, 17, 2, -1):
+            assert L.fl_debug_set_walk(bad, 0, 0, None) == -1, bad
+            assert L.fl_last_error(), bad
+            assert L.fl_spec_gradh_slices(96000, 8) == 3, bad            # a refused call changes no state
+    finally:
+        assert L.fl_debug_set_walk(1, 0, 0, None) == 0
+
+
 def test_ops_fail_loudly_without_gpu_tensors():
     from flamo_amd import ops
     with pytest.raises(RuntimeError, match="no CPU fallback"):

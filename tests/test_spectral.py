@@ -468,28 +468,6 @@ def test_matrix_cascade_operator_at_other_lengths(gpu, nfft, N):
     assert Hs.shape[0] == min(1001, M - 3) and torch.equal(Hs, Hn[3:3 + Hs.shape[0]])
 
 
-@pytest.mark.parametrize("variant", [2, 4, 5])
-def test_mid_kernel_variants_agree(gpu, variant):
-    """the row kernel's experimental forms (tuning hook: 2 / 4 batch items per workgroup with the three-sweep product, one
-    item with the three-sweep product) give the default form's results (odd batch: the tail group is partial)"""
-    from flamo_amd import _lib, ops
-    nfft, N, B = 96000, 8, 5
-    torch.manual_seed(variant)
-    M = nfft // 2 + 1
-    x = torch.randn(B, nfft, N, device=gpu)
-    H = ops.permute_bins(torch.randn(M, N, N, device=gpu, dtype=torch.complex64) / N ** 0.5, nfft)
-    y0 = ops.spectral_apply(x, H, nfft)
-    _lib.lib().fl_debug_set_spec(0, 100 * variant)
-    try:
-        y1 = ops.spectral_apply(x, H, nfft)
-        xg = x.clone().requires_grad_(True)
-        (g1,) = torch.autograd.grad(ops.spectral_apply(xg, H, nfft).square().sum(), [xg])
-    finally:
-        _lib.lib().fl_debug_set_spec(0, 0)      # back to the per-shape choice
-    (g0,) = torch.autograd.grad(ops.spectral_apply(xg, H, nfft).square().sum(), [xg])
-    assert relerr(y1, y0) < 1e-6 and relerr(g1, g0) < 1e-6
-
-
 @pytest.mark.parametrize("db", [0.0, 30.0])
 def test_cascade_times_matrix_float_evaluation(gpu, db):
     """the float evaluation of the cascade (1 -+ w basis, two sections per packed instruction) in the Matrix-then-cascade

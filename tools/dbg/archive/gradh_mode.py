@@ -1,4 +1,5 @@
-"""spectral_apply forward + backward (graph replay) with a tuning mode of the backward walking kernel:
+"""spectral_apply forward + backward (graph replay) with a tuning mode of the backward walking kernel (1: default, 15: all
+output channels per workgroup):
 python tools/dbg/gradh_mode.py <mode> [nfft N B]   -- run under rocprofv3 --kernel-trace --stats for per-kernel times"""
 import os, sys, time
 import torch
@@ -13,7 +14,7 @@ M = nfft // 2 + 1
 x = torch.randn(B, nfft, N, device=dev)
 H = (torch.randn(M, N, N, device=dev, dtype=torch.complex64) / N ** 0.5)
 Hr = ops.permute_bins(H, nfft).requires_grad_(True)
-_lib.lib().fl_debug_set_walk(mode, 0, 0, None)
+_lib.check(_lib.lib().fl_debug_set_walk(mode, 0, 0, None), "debug_set_walk")
 gs = GraphedStep(lambda xx: ops.mean_square(ops.spectral_apply(xx, Hr, nfft)), (x,), [Hr])
 for _ in range(60):
     gs.replay()

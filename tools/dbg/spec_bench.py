@@ -20,7 +20,7 @@ args = ap.parse_args()
 dev = torch.device("cuda:0")
 nfft, N, B = args.nfft, args.n, args.batch
 M = nfft // 2 + 1
-_lib.lib().fl_debug_set_spec(args.vt, args.rg)
+assert _lib.lib().fl_debug_set_spec(args.vt, args.rg) == 0, _lib.lib().fl_last_error()
 torch.manual_seed(0)
 x = torch.randn(B, nfft, N, device=dev)
 H = ops.permute_bins(torch.randn(M, N, N, device=dev, dtype=torch.complex64) / N ** 0.5, nfft).requires_grad_(True)
@@ -52,19 +52,17 @@ for with_x in (False, True):
         tot += ms * n / args.steps
     print(f"   sum of timed kernels {tot * 1e3:.1f} us")
 
-# ---- mid-kernel variants (tuning): response-row prefetch modes, no-response floor
+# ---- mid kernel alone: with the response, and the no-response floor
 S = ops._spec_cols_fwd(x, nfft, 0.0)
 Hp = ops._h_planar(H.detach(), True)
-for pf in (1, 5, 2, 4):
-    _lib.lib().fl_debug_set_spec(args.vt, 100 * pf + args.rg)
-    for _ in range(3):
-        ops._spec_mid(S.clone(), B, N, N, nfft, Hp, False, True, True, 1.0, 0, 0)
-    torch.cuda.synchronize()
-    ops.kernel_timer.reset(True)
-    for _ in range(10):
-        ops._spec_mid(S.clone(), B, N, N, nfft, Hp, False, True, True, 1.0, 0, 0)
-    torch.cuda.synchronize()
-    print(f"mid pf={pf}:", {k: round(v[1] * 1e3, 1) for k, v in ops.kernel_timer.summary().items()})
+for _ in range(3):
+    ops._spec_mid(S.clone(), B, N, N, nfft, Hp, False, True, True, 1.0, 0, 0)
+torch.cuda.synchronize()
+ops.kernel_timer.reset(True)
+for _ in range(10):
+    ops._spec_mid(S.clone(), B, N, N, nfft, Hp, False, True, True, 1.0, 0, 0)
+torch.cuda.synchronize()
+print("mid with response:", {k: round(v[1] * 1e3, 1) for k, v in ops.kernel_timer.summary().items()})
 ops.kernel_timer.reset(True)
 for _ in range(10):
     ops._spec_mid(S.clone(), B, N, N, nfft, None, False, True, True, 1.0, 0, 0)
@@ -75,9 +73,7 @@ ops.kernel_timer.enabled = False
 
 # ---- phase timeline of the mid kernel (cycle stamps of one lane per workgroup)
 nwg = ((nfft // 2 // 240 // 2 + 1 + 7) // 8) * 8 * B if nfft == 96000 else 0
-for bgv in ((5, 2) if nwg else ()):
-    _lib.lib().fl_debug_set_spec(args.vt, 100 * bgv + args.rg)
-    print(f"--- batch items per workgroup: {bgv}")
+if nwg:
     buf = torch.zeros(nwg * 8, dtype=torch.int64, device=dev)
     _lib.lib().fl_debug_set_spec_times(buf.data_ptr())
     ops._spec_mid(S.clone(), B, N, N, nfft, Hp, False, True, True, 1.0, 0, 0)
