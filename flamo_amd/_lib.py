@@ -1,6 +1,6 @@
-"""ctypes binding of libflamo_hip.so.  The C ABI is declared in include/flamo_hip.h (and, for the energy-decay-curve
-criterion, include/flamo_hip_edc.h), and the restype / argtypes of every entry point are read from those headers at import
-(_parse_header): no signature is written a second time here.
+"""ctypes binding of libflamo_hip.so.  The C ABI is declared in include/flamo_hip.h (and, for the energy-decay-curve and the
+average-power criteria, include/flamo_hip_edc.h and include/flamo_hip_avgpow.h), and the restype / argtypes of every entry
+point are read from those headers at import (_parse_header): no signature is written a second time here.
 
 The shared library is built in-tree (``flamo_amd/libflamo_hip.so``) by ``build()`` /
 ``make -C flamo_amd/csrc``.  There is NO fallback: if the library is missing or a tensor is
@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("FLAMO_HIP_LIB") or os.path.join(_HERE, "libflamo_hip.
 CSRC = os.path.join(_HERE, "csrc")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "flamo_hip.h")
 HEADER_EDC_PATH = os.path.join(os.path.dirname(_HERE), "include", "flamo_hip_edc.h")      # the criterion of csrc/edc.hip
+HEADER_AVGPOW_PATH = os.path.join(os.path.dirname(_HERE), "include", "flamo_hip_avgpow.h")      # ... of csrc/avgpow.hip
 
 _lock = threading.Lock()
 _lib = None
@@ -90,6 +91,9 @@ EXPORTS = tuple(_SIGNATURES)
 # the entries of include/flamo_hip_edc.h, a table of their own: bound by lib() like the others
 _SIGNATURES_EDC = _read_header(HEADER_EDC_PATH)
 
+# ... and those of include/flamo_hip_avgpow.h
+_SIGNATURES_AVGPOW = _read_header(HEADER_AVGPOW_PATH)
+
 
 def build(force: bool = False) -> str:
     """Compile every HIP source for gfx950 into flamo_amd/libflamo_hip.so (hipcc cross-compiles
@@ -127,7 +131,7 @@ def lib(pair_ok: bool = False) -> C.CDLL:
                         "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C flamo_amd/csrc`)."
                     )
                 handle = C.CDLL(LIB_PATH)
-                for name, (res, args) in (*_SIGNATURES.items(), *_SIGNATURES_EDC.items()):
+                for name, (res, args) in (*_SIGNATURES.items(), *_SIGNATURES_EDC.items(), *_SIGNATURES_AVGPOW.items()):
                     fn = getattr(handle, name)  # AttributeError if the symbol is missing
                     fn.restype = res
                     fn.argtypes = args

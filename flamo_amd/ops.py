@@ -2818,6 +2818,103 @@ def edc_loss(y_pred: torch.Tensor, y_true: torch.Tensor, energy_norm: bool = Fal
     return _EDCLoss.apply(y_pred, t, bool(energy_norm), bool(convergence), bool(clip))
 
 
+AVGPOW_NFFT, AVGPOW_HOP, AVGPOW_WIN = 1024, 256, 64      # frame length, hop and smoothing window of the reference's class
+AVGPOW_MIN_T = AVGPOW_HOP * (AVGPOW_WIN - 1)             # 64 frames: one column of the smoothed spectrogram
+_avgpow_windows = {}
+
+
+def _avgpow_consts(real: torch.dtype, dev: torch.device):
+    """(w, h, twiddles) on the device, cached per (device, precision): w = torch.hann_window(1024), which the reference builds
+    without a dtype -- float32 VALUES also under a float64 signal -- and h = torch.hann_window(64) in the signal's precision"""
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), real)
+    ent = _avgpow_windows.get(key)
+    if ent is None:
+        w = torch.hann_window(AVGPOW_NFFT).to(device=dev, dtype=real)
+        h = torch.hann_window(AVGPOW_WIN, dtype=real).to(dev)
+        ent = _avgpow_windows[key] = (w, h)
+    return ent + (twiddles(AVGPOW_NFFT, real, dev),)
+
+
+def _avgpow_signal(y: torch.Tensor):
+    """(tensor whose memory the kernels read, element stride of the time axis) of a (T,) or (1, T, 1) signal"""
+    s = y.stride(0 if y.dim() == 1 else 1)
+    if s >= 1:
+        return y, s
+    return y.contiguous(), 1
+
+
+class _AveragePower(torch.autograd.Function):
+    """the average-power criterion, one node over the prediction: frame kernel, combine and final sum forward (keeping P1, P2
+    and the three sums of squares); frame kernel and overlap-add backward"""
+
+    @staticmethod
+    def forward(ctx, y, t, si, sj):
+        dev = _require_gpu(y, t)
+        L = _lib.lib()
+        T = y.numel()
+        F = L.fl_avgpow_frames(T)
+        I, J = (AVGPOW_NFFT // 2 + 1 - AVGPOW_WIN) // si + 1, (F - AVGPOW_WIN) // sj + 1
+        w, h, tw = _avgpow_consts(y.dtype, dev)
+        ym, sp = _avgpow_signal(y)
+        tm, st = _avgpow_signal(t)
+        work = torch.empty(L.fl_avgpow_work_doubles(T, si, sj), dtype=torch.float64, device=dev)
+        keep = torch.empty(L.fl_avgpow_keep_doubles(T, si, sj), dtype=torch.float64, device=dev)
+        P1, P2 = (torch.empty((I, J), dtype=y.dtype, device=dev) for _ in range(2))
+        loss = _scalar_loss(y.dtype, dev)
+        with kernel_timer.span("avgpow_fwd"):
+            _lib.check(_fn("fl_avgpow_fwd", y.dtype)(ym.data_ptr(), sp, tm.data_ptr(), st, T, si, sj, w.data_ptr(), h.data_ptr(),
+                                                     tw.data_ptr(), work.data_ptr(), keep.data_ptr(), P1.data_ptr(), P2.data_ptr(),
+                                                     loss.data_ptr(), _stream()), "avgpow_fwd")
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(ym, keep)
+            ctx.cfg = (sp, T, F, si, sj, tuple(y.shape))
+        ctx.mark_non_differentiable(P1, P2)
+        ctx.set_materialize_grads(False)      # (no zero-filled cotangents made for P1 and P2 on every backward pass)
+        return loss, P1, P2
+
+    @staticmethod
+    def backward(ctx, gloss, _g1, _g2):
+        if gloss is None:
+            return None, None, None, None
+        ym, keep = ctx.saved_tensors
+        sp, T, F, si, sj, shape = ctx.cfg
+        w, h, tw = _avgpow_consts(ym.dtype, ym.device)
+        gframes = torch.empty((F, AVGPOW_NFFT), dtype=ym.dtype, device=ym.device)
+        gy = torch.empty(shape, dtype=ym.dtype, device=ym.device)
+        g = _gloss_as(gloss, ym.dtype)
+        with kernel_timer.span("avgpow_bwd"):
+            _lib.check(_fn("fl_avgpow_bwd", ym.dtype)(ym.data_ptr(), sp, T, si, sj, w.data_ptr(), h.data_ptr(), tw.data_ptr(),
+                                                     keep.data_ptr(), g.data_ptr(), gframes.data_ptr(), gy.data_ptr(), _stream()),
+                       "avgpow_bwd")
+        return gy, None, None, None
+
+
+def average_power(y_pred: torch.Tensor, y_true: torch.Tensor, stride: Tuple[int, int] = (4, 4)):
+    """The reference's AveragePower criterion (flamo/optimize/loss.py:506-545) of one signal, (T,) or (1, T, 1): magnitude
+    spectrograms of prediction and target (frames of 1024 samples, hop 256, periodic Hann window, reflect padding), each
+    smoothed by a 64 x 64 Hann window with ``stride`` = (along frequency, along frames), and
+    |P2 - P1|_F / |P1|_F / |P2|_F of the two.  Returns ``(loss, P1, P2)``: the loss a 0-d tensor of the signals' dtype under
+    one autograd node over the prediction, P1 / P2 the smoothed spectrograms (I, J), which take no gradient.  The target takes
+    no gradient.  Five launches in all (three forward, two backward); the spectrograms themselves never reach memory."""
+    _require_gpu(y_pred, y_true)
+    t = y_true.detach()
+    one = y_pred.dim() == 1 or (y_pred.dim() == 3 and y_pred.shape[0] == 1 and y_pred.shape[2] == 1)
+    if not one or y_pred.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"average_power: one real float32 / float64 signal, (T,) or (1, T, 1), got {tuple(y_pred.shape)} {y_pred.dtype}")
+    if tuple(t.shape) != tuple(y_pred.shape) or t.dtype != y_pred.dtype:
+        raise ValueError(f"average_power: prediction {tuple(y_pred.shape)} {y_pred.dtype} and target {tuple(t.shape)} {t.dtype} differ")
+    try:
+        si, sj = (int(s) for s in stride)
+    except (TypeError, ValueError):
+        raise ValueError(f"average_power: stride must be a pair of positive integers, got {stride!r}") from None
+    if si < 1 or sj < 1 or (si, sj) != tuple(stride):
+        raise ValueError(f"average_power: stride must be a pair of positive integers, got {stride!r}")
+    T = y_pred.numel()
+    if T < AVGPOW_MIN_T or _lib.lib().fl_avgpow_frames(T) < AVGPOW_WIN:
+        raise ValueError(f"average_power: T = {T} gives fewer than {AVGPOW_WIN} frames (T >= {AVGPOW_MIN_T} is needed; at most 2^30)")
+    return _AveragePower.apply(y_pred, t, si, sj)
+
+
 def mean_square(y: torch.Tensor) -> torch.Tensor:
     """(y ** 2).mean() of a real tensor in one streaming pass each way (forward: one read of y;
     backward: one read + one write), in whatever layout y is stored."""

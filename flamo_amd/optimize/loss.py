@@ -1,12 +1,13 @@
 """``mse_loss`` and ``sparsity_loss`` of the reference (flamo/optimize/loss.py:12-103) on the library's kernels -- the two
 criteria of the colorless-FDN training (examples/e8_colorless_fdn.py:137-138) -- and its broadband ``edc_loss``
-(loss.py:674-809), the criterion of a fit to a measured room impulse response.
+(loss.py:674-809) and ``AveragePower`` (loss.py:462-549), the criteria of a fit to a measured room impulse response.
 
 The reference's training loop calls ``criterion(estimations, targets)`` (flamo/optimize/trainer.py:179-189); with
 ``flamo_amd.optimize.mse_loss`` in that list the loop runs unedited and the criterion costs one streaming pass over the
 prediction each way (``ops.mse``) instead of torch's sum / sub / pow / mean kernels and their backward."""
 import numpy as np
 import torch
+import torch.nn.functional as F
 from torch import nn
 
 from .. import ops
@@ -112,6 +113,72 @@ class edc_loss(nn.Module):
                 and self.discard_n == ops.EDC_DISCARD_PERCENT):
             return ops.edc_loss(y_pred, y_true, energy_norm=self.energy_norm, convergence=self.convergence, clip=self.clip)
         return self._torch_forward(y_pred, y_true)
+
+
+class AveragePower(nn.Module):
+    """Average-power criterion, flamo/optimize/loss.py:462-549: the magnitude spectrograms of prediction and target (frames of
+    1024 samples, hop 256, Hann window) are each smoothed by a 64 x 64 Hann window with ``stride``, and the criterion is the
+    Frobenius norm of the difference of the two divided by the norm of each.  ``energy_norm`` divides both signals by their
+    2-norm first.  One signal, (T,) or (1, T, 1), with T >= 16128 (64 frames).  Same constructor, defaults, attributes and
+    methods as the reference's class.
+
+    A device float32 / float64 prediction of one signal with unit time stride, against a gradient-free target of the same
+    shape and dtype, runs on ``ops.average_power`` (a framed transform each way, the spectrograms never stored); host tensors,
+    a target that takes a gradient, other dtypes and the shapes the reference itself rejects take the reference's torch lines
+    (``_torch_forward``) and raise what they raise."""
+
+    def __init__(self, energy_norm: bool = False, name: str = "Average Power", stride: tuple = (4, 4), device="cpu"):
+        super().__init__()
+        self.name = name
+        self.energy_norm = energy_norm
+        self.stride = stride
+        self.device = device
+
+    def forward(self, y_pred, y_true):
+        if len(y_pred.shape) == 1:
+            y_pred = y_pred.unsqueeze(0).unsqueeze(-1)
+            y_true = y_true.unsqueeze(0).unsqueeze(-1)
+        assert (y_pred.shape == y_true.shape) & (len(y_true.shape) == 3), \
+            "y_pred and y_true must have the same shape (n_batch, n_samples, n_channels)"
+        if self.energy_norm:
+            y_pred = y_pred / torch.norm(y_pred, p=2)
+            y_true = y_true / torch.norm(y_true, p=2)
+        return self.average_power(y_pred, y_true)[0]
+
+    def _on_kernels(self, y_pred, y_true):
+        try:
+            si, sj = self.stride
+            strides_ok = int(si) == si and int(sj) == sj and si >= 1 and sj >= 1
+        except (TypeError, ValueError):
+            return False
+        return (strides_ok and torch.is_tensor(y_pred) and torch.is_tensor(y_true) and y_pred.is_cuda and y_true.is_cuda
+                and y_pred.dtype in (torch.float32, torch.float64) and y_true.dtype == y_pred.dtype
+                and y_pred.dim() == 3 and y_pred.shape[0] == 1 and y_pred.shape[2] == 1 and y_pred.stride(1) == 1
+                and y_true.shape == y_pred.shape and not y_true.requires_grad and y_pred.shape[1] >= ops.AVGPOW_MIN_T)
+
+    def average_power(self, y_pred, y_true):
+        """(loss, S1_win, S2_win): the criterion and the two smoothed spectrograms"""
+        if self._on_kernels(y_pred, y_true):
+            loss, P1, P2 = ops.average_power(y_pred, y_true, stride=tuple(int(s) for s in self.stride))
+            return loss, P1.squeeze(), P2.squeeze()
+        return self._torch_forward(y_pred, y_true)
+
+    def _torch_forward(self, y_pred, y_true):
+        """the reference's own lines, on whatever device the tensors live"""
+        dev = y_pred.device
+        S1 = torch.abs(torch.stft(y_pred.squeeze(), n_fft=1024, hop_length=256, window=torch.hann_window(1024).to(dev),
+                                  return_complex=True))
+        S2 = torch.abs(torch.stft(y_true.squeeze(), n_fft=1024, hop_length=256, window=torch.hann_window(1024).to(dev),
+                                  return_complex=True))
+        win = self.window2d(torch.hann_window(64, dtype=S1.dtype, device=dev))
+        S1_win = F.conv2d(S1.unsqueeze(0).unsqueeze(0), win.unsqueeze(0).unsqueeze(0), stride=self.stride).squeeze()
+        S2_win = F.conv2d(S2.unsqueeze(0).unsqueeze(0), win.unsqueeze(0).unsqueeze(0), stride=self.stride).squeeze()
+        return (torch.norm(S2_win - S1_win, p="fro") / torch.norm(S1_win, p="fro") / torch.norm(S2_win, p="fro"),
+                S1_win, S2_win)
+
+    def window2d(self, window):
+        """create a 2D window from a given 1D window"""
+        return window[:, None] * window[None, :]
 
 
 class masked_mse_loss(nn.Module):

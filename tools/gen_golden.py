@@ -619,6 +619,43 @@ def gen_edc_loss(dsp, system):
     save("edc_loss", dict(kind="edc_loss", cotangent=3.0, cases=cases), **arrays)
 
 
+# ----------------------------------------------------------------------------- average-power criterion
+def average_power_signals(T, seed):
+    """(prediction, target) for the average-power criterion, (T,) each: seeded Gaussian noise under an exponential envelope
+    that ends at -60 dB (prediction) and -50 dB (target), rounded to bfloat16's bits as `edc_signals` does, no exact zero"""
+    gen = torch.Generator().manual_seed(seed)
+    ramp = torch.arange(T, dtype=F64) / (T - 1)
+    out = []
+    for end_db in (-60.0, -50.0):
+        y = (torch.randn(T, dtype=F64, generator=gen) * 10 ** (end_db * ramp / 20)).bfloat16().double()
+        assert (y != 0).all()
+        out.append(y)
+    return out
+
+
+def gen_average_power(dsp, system):
+    """flamo/optimize/loss.py:462-549: loss and gradient in float64 under the cotangent 3.0, and the loss of a float32 run, at
+    T = 16128 (64 frames, one column of the smoothed spectrogram) and T = 17152 (two columns) with the defaults, and at
+    T = 17152 with energy_norm=True, stride=(2, 3)"""
+    from flamo.optimize.loss import AveragePower
+    arrays, cases, signals = {}, [], {}
+    for T, seed, opts in ((16128, 20261020, {}), (17152, 20261021, {}), (17152, 20261021, dict(energy_norm=True, stride=(2, 3)))):
+        if T not in signals:
+            signals[T] = len(signals)
+            y_pred, y_true = average_power_signals(T, seed)
+            arrays[f"s{signals[T]}_y_pred"], arrays[f"s{signals[T]}_y_true"] = y_pred.float(), y_true.float()
+        si = signals[T]
+        y_pred, y_true = arrays[f"s{si}_y_pred"].double(), arrays[f"s{si}_y_true"].double()
+        yp = y_pred.clone().requires_grad_(True)
+        loss = AveragePower(**opts)(yp, y_true.clone())
+        (g,) = torch.autograd.grad(3.0 * loss, [yp])
+        loss32 = AveragePower(**opts)(y_pred.float(), y_true.float())
+        k = len(cases)
+        arrays[f"c{k}_loss"], arrays[f"c{k}_grad"], arrays[f"c{k}_loss_f32"] = loss.detach(), g, loss32.detach()
+        cases.append(dict(signals=si, T=T, options={n: (list(v) if isinstance(v, tuple) else v) for n, v in opts.items()}))
+    save("average_power", dict(kind="average_power", cotangent=3.0, cases=cases), **arrays)
+
+
 def main():
     torch.set_default_dtype(torch.float32)
     dsp, system = refimport.load()
@@ -646,6 +683,9 @@ def main():
     if "--edc-only" in sys.argv:
         gen_edc_loss(dsp, system)
         return
+    if "--average-power-only" in sys.argv:
+        gen_average_power(dsp, system)
+        return
     if "--biquad-only" in sys.argv:
         gen_biquad_training(dsp, system)
         return
@@ -661,6 +701,7 @@ def main():
     gen_householder_sparsity(dsp, system)
     gen_round2(dsp, system)
     gen_edc_loss(dsp, system)
+    gen_average_power(dsp, system)
     total = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT) if f.endswith(".npz"))
     print(f"total {total/1024:.1f} KiB")
 
