@@ -1,5 +1,6 @@
 """ctypes binding of libflamo_hip.so.  The C ABI is declared in include/flamo_hip.h (and, for the energy-decay-curve and the
-average-power criteria, include/flamo_hip_edc.h and include/flamo_hip_avgpow.h), and the restype / argtypes of every entry
+average-power criteria and the FDN attenuation designs, include/flamo_hip_edc.h, include/flamo_hip_avgpow.h and
+include/flamo_hip_fdnatt.h), and the restype / argtypes of every entry
 point are read from those headers at import (_parse_header): no signature is written a second time here.
 
 The shared library is built in-tree (``flamo_amd/libflamo_hip.so``) by ``build()`` /
@@ -21,6 +22,7 @@ CSRC = os.path.join(_HERE, "csrc")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "flamo_hip.h")
 HEADER_EDC_PATH = os.path.join(os.path.dirname(_HERE), "include", "flamo_hip_edc.h")      # the criterion of csrc/edc.hip
 HEADER_AVGPOW_PATH = os.path.join(os.path.dirname(_HERE), "include", "flamo_hip_avgpow.h")      # ... of csrc/avgpow.hip
+HEADER_FDNATT_PATH = os.path.join(os.path.dirname(_HERE), "include", "flamo_hip_fdnatt.h")      # the designs of csrc/fdnatt.hip
 
 _lock = threading.Lock()
 _lib = None
@@ -94,6 +96,9 @@ _SIGNATURES_EDC = _read_header(HEADER_EDC_PATH)
 # ... and those of include/flamo_hip_avgpow.h
 _SIGNATURES_AVGPOW = _read_header(HEADER_AVGPOW_PATH)
 
+# ... and those of include/flamo_hip_fdnatt.h
+_SIGNATURES_FDNATT = _read_header(HEADER_FDNATT_PATH)
+
 
 def build(force: bool = False) -> str:
     """Compile every HIP source for gfx950 into flamo_amd/libflamo_hip.so (hipcc cross-compiles
@@ -131,7 +136,8 @@ def lib(pair_ok: bool = False) -> C.CDLL:
                         "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C flamo_amd/csrc`)."
                     )
                 handle = C.CDLL(LIB_PATH)
-                for name, (res, args) in (*_SIGNATURES.items(), *_SIGNATURES_EDC.items(), *_SIGNATURES_AVGPOW.items()):
+                for name, (res, args) in (*_SIGNATURES.items(), *_SIGNATURES_EDC.items(), *_SIGNATURES_AVGPOW.items(),
+                                           *_SIGNATURES_FDNATT.items()):
                     fn = getattr(handle, name)  # AttributeError if the symbol is missing
                     fn.restype = res
                     fn.argtypes = args

@@ -2187,6 +2187,92 @@ class GeqGains(_Design, namedtuple("GeqGains", "kind x consts gain_map")):
         return (out, None) if partW is None else (out, None, gW)
 
 
+class FdnAttenuation(_Design, namedtuple("FdnAttenuation", "kind x packed n_lines fs slope_nyq")):
+    """("fdn_geq" | "fdn_shelf1", x, packed, n_lines, fs, slope_nyq): the delay-scaled attenuation filters of a feedback delay
+    network (csrc/fdnatt.hip), one cascade per delay line.  "fdn_geq": x (n_bands,) reverberation times in seconds, packed =
+    [delays (n_lines), GEQDesign.device_consts] -- a graphic equaliser per line whose band k commands
+    -60 delays[n] / (x[k] fs) dB.  "fdn_shelf1": x = (rt at DC, crossover w_c), packed = delays, slope_nyq the dB per sample at
+    the Nyquist frequency -- one first-order shelving section per line.  One design launch each way; the backward's launch also
+    sums the cascade backward's block partials and reduces over the lines in a fixed order."""
+    __slots__ = ()
+    float_with_grad = property(lambda self: self.kind == "fdn_geq")      # graphic-equaliser sections (see FLOAT_CASCADE_EVAL)
+    n_sections = property(lambda self: self.x.shape[0] if self.kind == "fdn_geq" else 1)
+    full = False
+
+    def tensors(self):
+        return self.x, self.packed
+
+    def _check(self, x, packed):
+        if self.kind not in ("fdn_geq", "fdn_shelf1"):
+            raise ValueError(f"FdnAttenuation: unknown kind {self.kind!r}")
+        geq = self.kind == "fdn_geq"
+        if x.dtype not in (torch.float32, torch.float64) or x.dim() != 1 or (x.shape[0] < 4 if geq else x.shape[0] != 2):
+            raise ValueError("FdnAttenuation expects float32 / float64 parameters, (n_bands >= 4,) or (2,)")
+        want = self.n_lines + (2 * x.shape[0] if geq else 0)
+        if self.n_lines < 1 or packed.dtype != torch.float64 or packed.dim() != 1 or packed.shape[0] != want or not packed.is_contiguous():
+            raise ValueError(f"FdnAttenuation: packed constants must be {want} contiguous float64 values")
+
+    def sections(self, x, packed, op, prologue):
+        """-> (sec, None), sec = (xc, packed, b, a): b, a (3, n_sections, n_lines) fresh, designed here"""
+        if op:
+            raise ValueError(f"sos_response{op}: the FDN attenuation filters are diagonal (one cascade per line)")
+        self._check(x, packed)
+        xc, N = x.contiguous(), self.n_lines
+        b = torch.empty((3, self.n_sections, N), dtype=torch.float64, device=x.device)
+        a = torch.empty_like(b)
+        L, f32 = _lib.lib(), int(xc.dtype == torch.float32)
+        if self.kind == "fdn_geq":
+            _lib.check(L.fl_fdn_geq_sections(xc.data_ptr(), f32, packed.data_ptr(), xc.shape[0], N, float(self.fs),
+                                             packed.data_ptr() + 8 * N, b.data_ptr(), a.data_ptr(), _stream()), "fdn_geq_sections")
+        else:
+            _lib.check(L.fl_fdn_shelf1_sections(xc.data_ptr(), f32, packed.data_ptr(), N, float(self.fs), float(self.slope_nyq),
+                                                b.data_ptr(), a.data_ptr(), _stream()), "fdn_shelf1_sections")
+        return (xc, packed, b, a), None
+
+    def param_grads(self, sec, part, partW=None, Wr=None):
+        """(dL/dx, None): the design backward on the cascade backward's block partials part (nblk, 2, 3, n_sections, n_lines)
+        -- dL/db at its start, dL/da three taps on, blocks six taps apart"""
+        if partW is not None:
+            raise ValueError("FdnAttenuation: no constant factor folds into a diagonal response")
+        xc, packed = sec[:2]
+        N, st = self.n_lines, part.shape[3] * part.shape[4]
+        out = torch.empty_like(xc)
+        L, f32 = _lib.lib(), int(xc.dtype == torch.float32)
+        blocks = (part.data_ptr(), part.data_ptr() + 3 * st * part.element_size(), 6 * st, part.shape[0])
+        if self.kind == "fdn_geq":
+            _lib.check(L.fl_fdn_geq_sections_bwd(xc.data_ptr(), f32, packed.data_ptr(), *blocks, xc.shape[0], N, float(self.fs),
+                                                 packed.data_ptr() + 8 * N, out.data_ptr(), _stream()), "fdn_geq_sections_bwd")
+        else:
+            _lib.check(L.fl_fdn_shelf1_sections_bwd(xc.data_ptr(), f32, packed.data_ptr(), *blocks, N, float(self.fs),
+                                                    float(self.slope_nyq), out.data_ptr(), _stream()), "fdn_shelf1_sections_bwd")
+        return out, None
+
+
+class _FdnSections(torch.autograd.Function):
+    """the design of an FdnAttenuation alone: parameters -> (b, a), one launch each way"""
+
+    @staticmethod
+    def forward(ctx, design, x, packed):
+        _require_gpu(x, packed)
+        sec, _ = design.sections(x, packed, "", False)
+        ctx.design = design
+        ctx.save_for_backward(*sec[:2])
+        return sec[2], sec[3]
+
+    @staticmethod
+    def backward(ctx, gb, ga):
+        xc, packed = ctx.saved_tensors
+        shape = (3, ctx.design.n_sections, ctx.design.n_lines)
+        gb, ga = (torch.zeros(shape, dtype=torch.float64, device=xc.device) if g is None else g.to(torch.float64) for g in (gb, ga))
+        part = torch.stack((gb, ga)).unsqueeze(0).contiguous()
+        return (None, *ctx.design.param_grads((xc, packed), part))
+
+
+def fdn_sections(design: FdnAttenuation):
+    """(b, a), float64 (3, n_sections, n_lines), of the delay-scaled attenuation filters `design` describes"""
+    return _FdnSections.apply(design, *design.tensors())
+
+
 class _Cascade(torch.autograd.Function):
     """Response of a cascade.  Raw sections: one launch each way (+ the sum of the block partials).  Graphic equaliser: raw
     parameters -> response in two launches (design + cascade; one in float32), gradient in two (cascade backward + design

@@ -656,12 +656,104 @@ def gen_average_power(dsp, system):
     save("average_power", dict(kind="average_power", cotangent=3.0, cases=cases), **arrays)
 
 
+# ----------------------------------------------------------------------------- auxiliary.reverb
+REVERB_DELAYS = [157, 263]                  # the module cases: two lines keep H and W of twelve cases under the size limit
+REVERB_FDN_DELAYS = [101, 157, 211, 263]
+
+
+def gen_reverb(dsp, system):
+    """flamo/auxiliary/reverb.py in float64: per case of parallelFDNGEQ / parallelFirstOrderShelving / parallelFDNAccurateGEQ the
+    parameter, the delays, H = freq_response(param), a fixed complex cotangent W (float32 values) and, for the trainable ones,
+    the gradient of Re sum conj(W) H; one whole FDN with parallelFDNGEQ in its feedback path; one HomogeneousFDN with explicit
+    delays.  The (M, S, N) section spectra are not stored."""
+    from types import SimpleNamespace
+    from flamo.auxiliary import reverb
+    arrays, cases = {}, []
+    delays = torch.tensor(REVERB_DELAYS, dtype=F64)
+    specs = [(cls, oi, nfft, db) for cls, oi in (("parallelFDNGEQ", 1), ("parallelFirstOrderShelving", 1), ("parallelFDNAccurateGEQ", 1))
+             for nfft in (960, 1500) for db in (0.0, 30.0)] + [("parallelFDNGEQ", 3, 960, 30.0)]
+    for cls, oi, nfft, db in specs:
+        k = len(cases)
+        torch.manual_seed(20261020 + k)
+        kw = dict(nfft=nfft, delays=delays, alias_decay_db=db, dtype=F64)
+        if cls == "parallelFirstOrderShelving":
+            mod = reverb.parallelFirstOrderShelving(rt_nyquist=0.2, requires_grad=True, **kw)
+            param = torch.tensor([1.5 + 0.1 * (k % 4), 0.35 + 0.2 * (k % 4)], dtype=F64)
+        elif cls == "parallelFDNGEQ":
+            mod = reverb.parallelFDNGEQ(octave_interval=oi, requires_grad=True, **kw)
+            param = torch.rand(mod.param.shape, dtype=F64) * 2.5 + 0.3
+        else:
+            mod = reverb.parallelFDNAccurateGEQ(octave_interval=oi, **kw)
+            param = torch.rand(mod.param.shape, dtype=F64) * 2.0 + 0.5
+        param = param.float().double()          # float32 values: a float32 module starts from the very same numbers
+        mod.assign_value(param)
+        H = mod.freq_response(mod.param)
+        W = crandn(*H.shape).to(torch.complex64)
+        arrays[f"c{k}_param"], arrays[f"c{k}_H"], arrays[f"c{k}_W"] = param, H.detach().to(C128), W
+        if mod.param.requires_grad:
+            (g,) = vjp_complex(H, W.to(C128), [mod.param])
+            arrays[f"c{k}_grad"] = g
+        cases.append(dict(cls=cls, octave_interval=oi, nfft=nfft, alias_decay_db=db, rt_nyquist=0.2,
+                          state_keys=list(mod.state_dict().keys()), param_shape=list(mod.param.shape)))
+        print(f"  reverb case {k}: {cls} oi {oi} nfft {nfft} db {db}")
+
+    # the whole FDN of examples/e8_fdn.py with the delay-scaled equaliser in the feedback path
+    torch.manual_seed(20261040)
+    N, nfft, db = 4, 960, 30.0
+    kw = dict(nfft=nfft, alias_decay_db=db, dtype=F64)
+    fd = torch.tensor(REVERB_FDN_DELAYS, dtype=F64)
+    ig = dsp.Gain(size=(N, 1), requires_grad=True, **kw)
+    og = dsp.Gain(size=(1, N), requires_grad=True, **kw)
+    dl = dsp.parallelDelay(size=(N,), max_len=int(fd.max()), isint=True, requires_grad=False, **kw)
+    dl.assign_value(dl.sample2s(fd))
+    mix = dsp.Matrix(size=(N, N), matrix_type="orthogonal", requires_grad=True, **kw)
+    att = reverb.parallelFDNGEQ(octave_interval=1, delays=fd, requires_grad=True, **kw)
+    att.assign_value((torch.rand(att.param.shape, dtype=F64) * 2.0 + 0.5).float().double())
+    for m in (ig, og, mix):                 # float32 values: a float32 run starts from the very same numbers
+        m.assign_value(m.param.detach().float().double())
+    rec = system.Recursion(fF=dl, fB=system.Series(OrderedDict({"mixing_matrix": mix, "attenuation": att})))
+    core = system.Series(OrderedDict({"input_gain": ig, "feedback_loop": rec, "output_gain": og}))
+    model = system.Shell(core=core, input_layer=dsp.FFT(nfft, dtype=F64),
+                         output_layer=dsp.iFFTAntiAlias(nfft=nfft, alias_decay_db=db, dtype=F64))
+    x = torch.zeros(1, nfft, 1, dtype=F64)
+    x[:, 0, :] = 1
+    x.requires_grad_(True)
+    y = model(x)
+    c = torch.randn(*y.shape, dtype=F64).float().double()
+    plist = [ig.param, og.param, mix.param, att.param]
+    g = torch.autograd.grad(torch.sum(y * c), [x] + plist)
+    arrays.update(fdn_x=x, fdn_y=y, fdn_c=c, fdn_gx=g[0], fdn_in_gain=plist[0], fdn_out_gain=plist[1], fdn_U_param=plist[2],
+                  fdn_attn_param=plist[3], fdn_g_in_gain=g[1], fdn_g_out_gain=g[2], fdn_g_U_param=g[3], fdn_g_attn_param=g[4],
+                  fdn_delays_s=dl.param.detach())
+    fdn_meta = dict(N=N, nfft=nfft, alias_decay_db=db, delays=REVERB_FDN_DELAYS, state_keys=list(model.state_dict().keys()))
+
+    # HomogeneousFDN on explicit delays (any object with the attributes of HomogeneousFDNConfig)
+    torch.manual_seed(20261041)
+    hcfg = dict(N=4, delays=REVERB_FDN_DELAYS, nfft=960, alias_decay_db=30.0, sample_rate=48000, delay_range_ms=[20.0, 50.0],
+                is_delay_int=True, input_gain_grad=False, output_gain_grad=False, delays_grad=False, mixing_matrix_grad=True,
+                attenuation_grad=False)
+    hom = reverb.HomogeneousFDN(SimpleNamespace(device="cpu", dtype=F64, **hcfg))
+    raw = hom.get_raw_parameters()
+    xh = torch.zeros(1, 960, 1, dtype=F64)
+    xh[:, 0, :] = 1
+    with torch.no_grad():
+        yh = hom.model(xh)
+    for key, v in raw.items():
+        arrays[f"hom_{key}"] = np.asarray(v)
+    arrays.update(hom_x=xh, hom_y=yh, hom_rt2gain=hom.rt2gain(torch.tensor([1.0, 2.5], dtype=F64)))
+    hom_meta = dict(config=hcfg, state_keys=list(hom.model.state_dict().keys()), raw_keys=list(raw.keys()))
+    save("reverb", dict(kind="reverb", delays=REVERB_DELAYS, fs=48000, cases=cases, fdn=fdn_meta, homogeneous=hom_meta), **arrays)
+
+
 def main():
     torch.set_default_dtype(torch.float32)
     dsp, system = refimport.load()
     import warnings
 
     warnings.filterwarnings("ignore")
+    if "--reverb-only" in sys.argv:
+        gen_reverb(dsp, system)
+        return
     if "--round2-only" in sys.argv:
         gen_round2(dsp, system)
         return
@@ -702,7 +794,8 @@ def main():
     gen_round2(dsp, system)
     gen_edc_loss(dsp, system)
     gen_average_power(dsp, system)
-    total = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT) if f.endswith(".npz"))
+    gen_reverb(dsp, system)
+    total =sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT) if f.endswith(".npz"))
     print(f"total {total/1024:.1f} KiB")
 
 
