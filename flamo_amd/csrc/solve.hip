@@ -509,9 +509,6 @@ __global__ void __launch_bounds__(256) solve_inplace_kernel(
     cx<T>* __restrict__ OUT, long os_b, long os_n, long os_k,
     int B, int M, int N, int K) {
     constexpr int NMAX = LANES * RPL, BPB = 256 / LANES;
-    const int thr_steps = (adjoint >> 8) & 0xFF;     // tuning: exponent steps of the pivot threshold (host passes >= 1)
-    const bool no_prefetch = (adjoint >> 16) & 1;    // tuning (fl_debug_set_solve_variant(5)): the right-hand side is fetched behind the elimination
-    adjoint &= 1;
     const int gi = threadIdx.x % LANES;
     const int f = blockIdx.x * BPB + threadIdx.x / LANES;
     // the frequency-independent mixing matrix, zero-padded to NMAX x NMAX (and transposed for the adjoint
@@ -696,7 +693,7 @@ __global__ void __launch_bounds__(256) solve_inplace_kernel(
             kmax = max(kmax, dpp_mov<DPP_QUAD_XOR1>(kmax));
             // keep the diagonal unless it is more than 2x smaller than the column maximum: a factor 2 is one
             // exponent step, i.e. 1 << 23 on the bit pattern (denormal magnitudes compare conservatively)
-            const bool exchange = group_bcast<LANES, LK>(dkey) + (thr_steps << 23) < kmax;
+            const bool exchange = group_bcast<LANES, LK>(dkey) + (1 << 23) < kmax;
             if (__builtin_expect(__any(exchange), 0)) {   // uniform over the wavefront (and rare: laid out off the hot path);
                                                           // groups that keep their diagonal map to themselves
                 const int best = NMAX - 1 - (kmax & (NMAX - 1));
@@ -866,7 +863,7 @@ __global__ void __launch_bounds__(256) solve_inplace_kernel(
     bool moved = false;
 #pragma unroll
     for (int s = 0; s < RPL; ++s) moved |= orig[s] != s * LANES + gi;
-    const bool refetch = !kPrefetchRhs || P != nullptr || no_prefetch || __any(moved);
+    const bool refetch = !kPrefetchRhs || P != nullptr || __any(moved);
     for (int col = 0; col < ncols; ++col) {
         const int b = col / K, kk = col - b * K;
         cx<T> y[RPL];
@@ -943,74 +940,51 @@ __global__ void __launch_bounds__(256) solve_inplace_kernel(
     }
 }
 
-static int g_solve_rpl2_16 = 0;   // factored loop, N in (4, 16]: 0 = two rows per lane (default), 1 = one row per lane (variant 4)
-static int g_solve_rpl2_p = 0;    // tuning: variant 3 = two-rows-per-lane kernel also for a materialised P
-static int g_solve_thr = 1;       // pivot threshold 2^-thr (tuning: variant 10 + thr)
-static int g_solve_noprefetch = 0;   // tuning: variant 5 = the in-place kernels fetch the right-hand side behind the elimination
-static int g_solve_variant = 0;   // tuning hook: 1 forces the shuffle kernel for every N
+// fl_debug_set_solve_variant: 0 (default) = the in-place kernels, two rows per lane for the factored loop at N in (4, 16];
+// 1 = the shuffle kernel for every N; 4 = the in-place kernels with one row per lane
+static int g_solve_variant = 0;
+
+// NMAX of the register-resident kernels for N channels: the next power of two, at least 4
+static int solve_np(int N) {
+    int np = 4;
+    while (np < N) np *= 2;
+    return np;
+}
+// ... as a template argument: f(std::integral_constant<int, NMAX>{}), false beyond 64 (float) / 32 (double: no 64-wide kernels).
+// (A kernel instantiation named for the first time under this, or in launch_solve, also goes into pin_kernel_order's list.)
+template <typename T, class F>
+static bool solve_dispatch(int N, F&& f) {
+    if constexpr (sizeof(T) == 8) return dispatch<4, 8, 16, 32>(solve_np(N), f);
+    else return dispatch<4, 8, 16, 32, 64>(solve_np(N), f);
+}
 
 template <typename T, int NMAX>
 static int launch_solve(const void* P, long p_pitch, const Dud<T>& dud, int one_minus, int adjoint, const void* R, long rs_b, long rs_n, long rs_k,
                         void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, int K, hipStream_t st) {
-    constexpr int BPB = 256 / NMAX;
-    dim3 grid(cdiv_i(M, BPB));
-    if (g_solve_variant == 0) {
-        if constexpr (NMAX == 16) {
-            // N in (8, 16], factored loop: 8 lanes x 2 rows per lane -- 8 bins per wavefront, every broadcast of a pivot-row
-            // element feeds two row updates: 86 -> 73 us at N = 16 (c64), 131 -> 108 us (c128), 82 -> 63 us at N = 9
-            // (tools/dbg/archive/solve_rpl2_16.py; 4 lanes x 4 rows: 80 us, and it spills).  fl_debug_set_solve_variant(4): the
-            // one-row-per-lane kernels.
-            if (!P && g_solve_rpl2_16 != 1 && dud.wadj) {
-                hipLaunchKernelGGL((solve_inplace_kernel<T, 8, 2, true>), dim3(cdiv_i(M, 32)), dim3(256), 0, st, (const cx<T>*)P, p_pitch,
-                                   dud, one_minus, adjoint | (g_solve_thr << 8) | (g_solve_noprefetch << 16), (const cx<T>*)R, rs_b, rs_n, rs_k, (cx<T>*)OUT,
-                                   os_b, os_n, os_k, B, M, N, K);
-                FL_CHECK_LAUNCH("solve");
-                return FL_OK;
-            }
-            if (!P && g_solve_rpl2_16 != 1) {
-                hipLaunchKernelGGL((solve_inplace_kernel<T, 8, 2>), dim3(cdiv_i(M, 32)), dim3(256), 0, st, (const cx<T>*)P, p_pitch,
-                                   dud, one_minus, adjoint | (g_solve_thr << 8) | (g_solve_noprefetch << 16), (const cx<T>*)R, rs_b, rs_n, rs_k, (cx<T>*)OUT,
-                                   os_b, os_n, os_k, B, M, N, K);
-                FL_CHECK_LAUNCH("solve");
-                return FL_OK;
-            }
+    // every kernel takes the same arguments; a workgroup's 256 lanes are `lanes` per bin
+    auto launch = [&](auto kern, int lanes) {
+        hipLaunchKernelGGL(kern, dim3(cdiv_i(M, 256 / lanes)), dim3(256), 0, st, (const cx<T>*)P, p_pitch, dud, one_minus, adjoint,
+                           (const cx<T>*)R, rs_b, rs_n, rs_k, (cx<T>*)OUT, os_b, os_n, os_k, B, M, N, K);
+        FL_CHECK_LAUNCH("solve");
+        return FL_OK;
+    };
+    if (g_solve_variant != 1) {
+        if constexpr (NMAX == 8 || NMAX == 16) {
+            // N in (4, 16], factored loop: NMAX / 2 lanes x 2 rows per lane -- twice the bins per wavefront, every broadcast of a
+            // pivot-row element feeds two row updates: 86 -> 73 us at N = 16 (c64), 131 -> 108 us (c128), 82 -> 63 us at N = 9,
+            // 29 -> 23 us at N = 8 (tools/dbg/archive/solve_rpl2_16.py; 4 lanes x 4 rows: 80 us, and it spills).
+            // fl_debug_set_solve_variant(4): the one-row-per-lane kernels.  (WADJ: an instantiation of its own, see the kernel)
+            constexpr int L = NMAX / 2;
+            if (!P && g_solve_variant == 0)
+                return dud.wadj ? launch(solve_inplace_kernel<T, L, 2, true>, L) : launch(solve_inplace_kernel<T, L, 2>, L);
         }
-        if constexpr (NMAX == 8) {
-            if (!P && g_solve_rpl2_16 != 1 && dud.wadj) {
-                hipLaunchKernelGGL((solve_inplace_kernel<T, 4, 2, true>), dim3(cdiv_i(M, 64)), dim3(256), 0, st, (const cx<T>*)P, p_pitch,
-                                   dud, one_minus, adjoint | (g_solve_thr << 8) | (g_solve_noprefetch << 16), (const cx<T>*)R, rs_b, rs_n, rs_k, (cx<T>*)OUT,
-                                   os_b, os_n, os_k, B, M, N, K);
-                FL_CHECK_LAUNCH("solve");
-                return FL_OK;
-            }
-            if (!P && g_solve_rpl2_16 != 1) {      // N in (4, 8] on 4 lanes x 2 rows (16 bins per wavefront): 29 -> 23 us at N = 8
-                hipLaunchKernelGGL((solve_inplace_kernel<T, 4, 2>), dim3(cdiv_i(M, 64)), dim3(256), 0, st, (const cx<T>*)P, p_pitch,
-                                   dud, one_minus, adjoint | (g_solve_thr << 8) | (g_solve_noprefetch << 16), (const cx<T>*)R, rs_b, rs_n, rs_k, (cx<T>*)OUT,
-                                   os_b, os_n, os_k, B, M, N, K);
-                FL_CHECK_LAUNCH("solve");
-                return FL_OK;
-            }
-        }
-        if constexpr (NMAX <= 16) {
-            hipLaunchKernelGGL((solve_inplace_kernel<T, NMAX, 1>), grid, dim3(256), 0, st, (const cx<T>*)P, p_pitch, dud, one_minus,
-                               adjoint | (g_solve_thr << 8) | (g_solve_noprefetch << 16), (const cx<T>*)R, rs_b, rs_n, rs_k, (cx<T>*)OUT, os_b, os_n, os_k, B, M, N, K);
-            FL_CHECK_LAUNCH("solve");
-            return FL_OK;
-        } else if constexpr (NMAX == 32 && sizeof(T) == 4) {    // two rows per lane, 16 lanes per bin
-            // (a materialised P keeps the shuffle kernel for now: its row-per-lane loads are 32-byte pieces here)
-            if (!P || g_solve_rpl2_p) {
-                hipLaunchKernelGGL((solve_inplace_kernel<T, 16, 2>), dim3(cdiv_i(M, 16)), dim3(256), 0, st, (const cx<T>*)P, p_pitch,
-                                   dud, one_minus, adjoint | (g_solve_thr << 8) | (g_solve_noprefetch << 16), (const cx<T>*)R, rs_b, rs_n, rs_k, (cx<T>*)OUT, os_b,
-                                   os_n, os_k, B, M, N, K);
-                FL_CHECK_LAUNCH("solve");
-                return FL_OK;
-            }
-        }
+        if constexpr (NMAX <= 16) return launch(solve_inplace_kernel<T, NMAX, 1>, NMAX);
+        // float, N in (16, 32]: two rows per lane, 16 lanes per bin (a materialised P keeps the shuffle kernel: with one workgroup
+        // per CU nothing hides this kernel's loads, 1.35 against 1.07 ms even when they go through LDS -- DESIGN_HISTORY.md)
+        if constexpr (NMAX == 32 && sizeof(T) == 4)
+            if (!P) return launch(solve_inplace_kernel<T, 16, 2>, 16);
     }
-    hipLaunchKernelGGL((solve_kernel<T, NMAX>), grid, dim3(256), 0, st, (const cx<T>*)P, p_pitch, dud, one_minus, adjoint,
-                       (const cx<T>*)R, rs_b, rs_n, rs_k, (cx<T>*)OUT, os_b, os_n, os_k, B, M, N, K);
-    FL_CHECK_LAUNCH("solve");
-    return FL_OK;
+    return launch(solve_kernel<T, NMAX>, NMAX);
 }
 
 
@@ -1177,7 +1151,7 @@ static int solve_impl(const void* P, long p_pitch, const Dud<T>& dud, int one_mi
     FL_REQUIRE((P || dud.U) && (R || dud.rv) && OUT, "solve: null pointer");
     if (dud.rv || dud.cz) {
         FL_REQUIRE(dud.rv && dud.rs && K == 1 && !P, "solve: the rank-one right-hand side needs its scalar signal, one column per batch item and the factored loop");
-        if (g_solve_variant != 0 || N > (sizeof(T) == 4 ? 32 : 16)) {
+        if (g_solve_variant == 1 || N > (sizeof(T) == 4 ? 32 : 16)) {
             set_error("solve: the rank-one right-hand side / contracted output exist in the in-place kernels only (N <= %d here)",
                       sizeof(T) == 4 ? 32 : 16);
             return FL_ERR_UNSUPPORTED;
@@ -1195,16 +1169,10 @@ static int solve_impl(const void* P, long p_pitch, const Dud<T>& dud, int one_mi
             int cb = 16;
             while (cb > 1 && (size_t)N * cb * sizeof(cx<T>) + (size_t)N * sizeof(int) > budget) cb >>= 1;
             const size_t lds = (size_t)N * cb * sizeof(cx<T>) + (size_t)N * sizeof(int);
-            static bool attr_ws[64] = {};
-            int dev = 0;
-            if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-            if (!attr_ws[dev] && lds > 64 * 1024) {
-                const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(solve_lds_kernel<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)budget);
-                if (e != hipSuccess) {
-                    set_error("solve: %zu bytes of LDS per workgroup are not available on device %d (%s)", budget, dev, hipGetErrorString(e));
-                    return FL_ERR_UNSUPPORTED;
-                }
-                attr_ws[dev] = true;
+            static bool done_ws[kMaxDevices] = {};
+            if (lds > 64 * 1024) {      // (nothing to set at or below the default)
+                const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(solve_lds_kernel<T, true>), lds, true, done_ws, "solve");
+                if (rc) return rc;
             }
             hipLaunchKernelGGL((solve_lds_kernel<T, true>), dim3(slots), dim3(256), lds, (hipStream_t)stream, (const cx<T>*)P, p_pitch, one_minus,
                                adjoint, (const cx<T>*)R, rs_b, rs_n, rs_k, (cx<T>*)OUT, os_b, os_n, os_k, B, M, N, K, cb, (cx<T>*)ws);
@@ -1223,33 +1191,21 @@ static int solve_impl(const void* P, long p_pitch, const Dud<T>& dud, int one_mi
         int cb = 16;
         while (cb > 4 && ((size_t)N * (N + 1) + (size_t)N * cb) * sizeof(cx<T>) + (size_t)N * sizeof(int) > budget) cb >>= 1;
         const size_t lds = ((size_t)N * (N + 1) + (size_t)N * cb) * sizeof(cx<T>) + (size_t)N * sizeof(int);
-        // the attribute is per device: set (and checked) once on each device this process uses
-        static bool attr_set[64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-        if (!attr_set[dev]) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(solve_lds_kernel<T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)budget);
-            if (e != hipSuccess) {
-                set_error("solve: %zu bytes of LDS per workgroup are not available on device %d (%s)", budget, dev, hipGetErrorString(e));
-                return FL_ERR_UNSUPPORTED;
-            }
-            attr_set[dev] = true;
-        }
+        static bool done[kMaxDevices] = {};
+        const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(solve_lds_kernel<T, false>), lds, true, done, "solve");
+        if (rc) return rc;
         hipLaunchKernelGGL((solve_lds_kernel<T, false>), dim3(M), dim3(256), lds, (hipStream_t)stream, (const cx<T>*)P, p_pitch, one_minus, adjoint,
                            (const cx<T>*)R, rs_b, rs_n, rs_k, (cx<T>*)OUT, os_b, os_n, os_k, B, M, N, K, cb, (cx<T>*)nullptr);
         FL_CHECK_LAUNCH("solve_lds");
         return FL_OK;
     }
     if (B == 0 || M == 0) return FL_OK;
-    hipStream_t st = (hipStream_t)stream;
-#define FL_SOLVE(NM) return launch_solve<T, NM>(P, p_pitch, dud, one_minus, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, st)
-    if (N <= 4) FL_SOLVE(4);
-    if (N <= 8) FL_SOLVE(8);
-    if (N <= 16) FL_SOLVE(16);
-    if (N <= 32) FL_SOLVE(32);
-    if constexpr (sizeof(T) == 4) FL_SOLVE(64);
-#undef FL_SOLVE
-    return FL_ERR_UNSUPPORTED;
+    int rc = FL_ERR_UNSUPPORTED;
+    solve_dispatch<T>(N, [&](auto nm) {
+        rc = launch_solve<T, decltype(nm)::value>(P, p_pitch, dud, one_minus, adjoint, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K,
+                                                  (hipStream_t)stream);
+    });
+    return rc;
 }
 
 
@@ -1493,10 +1449,7 @@ __global__ void __launch_bounds__(256) dud_grads_final_kernel(const cx<T>* __res
 }
 
 static int dud_grads_blocks(int M, int N) {
-    int np = 4;
-    while (np < N) np *= 2;
-    const int bpi = 256 / np;
-    int nblk = cdiv_i(M, bpi);
+    int nblk = cdiv_i(M, 256 / solve_np(N));
     return nblk > 768 ? 768 : nblk;      // three resident workgroups per CU: one wave of workgroups
 }
 
@@ -1523,24 +1476,17 @@ static int dud_grads_impl(const Dud<T>& d, const void* gR, const void* OUT, long
         }
         return FL_OK;
     }
-#define FL_DG(NP_)                                                                                                              \
-    {                                                                                                                           \
-        constexpr int BPI = 256 / NP_;                                                                                          \
-        const int per = cdiv_i(cdiv_i(M, nblk), BPI) * BPI;                                                                     \
-        const size_t lds = ((size_t)NP_ * (NP_ + 2) + 4 * (size_t)BPI * (NP_ + 2)) * sizeof(cx<T>);                             \
-        if (gr)                                                                                                                 \
-            hipLaunchKernelGGL((dud_grads_kernel<T, NP_, true>), dim3(nblk), dim3(256), lds, st, d, (const cx<T>*)gR,           \
-                               (const cx<T>*)OUT, s_b, s_n, s_k, B, M, N, K, per, (cx<T>*)gl, gl_sn, (cx<T>*)gr, gr_sn,         \
-                               (cx<T>*)partU, (cx<T>*)gR0, side);                                                               \
-        else                                                                                                                    \
-            hipLaunchKernelGGL((dud_grads_kernel<T, NP_, false>), dim3(nblk), dim3(256), lds, st, d, (const cx<T>*)gR,          \
-                               (const cx<T>*)OUT, s_b, s_n, s_k, B, M, N, K, per, (cx<T>*)gl, gl_sn, (cx<T>*)gr, gr_sn,         \
-                               (cx<T>*)partU, (cx<T>*)gR0, side);                                                               \
-    }
-    if (N <= 4) FL_DG(4) else if (N <= 8) FL_DG(8) else if (N <= 16) FL_DG(16) else if (N <= 32) FL_DG(32) else {
-        if constexpr (sizeof(T) == 4) FL_DG(64) else return FL_ERR_UNSUPPORTED;
-    }
-#undef FL_DG
+    solve_dispatch<T>(N, [&](auto np) {
+        constexpr int NP = decltype(np)::value, BPI = 256 / NP;
+        const int per = cdiv_i(cdiv_i(M, nblk), BPI) * BPI;
+        const size_t lds = ((size_t)NP * (NP + 2) + 4 * (size_t)BPI * (NP + 2)) * sizeof(cx<T>);
+        auto launch = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), lds, st, d, (const cx<T>*)gR, (const cx<T>*)OUT, s_b, s_n, s_k, B, M, N, K, per,
+                               (cx<T>*)gl, gl_sn, (cx<T>*)gr, gr_sn, (cx<T>*)partU, (cx<T>*)gR0, side);
+        };
+        if (gr) launch(dud_grads_kernel<T, NP, true>);
+        else launch(dud_grads_kernel<T, NP, false>);
+    });      // (N is within the limit: checked above)
     FL_CHECK_LAUNCH("solve_dud_grads");
     if (gU) {
         const int count = N * N + (side.on ? 2 * N : 0);       // gU is then (N*N + 2N): [gU | g_b | g_c]
@@ -1565,21 +1511,13 @@ static int solve_scaled_keep_impl(const void* P, long p_pitch, const void* l, lo
     if (B == 0 || M == 0) return FL_OK;
     Dud<T> d = {(const cx<T>*)l, l_sn, 0, nullptr, nullptr, 0, 0};
     d.lu_out = (cx<T>*)LU; d.piv_out = (int*)piv;
-    hipStream_t st = (hipStream_t)stream;
-#define FL_KEEP(NM)                                                                                                                  \
-    {                                                                                                                                \
-        hipLaunchKernelGGL((solve_kernel<T, NM>), dim3(cdiv_i(M, 256 / NM)), dim3(256), 0, st, (const cx<T>*)P, p_pitch, d, 1, 0,    \
-                           (const cx<T>*)R, rs_b, rs_n, rs_k, (cx<T>*)OUT, os_b, os_n, os_k, B, M, N, K);                            \
-        FL_CHECK_LAUNCH("solve_scaled_keep");                                                                                        \
-        return FL_OK;                                                                                                                \
-    }
-    if (N <= 4) FL_KEEP(4)
-    if (N <= 8) FL_KEEP(8)
-    if (N <= 16) FL_KEEP(16)
-    if (N <= 32) FL_KEEP(32)
-    if constexpr (sizeof(T) == 4) FL_KEEP(64)
-#undef FL_KEEP
-    return FL_ERR_UNSUPPORTED;
+    solve_dispatch<T>(N, [&](auto nm) {
+        constexpr int NM = decltype(nm)::value;
+        hipLaunchKernelGGL((solve_kernel<T, NM>), dim3(cdiv_i(M, 256 / NM)), dim3(256), 0, (hipStream_t)stream, (const cx<T>*)P, p_pitch, d, 1, 0,
+                           (const cx<T>*)R, rs_b, rs_n, rs_k, (cx<T>*)OUT, os_b, os_n, os_k, B, M, N, K);
+    });
+    FL_CHECK_LAUNCH("solve_scaled_keep");
+    return FL_OK;
 }
 template <typename T>
 static int solve_kept_adjoint_impl(const void* LU, const void* piv, const void* R, long rs_b, long rs_n,
@@ -1591,36 +1529,20 @@ static int solve_kept_adjoint_impl(const void* LU, const void* piv, const void* 
     FL_REQUIRE(!rv || K == 1, "solve_kept_adjoint: the rank-one right-hand side has one column per batch item");
     FL_REQUIRE(N <= (sizeof(T) == 8 ? 32 : 64), "solve_kept_adjoint: N exceeds the register-resident kernels (%d)", sizeof(T) == 8 ? 32 : 64);
     if (B == 0 || M == 0) return FL_OK;
-    hipStream_t st = (hipStream_t)stream;
-#define FL_KEPT(NM)                                                                                                                  \
-    {                                                                                                                                \
-        hipLaunchKernelGGL((solve_kept_adjoint_kernel<T, NM>), dim3(cdiv_i(M, 256 / NM)), dim3(256), 0, st, (const cx<T>*)LU,       \
-                           (const int*)piv, tile_bins > 0 ? tile_bins : 256 / NM, (const cx<T>*)R, rs_b, rs_n, rs_k, rv, rv_real,    \
-                           (const cx<T>*)rsig, rsig_sb, (cx<T>*)OUT, os_b, os_n, os_k, B, M, N, K);                                  \
-        FL_CHECK_LAUNCH("solve_kept_adjoint");                                                                                       \
-        return FL_OK;                                                                                                                \
-    }
-    if (N <= 4) FL_KEPT(4)
-    if (N <= 8) FL_KEPT(8)
-    if (N <= 16) FL_KEPT(16)
-    if (N <= 32) FL_KEPT(32)
-    if constexpr (sizeof(T) == 4) FL_KEPT(64)
-#undef FL_KEPT
-    return FL_ERR_UNSUPPORTED;
+    solve_dispatch<T>(N, [&](auto nm) {
+        constexpr int NM = decltype(nm)::value;
+        hipLaunchKernelGGL((solve_kept_adjoint_kernel<T, NM>), dim3(cdiv_i(M, 256 / NM)), dim3(256), 0, (hipStream_t)stream, (const cx<T>*)LU,
+                           (const int*)piv, tile_bins > 0 ? tile_bins : 256 / NM, (const cx<T>*)R, rs_b, rs_n, rs_k, rv, rv_real,
+                           (const cx<T>*)rsig, rsig_sb, (cx<T>*)OUT, os_b, os_n, os_k, B, M, N, K);
+    });
+    FL_CHECK_LAUNCH("solve_kept_adjoint");
+    return FL_OK;
 }
 extern "C" {
 int fl_solve_max_n(int f64) { return f64 ? solve_lds_max_n<double>() : solve_lds_max_n<float>(); }
 
 int fl_debug_set_solve_variant(int variant) {
-    g_solve_thr = 1;
-    g_solve_rpl2_p = variant == 3;
-    g_solve_rpl2_16 = variant == 4 ? 1 : 0;
-    g_solve_noprefetch = variant == 5 ? 1 : 0;
-    if (variant == 3 || variant == 4 || variant == 5) variant = 0;
-    if (variant >= 10) {          // 10 + t: in-place kernels with pivot threshold 2^-t
-        g_solve_thr = variant - 10;
-        variant = 0;
-    }
+    FL_REQUIRE(variant == 0 || variant == 1 || variant == 4, "debug_set_solve_variant: variant is 0, 1 or 4 (got %d)", variant);
     g_solve_variant = variant;
     return FL_OK;
 }
@@ -1631,34 +1553,51 @@ long fl_solve_ws_bytes(int N, int M, int f64) {
                : (long)solve_ws_slots<float>(N, M) * N * (N + 1) * (long)sizeof(cx<float>);
 }
 // elements of the kept-factor arrays for N channels and M bins (both tiled by the workgroup's bins: see Dud)
-static int kept_bpb(int N, bool f64) { return 256 / (N <= 4 ? 4 : N <= 8 ? 8 : N <= 16 ? 16 : N <= 32 ? 32 : 64); }
 size_t fl_solve_kept_lu_elems(int N, int M, int f64) {
     if (N <= 0 || M <= 0 || N > (f64 ? 32 : 64)) return 0;
-    const int bpb = kept_bpb(N, f64);
+    const int bpb = 256 / solve_np(N);
     return (size_t)cdiv_i(M, bpb) * N * N * bpb;
 }
 size_t fl_solve_kept_piv_elems(int N, int M, int f64) {
     if (N <= 0 || M <= 0 || N > (f64 ? 32 : 64)) return 0;
-    const int bpb = kept_bpb(N, f64);
+    const int bpb = 256 / solve_np(N);
     return (size_t)cdiv_i(M, bpb) * N * bpb;
 }
 // the FDN form, forward system, with w = A^-H cw^H beside OUT and cz (Dud::wadj): float32, 4 < N <= 16
-int fl_solve_fdn_wadj_supported(int N) { return (N > 4 && N <= 16 && g_solve_variant == 0 && g_solve_rpl2_16 != 1) ? 1 : 0; }
+int fl_solve_fdn_wadj_supported(int N) { return (N > 4 && N <= 16 && g_solve_variant == 0) ? 1 : 0; }
 // the FDN form (fl_solve_fdn_*) with kept factors: 8 < N <= 16 on the two-rows-per-lane kernel (its workgroup's 32 bins are a tile)
 int fl_solve_fdn_keep_tile(int N, int f64) {
     (void)f64;
-    return (N > 8 && N <= 16 && g_solve_variant == 0 && g_solve_rpl2_16 != 1) ? 32 : 0;
+    return (N > 8 && N <= 16 && g_solve_variant == 0) ? 32 : 0;
 }
 int fl_solve_dud_grads_blocks(int M, int N) { return dud_grads_blocks(M, N); }
 }
 
-// The code object lists the kernels in the order in which their dispatchers are first instantiated.  That order is pinned here,
-// ahead of the entries, to the one the code object has always had: rearranging the entries below cannot move a kernel, so a
+// The code object lists the kernels in the order in which they are first named, and the dispatchers above name them from inside
+// generic lambdas, whose order of instantiation is the compiler's.  The order is pinned here, ahead of the entries (the first to
+// instantiate a dispatcher), to the one the code object has always had: rearranging the host code cannot move a kernel, so a
 // host-side change leaves the device code byte-identical (which is how such a change is checked).
 static void pin_kernel_order() {
-    (void)&solve_impl<float>, (void)&solve_impl<double>, (void)&dud_grads_impl<double>;
-    (void)&solve_kept_adjoint_impl<float>, (void)&solve_kept_adjoint_impl<double>;
-    (void)&solve_scaled_keep_impl<float>, (void)&solve_scaled_keep_impl<double>, (void)&dud_grads_impl<float>;
+    (void)&solve_lds_kernel<float, true>, (void)&solve_lds_kernel<float, false>, (void)&solve_inplace_kernel<float, 4, 1>,
+        (void)&solve_kernel<float, 4>, (void)&solve_inplace_kernel<float, 4, 2, true>, (void)&solve_inplace_kernel<float, 4, 2>,
+        (void)&solve_inplace_kernel<float, 8, 1>, (void)&solve_kernel<float, 8>, (void)&solve_inplace_kernel<float, 8, 2, true>,
+        (void)&solve_inplace_kernel<float, 8, 2>, (void)&solve_inplace_kernel<float, 16, 1>, (void)&solve_kernel<float, 16>,
+        (void)&solve_inplace_kernel<float, 16, 2>, (void)&solve_kernel<float, 32>, (void)&solve_kernel<float, 64>;
+    (void)&solve_lds_kernel<double, true>, (void)&solve_lds_kernel<double, false>, (void)&solve_inplace_kernel<double, 4, 1>,
+        (void)&solve_kernel<double, 4>, (void)&solve_inplace_kernel<double, 4, 2, true>, (void)&solve_inplace_kernel<double, 4, 2>,
+        (void)&solve_inplace_kernel<double, 8, 1>, (void)&solve_kernel<double, 8>, (void)&solve_inplace_kernel<double, 8, 2, true>,
+        (void)&solve_inplace_kernel<double, 8, 2>, (void)&solve_inplace_kernel<double, 16, 1>, (void)&solve_kernel<double, 16>,
+        (void)&solve_kernel<double, 32>;
+    (void)&dud_grads_kernel<double, 4, true>, (void)&dud_grads_kernel<double, 4, false>, (void)&dud_grads_kernel<double, 8, true>,
+        (void)&dud_grads_kernel<double, 8, false>, (void)&dud_grads_kernel<double, 16, true>, (void)&dud_grads_kernel<double, 16, false>,
+        (void)&dud_grads_kernel<double, 32, true>, (void)&dud_grads_kernel<double, 32, false>, (void)&dud_grads_final_kernel<double>;
+    (void)&solve_kept_adjoint_kernel<float, 4>, (void)&solve_kept_adjoint_kernel<float, 8>, (void)&solve_kept_adjoint_kernel<float, 16>,
+        (void)&solve_kept_adjoint_kernel<float, 32>, (void)&solve_kept_adjoint_kernel<float, 64>, (void)&solve_kept_adjoint_kernel<double, 4>,
+        (void)&solve_kept_adjoint_kernel<double, 8>, (void)&solve_kept_adjoint_kernel<double, 16>, (void)&solve_kept_adjoint_kernel<double, 32>;
+    (void)&dud_grads_kernel<float, 4, true>, (void)&dud_grads_kernel<float, 4, false>, (void)&dud_grads_kernel<float, 8, true>,
+        (void)&dud_grads_kernel<float, 8, false>, (void)&dud_grads_kernel<float, 16, true>, (void)&dud_grads_kernel<float, 16, false>,
+        (void)&dud_grads_kernel<float, 32, true>, (void)&dud_grads_kernel<float, 32, false>, (void)&dud_grads_kernel<float, 64, true>,
+        (void)&dud_grads_kernel<float, 64, false>, (void)&dud_grads_final_kernel<float>;
 }
 
 // ---------------------------------------------------------------- the entries that exist in both precisions (FL_ENTRY_C64_C128, common.h)

@@ -699,7 +699,8 @@ int fl_solve_fdn_c128(const void* l, long l_sn, long l_sf, const void* l2, long 
                       int cw_real, void* cz, long cz_sb, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, void* stream);
 /* tuning/test hook: 0 (default) = N <= 16 factor with rows exchanged in place (compile-time DPP broadcasts,
  * threshold pivoting; two rows per lane for the factored loop at N in (4, 16]); 1 = the shuffle kernel with implicit
- * partial pivoting for every N; 4 = the in-place kernels with one row per lane */
+ * partial pivoting for every N; 4 = the in-place kernels with one row per lane.  Any other value is FL_ERR_BAD_ARG and
+ * changes nothing. */
 int fl_debug_set_solve_variant(int variant);
 
 /* ------------------------------------------------------------------------------------------------

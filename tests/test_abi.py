@@ -199,6 +199,26 @@ def test_walk_hook_accepts_only_the_remaining_modes():
         assert L.fl_debug_set_walk(1, 0, 0, None) == 0
 
 
+def test_solve_variant_hook_accepts_only_the_remaining_codes():
+    """fl_debug_set_solve_variant: 0 (default), 1 (shuffle kernel for every N) and 4 (in-place kernels, one row per lane); the
+    codes of the finished sweeps (3: two-rows-per-lane kernel for a materialised P, 5: right-hand side fetched behind the
+    elimination, 10 + t: pivot threshold 2^-t) and unknown ones are errors with a message."""
+    from flamo_amd import _lib
+    L = _lib.lib()
+    probes = lambda: (L.fl_solve_fdn_wadj_supported(16), L.fl_solve_fdn_keep_tile(16, 0))  # noqa: E731
+    try:
+        for ok, want in ((0, (1, 32)), (1, (0, 0)), (4, (0, 0))):
+            assert L.fl_debug_set_solve_variant(ok) == 0, ok
+            assert probes() == want, ok
+        for bad in (3, 5, 10, 11, 12, 2, -1):
+            assert L.fl_debug_set_solve_variant(bad) == -1, bad
+            assert f"got {bad})".encode() in L.fl_last_error(), bad      # this call's own message, not an earlier one
+            assert probes() == (0, 0), bad                              # a refused call changes no state (still code 4)
+    finally:
+        assert L.fl_debug_set_solve_variant(0) == 0
+    assert probes() == (1, 32)
+
+
 def test_ops_fail_loudly_without_gpu_tensors():
     from flamo_amd import ops
     with pytest.raises(RuntimeError, match="no CPU fallback"):
