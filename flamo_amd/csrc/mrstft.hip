@@ -1,0 +1,470 @@
+// Multi-resolution STFT criterion (gfx950 / MI355X): for each resolution (n_fft, hop, win) the magnitude spectrograms of
+// prediction and target, M = sqrt(max(|X|^2, eps)), and of them
+//
+//   sc = |M_t - M_p|_F / |M_t|_F      log = mean |log M_p - log M_t|      lin = mean |M_p - M_t|
+//
+// over all rows (batch x channel columns), bins and frames; the loss is the mean over the resolutions of the weighted three
+// (include/flamo_hip_mrstft.h has the definition in full).  In torch this is, per resolution, two stft, clamp, sqrt, two log,
+// three reductions and the backward of all of it.
+//
+// Launches: THREE forward (frames, combine, final) and TWO backward (frames, overlap-add), for all resolutions, rows and both
+// signals together, whatever the number of resolutions: the frame kernels' grid is the list of all (resolution, row, frame)
+// triples, and the frame length is uniform per workgroup.
+//
+// Frames.  One wavefront per frame, as in avgpow.hip: the n_fft real samples are Nc = n_fft / 2 complex ones, P = Nc / 64 per
+// lane (2, 4, 8, 16 for n_fft = 256 .. 2048).  The window is applied while loading and only the samples under its support
+// [lpad, lpad + win) are read.  The packed transform is a Stockham walk of three passes, radix P x 8 x 8, every pass an
+// in-register transform of regfft.h: the first straight on the loaded values (lane j holds z[j + 64 r]), the two radix-8
+// passes on 8 P butterflies (P / 8 per lane; with P < 8 the lanes from 8 P on idle), with an exchange through LDS behind each.
+// The Nc + 1 bins of the real transform are split from the packed one bin by bin.  The spectrograms never reach memory: a
+// frame leaves four doubles (sum (M_t - M_p)^2, sum M_t^2, sum |log M_p - log M_t|, sum |M_p - M_t|), the combine adds them
+// per resolution in a fixed order (no atomics: two runs give the same bits), the final kernel forms the loss and the three
+// factors of dL/dM_p the backward pass needs.  The backward frame kernel recomputes both transforms, forms
+// dL/dX = dL/dM_p X / M_p (zero where |X|^2 <= eps), runs the adjoint of the split and the inverse walk, and writes the win
+// samples under the window; the overlap-add gathers per sample, resolution by resolution and frame by frame, with the
+// reflected margins folded back onto the interior samples they mirror.
+//
+// Precision.  The signals, the frame gradients and the gradient have the signals' type; everything between is a double in
+// float32 too (see `C` below), so the two precisions run the same kernels and differ in their loads and stores.
+//
+// LDS.  A[Nc + 64] complex doubles, index i stored at i + (i >> log2 P): one pad per P values, so that the first pass's stores
+// (lane j writes j P + t: a stride of P + 1 values = 4 (P + 1) dwords, whose gcd with the 64 banks is 4 = the width of one
+// value) and the radix-8 passes' loads (consecutive j) both spread over all banks.  Sized for n_fft = 2048: 1088 values, 17 KB.
+// Beside it the forward kernel keeps the prediction's clamped |X|^2 (1025 doubles, 8 KB) and the backward kernel the
+// prediction's bins, then dL/dX (1025 complex doubles, 16 KB): 25 KB forward and 33 KB backward per wavefront, six and four
+// wavefronts per CU of its 160 KB.
+//
+// Registers, 16 per lane (n_fft = 2048): the 16 complex doubles of a pass are 64 VGPRs; a radix-16 transform of regfft.h holds
+// its input, the intermediate products and four-value temporaries at once, and the compiler reports 170 VGPRs for the forward
+// and 200 for the backward kernel, no scratch: under the 256 of two wavefronts per SIMD, and at four to six wavefronts per CU
+// it is LDS, not registers, that bounds the occupancy.
+#include "common.h"
+#include "regfft.h"
+#include "../../include/flamo_hip_mrstft.h"
+
+namespace fl {
+namespace mrstft {
+
+// Everything between the loads of the signals and the stores of the gradient is a double, in float32 too: a float32 transform
+// leaves an absolute error of ~6e-8 |frame| on every bin, and the log term weighs a bin by 1 / M^2 -- on decaying responses the
+// quiet bins then carry a relative error thousands of roundoffs large into the gradient (as the float32 torch lines do).
+using C = double;
+
+constexpr int MAXR = 8, NFFT_MIN = 256, NFFT_MAX = 2048, NTW = 2048;
+constexpr int NC_MAX = NFFT_MAX / 2, ALDS = NC_MAX + 64, NB_MAX = NC_MAX + 1;
+constexpr long T_MAX = 1L << 30, BLOCKS_MAX = (1L << 31) - 1, SAMPLES_MAX = 1L << 38;
+constexpr int KEEP_STRIDE = 8, KEEP_LOSS = KEEP_STRIDE * MAXR, KEEP_DOUBLES = KEEP_LOSS + 1;
+
+struct Res {
+    int nfft, hop, win, lpad;
+    long F;        // frames per row
+    long blk0;     // first workgroup of the frame kernels
+    long g0;       // first element in gframes
+    long w0;       // first element in the window table
+};
+struct Plan {
+    int R;
+    long B, T, N, rows, blocks, gelems;
+    Res r[MAXR];
+};
+struct Strides {
+    long b, t, c;
+};
+
+static bool make_plan(long B, long T, long N, int R, const int* res, Plan& p) {
+    if (!res || R < 1 || R > MAXR || B < 1 || N < 1 || T < 1 || T > T_MAX) return false;
+    if (B > SAMPLES_MAX / T || B * T > SAMPLES_MAX / N) return false;
+    p.R = R; p.B = B; p.T = T; p.N = N; p.rows = B * N;
+    long blocks = 0, g = 0, w = 0;
+    for (int r = 0; r < R; ++r) {
+        const int nfft = res[3 * r], hop = res[3 * r + 1], win = res[3 * r + 2];
+        if (nfft < NFFT_MIN || nfft > NFFT_MAX || (nfft & (nfft - 1)) || hop < 1 || win < 1 || win > nfft || T <= nfft / 2) return false;
+        Res& q = p.r[r];
+        q.nfft = nfft; q.hop = hop; q.win = win; q.lpad = (nfft - win) / 2;
+        q.F = 1 + T / hop;
+        q.blk0 = blocks; q.g0 = g; q.w0 = w;
+        if (q.F > BLOCKS_MAX / p.rows) return false;
+        blocks += p.rows * q.F;
+        if (blocks > BLOCKS_MAX) return false;
+        g += p.rows * q.F * win;
+        w += win;
+    }
+    p.blocks = blocks; p.gelems = g;
+    return true;
+}
+
+template <int P> struct Log2;
+template <> struct Log2<2> { static constexpr int v = 1; };
+template <> struct Log2<4> { static constexpr int v = 2; };
+template <> struct Log2<8> { static constexpr int v = 3; };
+template <> struct Log2<16> { static constexpr int v = 4; };
+
+template <int P>
+__device__ inline int zp(int i) { return i + (i >> Log2<P>::v); }
+
+__device__ inline double wave_sum(double a) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) a += __shfl_xor(a, off, 64);
+    return a;
+}
+
+// One radix-8 Stockham pass over the 64 P values in A, NS = the product of the radices before it: butterfly j reads
+// A[j + t 8 P], t < 8, multiplies by W_{8 NS}^(t (j mod NS)) and writes A[(j / NS) 8 NS + (j mod NS) + t NS].
+template <int P, int NS, bool INV>
+__device__ inline void pass8(cx<C>* A, const cx<C>* __restrict__ tw, int lane) {
+    constexpr int NBF = 8 * P, NI = P >= 8 ? P / 8 : 1, STEP = NTW / (8 * NS);
+    cx<C> u[NI][8];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        const int j = lane + 64 * i;
+        if (j < NBF) {
+            const int jm = j & (NS - 1);
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                u[i][t] = A[zp<P>(j + t * NBF)];
+                if (t > 0) {
+                    const cx<C> w = tw[t * jm * STEP];
+                    u[i][t] = mul_plain(u[i][t], INV ? conj(w) : w);
+                }
+            }
+            RegFFT<C, 8, INV>::run(u[i]);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        const int j = lane + 64 * i;
+        if (j < NBF) {
+            const int jm = j & (NS - 1), base = (j - jm) * 8 + jm;
+#pragma unroll
+            for (int t = 0; t < 8; ++t) A[zp<P>(base + t * NS)] = u[i][t];
+        }
+    }
+    __syncthreads();
+}
+
+// Z[k] = sum_n z[n] exp(-+2 pi i k n / (64 P)) by one wavefront.  In: v[r] = z[lane + 64 r].  Out: A[zp(k)] = Z[k], visible
+// to every lane.  tw[j] = exp(-2 pi i j / 2048).
+template <int P, bool INV>
+__device__ inline void fft_wave(cx<C> (&v)[P], cx<C>* A, const cx<C>* __restrict__ tw, int lane) {
+    RegFFT<C, P, INV>::run(v);
+#pragma unroll
+    for (int t = 0; t < P; ++t) A[zp<P>(lane * P + t)] = v[t];
+    __syncthreads();
+    pass8<P, P, INV>(A, tw, lane);
+    pass8<P, 8 * P, INV>(A, tw, lane);
+}
+
+// sample j of the row reflect-padded by `half` on each side (j counted from the first padded sample); T > half
+template <typename T>
+__device__ inline T padded(const T* __restrict__ y, long stride, long Tn, long j, int half) {
+    long t = j - half;
+    if (t < 0) t = -t;
+    if (t >= Tn) t = 2 * (Tn - 1) - t;
+    return y[t * stride];
+}
+
+// the windowed frame f as 64 P complex values (even samples real, odd samples imaginary), transformed into A; only the
+// samples under the window are read
+template <typename T, int P>
+__device__ inline void frame_transform(const T* __restrict__ y, long stride, long Tn, long f, const Res& q, const C* __restrict__ w,
+                                       const cx<C>* __restrict__ tw, cx<C>* A, int lane) {
+    cx<C> v[P];
+    const long j0 = f * q.hop;
+#pragma unroll
+    for (int r = 0; r < P; ++r) {
+        const int n = 2 * (lane + 64 * r) - q.lpad;      // place under the window of the even sample
+        C re = 0.0, im = 0.0;
+        if (n >= 0 && n < q.win) re = (C)padded(y, stride, Tn, j0 + n + q.lpad, 64 * P) * w[n];
+        if (n + 1 >= 0 && n + 1 < q.win) im = (C)padded(y, stride, Tn, j0 + n + 1 + q.lpad, 64 * P) * w[n + 1];
+        v[r] = cx<C>(re, im);
+    }
+    fft_wave<P, false>(v, A, tw, lane);
+}
+
+// bin k (0 .. Nc) of the real transform from the packed one: X[k] = E[k] + W_{2 Nc}^k O[k],
+// E = (Z[k] + conj Z[Nc - k]) / 2, O = -i (Z[k] - conj Z[Nc - k]) / 2
+template <int P>
+__device__ inline cx<C> split_bin(const cx<C>* A, const cx<C>* __restrict__ tw, int k) {
+    constexpr int NC = 64 * P;
+    if (k == NC) {
+        const cx<C> z = A[0];
+        return cx<C>(z.x - z.y, 0.0);
+    }
+    const cx<C> a = A[zp<P>(k)], b = conj(A[zp<P>((NC - k) & (NC - 1))]);
+    const cx<C> e = 0.5 * (a + b), o = 0.5 * mul_mi(a - b);
+    return e + mul_plain(o, tw[k * (NTW / (2 * NC))]);
+}
+
+__device__ inline double power(cx<C> x) { return x.x * x.x + x.y * x.y; }
+
+// (resolution, row, frame) of a workgroup
+__device__ inline void locate(const Plan& p, long blk, int& r, long& row, long& f) {
+    r = p.R - 1;
+    while (r > 0 && blk < p.r[r].blk0) --r;
+    const long local = blk - p.r[r].blk0;
+    row = local / p.r[r].F;
+    f = local - row * p.r[r].F;
+}
+
+__device__ inline long row_offset(const Plan& p, long row, Strides s) {
+    const long b = row / p.N, c = row - b * p.N;
+    return b * s.b + c * s.c;
+}
+
+// ---------------------------------------------------------------- forward: the four sums of a frame
+template <typename T, int P>
+__device__ inline void frame_sums(const T* __restrict__ yp, long sp, const T* __restrict__ yt, long st, long Tn, long f, const Res& q,
+                                  const C* __restrict__ w, const cx<C>* __restrict__ tw, double eps, cx<C>* A, double* Sp,
+                                  double* __restrict__ out, int lane) {
+    constexpr int NC = 64 * P;
+    frame_transform<T, P>(yp, sp, Tn, f, q, w, tw, A, lane);
+    for (int k = lane; k <= NC; k += 64) Sp[k] = fmax(power(split_bin<P>(A, tw, k)), eps);
+    __syncthreads();
+    frame_transform<T, P>(yt, st, Tn, f, q, w, tw, A, lane);
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    for (int k = lane; k <= NC; k += 64) {
+        const double pt = fmax(power(split_bin<P>(A, tw, k)), eps), pp = Sp[k];
+        const double mp = sqrt(pp), mt = sqrt(pt), d = mt - mp;
+        s0 += d * d;
+        s1 += mt * mt;
+        s2 += fabs(0.5 * (log(pp) - log(pt)));
+        s3 += fabs(d);
+    }
+    s0 = wave_sum(s0);
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    s3 = wave_sum(s3);
+    if (lane == 0) {
+        out[0] = s0;
+        out[1] = s1;
+        out[2] = s2;
+        out[3] = s3;
+    }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(64) mrstft_frames_kernel(const T* __restrict__ yp, Strides sp, const T* __restrict__ yt, Strides st,
+                                                           Plan p, const C* __restrict__ wtab, const cx<C>* __restrict__ tw,
+                                                           double eps, double* __restrict__ partial) {
+    __shared__ cx<C> A[ALDS];
+    __shared__ double Sp[NB_MAX];
+    const int lane = threadIdx.x;
+    int r;
+    long row, f;
+    locate(p, blockIdx.x, r, row, f);
+    const Res& q = p.r[r];
+    const T* a = yp + row_offset(p, row, sp);
+    const T* b = yt + row_offset(p, row, st);
+    const C* w = wtab + q.w0;
+    double* out = partial + 4 * (long)blockIdx.x;
+    switch (q.nfft) {
+        case 256: frame_sums<T, 2>(a, sp.t, b, st.t, p.T, f, q, w, tw, eps, A, Sp, out, lane); break;
+        case 512: frame_sums<T, 4>(a, sp.t, b, st.t, p.T, f, q, w, tw, eps, A, Sp, out, lane); break;
+        case 1024: frame_sums<T, 8>(a, sp.t, b, st.t, p.T, f, q, w, tw, eps, A, Sp, out, lane); break;
+        default: frame_sums<T, 16>(a, sp.t, b, st.t, p.T, f, q, w, tw, eps, A, Sp, out, lane); break;
+    }
+}
+
+// ---------------------------------------------------------------- combine: one workgroup per resolution, a fixed order
+__global__ void __launch_bounds__(256) mrstft_combine_kernel(const double* __restrict__ partial, Plan p, double* __restrict__ keep) {
+    __shared__ double red[4][4];
+    const int r = blockIdx.x;
+    const long n = p.rows * p.r[r].F;
+    const double* q = partial + 4 * p.r[r].blk0;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (long i = threadIdx.x; i < n; i += 256) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) s[c] += q[4 * i + c];
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        s[c] = wave_sum(s[c]);
+        if (lane == 0) red[c][wave] = s[c];
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) keep[KEEP_STRIDE * r + threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+}
+
+// one thread: the loss and, per resolution, the factors of dL/dM_p = c0 (M_p - M_t) + c1 sign / M_p + c2 sign
+// (the norm's gradient is 0 at M_p = M_t, as torch's is)
+template <typename T>
+__global__ void __launch_bounds__(64) mrstft_final_kernel(Plan p, double w_sc, double w_log, double w_lin, double* __restrict__ keep,
+                                                         T* __restrict__ loss) {
+    if (threadIdx.x != 0) return;
+    double l = 0.0;
+    for (int r = 0; r < p.R; ++r) {
+        double* k = keep + KEEP_STRIDE * r;
+        const double n = (double)p.rows * (double)p.r[r].F * (double)(p.r[r].nfft / 2 + 1);
+        const double D = k[0], S = k[1];
+        l += w_sc * (sqrt(D) / sqrt(S)) + w_log * (k[2] / n) + w_lin * (k[3] / n);
+        k[4] = D > 0.0 ? w_sc / (p.R * sqrt(D) * sqrt(S)) : 0.0;
+        k[5] = w_log / (p.R * n);
+        k[6] = w_lin / (p.R * n);
+        k[7] = 0.0;
+    }
+    l /= p.R;
+    keep[KEEP_LOSS] = l;
+    loss[0] = (T)l;
+}
+
+// ---------------------------------------------------------------- backward: the gradient of a frame's windowed samples
+template <typename T, int P>
+__device__ inline void frame_grad(const T* __restrict__ yp, long sp, const T* __restrict__ yt, long st, long Tn, long f, const Res& q,
+                                  const C* __restrict__ w, const cx<C>* __restrict__ tw, double eps, const double* __restrict__ coef,
+                                  cx<C>* A, cx<C>* Y, T* __restrict__ out, int lane) {
+    constexpr int NC = 64 * P;
+    const double c0 = coef[4], c1 = coef[5], c2 = coef[6];
+    frame_transform<T, P>(yp, sp, Tn, f, q, w, tw, A, lane);
+    for (int k = lane; k <= NC; k += 64) Y[k] = split_bin<P>(A, tw, k);
+    __syncthreads();
+    frame_transform<T, P>(yt, st, Tn, f, q, w, tw, A, lane);
+    // G = dL/dM_p X / M_p; the Hermitian spectrum whose inverse transform is Re sum_{k <= Nc} G[k] exp(+2 pi i k n / n_fft):
+    // G / 2 inside, Re G at the two ends
+    for (int k = lane; k <= NC; k += 64) {
+        const cx<C> x = Y[k];
+        const double pp = power(x);
+        cx<C> g(0.0, 0.0);
+        if (pp > eps) {
+            const double pt = fmax(power(split_bin<P>(A, tw, k)), eps);
+            const double mp = sqrt(pp), mt = sqrt(pt);
+            const double sg = pp > pt ? 1.0 : (pp < pt ? -1.0 : 0.0);
+            const double s = (c0 * (mp - mt) + c1 * sg / mp + c2 * sg) / mp;
+            g = (k == 0 || k == NC) ? cx<C>(s * x.x, 0.0) : cx<C>(0.5 * s * x.x, 0.5 * s * x.y);
+        }
+        Y[k] = g;
+    }
+    __syncthreads();
+    // v[m] = y[2 m] + i y[2 m + 1] = sum_{k < Nc} ((Y[k] + conj Y[Nc - k]) + i conj(W^k) (Y[k] - conj Y[Nc - k])) exp(+2 pi i k m / Nc)
+    cx<C> v[P];
+#pragma unroll
+    for (int r = 0; r < P; ++r) {
+        const int k = lane + 64 * r;
+        const cx<C> a = Y[k], b = conj(Y[NC - k]);
+        v[r] = (a + b) + mul_i(mul_plain(a - b, conj(tw[k * (NTW / (2 * NC))])));
+    }
+    fft_wave<P, true>(v, A, tw, lane);
+#pragma unroll
+    for (int r = 0; r < P; ++r) {
+        const int m = lane + 64 * r, n = 2 * m - q.lpad;
+        const cx<C> z = A[zp<P>(m)];
+        if (n >= 0 && n < q.win) out[n] = (T)(z.x * w[n]);
+        if (n + 1 >= 0 && n + 1 < q.win) out[n + 1] = (T)(z.y * w[n + 1]);
+    }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(64) mrstft_frames_bwd_kernel(const T* __restrict__ yp, Strides sp, const T* __restrict__ yt, Strides st,
+                                                               Plan p, const C* __restrict__ wtab, const cx<C>* __restrict__ tw,
+                                                               double eps, const double* __restrict__ keep, T* __restrict__ gframes) {
+    __shared__ cx<C> A[ALDS];
+    __shared__ cx<C> Y[NB_MAX];
+    const int lane = threadIdx.x;
+    int r;
+    long row, f;
+    locate(p, blockIdx.x, r, row, f);
+    const Res& q = p.r[r];
+    const T* a = yp + row_offset(p, row, sp);
+    const T* b = yt + row_offset(p, row, st);
+    const C* w = wtab + q.w0;
+    const double* coef = keep + KEEP_STRIDE * r;
+    T* out = gframes + q.g0 + (row * q.F + f) * q.win;
+    switch (q.nfft) {
+        case 256: frame_grad<T, 2>(a, sp.t, b, st.t, p.T, f, q, w, tw, eps, coef, A, Y, out, lane); break;
+        case 512: frame_grad<T, 4>(a, sp.t, b, st.t, p.T, f, q, w, tw, eps, coef, A, Y, out, lane); break;
+        case 1024: frame_grad<T, 8>(a, sp.t, b, st.t, p.T, f, q, w, tw, eps, coef, A, Y, out, lane); break;
+        default: frame_grad<T, 16>(a, sp.t, b, st.t, p.T, f, q, w, tw, eps, coef, A, Y, out, lane); break;
+    }
+}
+
+// ---------------------------------------------------------------- overlap-add: a gather per sample, in a fixed order
+template <typename T>
+__global__ void __launch_bounds__(256) mrstft_ola_kernel(const T* __restrict__ gframes, Plan p, const T* __restrict__ gloss,
+                                                        T* __restrict__ gy) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= p.rows * p.T) return;
+    const long row = e / p.T, t = e - row * p.T;
+    double acc = 0.0;
+    for (int r = 0; r < p.R; ++r) {
+        const Res& q = p.r[r];
+        const int half = q.nfft / 2;
+        const T* g = gframes + q.g0 + row * q.F * q.win;
+        // the frames that hold the padded sample j under their window, first to last
+        auto gather = [&](long j) {
+            const long hi = j - q.lpad, lo = hi - q.win + 1;
+            if (hi < 0) return;
+            const long f0 = lo <= 0 ? 0 : (lo + q.hop - 1) / q.hop;
+            const long f1 = min(q.F - 1, hi / q.hop);
+            for (long f = f0; f <= f1; ++f) acc += (double)g[f * q.win + (hi - f * q.hop)];
+        };
+        gather(t + half);                                              // the sample itself
+        if (t >= 1 && t <= half) gather(half - t);                     // its image in the left margin
+        if (t <= p.T - 2) gather(2 * (p.T - 1) - t + half);            // ... in the right margin (frames beyond the last hold none)
+    }
+    const long b = row / p.N, c = row - b * p.N;
+    gy[(b * p.T + t) * p.N + c] = (T)((double)gloss[0] * acc);
+}
+
+}  // namespace mrstft
+}  // namespace fl
+
+using namespace fl;
+using namespace fl::mrstft;
+
+extern "C" long fl_mrstft_blocks(long B, long T, long N, int R, int* res) {
+    Plan p;
+    return make_plan(B, T, N, R, res, p) ? p.blocks : -1;
+}
+extern "C" long fl_mrstft_gframe_elems(long B, long T, long N, int R, int* res) {
+    Plan p;
+    return make_plan(B, T, N, R, res, p) ? p.gelems : -1;
+}
+extern "C" long fl_mrstft_keep_doubles(void) { return KEEP_DOUBLES; }
+
+#define FL_MRSTFT_PLAN(who)                                                                                                  \
+    Plan p;                                                                                                                  \
+    FL_REQUIRE(make_plan(B, Tn, N, R, res, p),                                                                               \
+               who ": bad sizes (1 <= R <= 8 resolutions, n_fft a power of two from 256 to 2048, 1 <= win <= n_fft, hop >= 1, " \
+                   "n_fft / 2 < T <= 2^30, fewer than 2^31 frames and at most 2^38 samples in all)")
+
+// (Tn: the header's T, the signals' length -- T is the precision here)
+FL_ENTRY_F32_F64(fl_mrstft_fwd, (const void* yp, long spb, long spt, long spc, const void* yt, long stb, long stt, long stc, long B, long Tn,
+                                 long N, int R, int* res, const void* wtab, const void* tw, double w_sc, double w_log, double w_lin,
+                                 double eps, void* partial, void* keep, void* loss, void* stream),
+                 (yp, spb, spt, spc, yt, stb, stt, stc, B, Tn, N, R, res, wtab, tw, w_sc, w_log, w_lin, eps, partial, keep, loss, stream)) {
+    FL_REQUIRE(yp && yt && res && wtab && tw && partial && keep && loss, "mrstft_fwd: null pointer");
+    FL_MRSTFT_PLAN("mrstft_fwd");
+    FL_REQUIRE(eps >= 0.0, "mrstft_fwd: eps must be >= 0");
+    FL_REQUIRE((uintptr_t)tw % (2 * sizeof(C)) == 0, "mrstft_fwd: the twiddle table must be aligned to its complex elements");
+    hipLaunchKernelGGL((mrstft_frames_kernel<T>), dim3((unsigned)p.blocks), dim3(64), 0, (hipStream_t)stream, (const T*)yp,
+                       Strides{spb, spt, spc}, (const T*)yt, Strides{stb, stt, stc}, p, (const C*)wtab, (const cx<C>*)tw, eps,
+                       (double*)partial);
+    FL_CHECK_LAUNCH("mrstft_frames");
+    hipLaunchKernelGGL(mrstft_combine_kernel, dim3((unsigned)p.R), dim3(256), 0, (hipStream_t)stream, (const double*)partial, p,
+                       (double*)keep);
+    FL_CHECK_LAUNCH("mrstft_combine");
+    hipLaunchKernelGGL((mrstft_final_kernel<T>), dim3(1), dim3(64), 0, (hipStream_t)stream, p, w_sc, w_log, w_lin, (double*)keep,
+                       (T*)loss);
+    FL_CHECK_LAUNCH("mrstft_final");
+    return FL_OK;
+}
+
+FL_ENTRY_F32_F64(fl_mrstft_bwd, (const void* yp, long spb, long spt, long spc, const void* yt, long stb, long stt, long stc, long B, long Tn,
+                                 long N, int R, int* res, const void* wtab, const void* tw, double eps, const void* keep,
+                                 const void* gloss, void* gframes, void* gy, void* stream),
+                 (yp, spb, spt, spc, yt, stb, stt, stc, B, Tn, N, R, res, wtab, tw, eps, keep, gloss, gframes, gy, stream)) {
+    FL_REQUIRE(yp && yt && res && wtab && tw && keep && gloss && gframes && gy, "mrstft_bwd: null pointer");
+    FL_MRSTFT_PLAN("mrstft_bwd");
+    FL_REQUIRE(eps >= 0.0, "mrstft_bwd: eps must be >= 0");
+    FL_REQUIRE((uintptr_t)tw % (2 * sizeof(C)) == 0, "mrstft_bwd: the twiddle table must be aligned to its complex elements");
+    hipLaunchKernelGGL((mrstft_frames_bwd_kernel<T>), dim3((unsigned)p.blocks), dim3(64), 0, (hipStream_t)stream, (const T*)yp,
+                       Strides{spb, spt, spc}, (const T*)yt, Strides{stb, stt, stc}, p, (const C*)wtab, (const cx<C>*)tw, eps,
+                       (const double*)keep, (T*)gframes);
+    FL_CHECK_LAUNCH("mrstft_frames_bwd");
+    const long blocks = (p.rows * p.T + 255) / 256;
+    hipLaunchKernelGGL((mrstft_ola_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const T*)gframes, p,
+                       (const T*)gloss, (T*)gy);
+    FL_CHECK_LAUNCH("mrstft_ola");
+    return FL_OK;
+}

@@ -3001,6 +3001,126 @@ def average_power(y_pred: torch.Tensor, y_true: torch.Tensor, stride: Tuple[int,
     return _AveragePower.apply(y_pred, t, si, sj)
 
 
+MRSTFT_MAX_RES, MRSTFT_NFFTS, MRSTFT_MAX_T = 8, (256, 512, 1024, 2048), 1 << 30      # what csrc/mrstft.hip takes
+MRSTFT_NTW = 2048                                                                  # its one twiddle table
+_mrstft_tables = {}
+
+
+def _mrstft_resolutions(resolutions):
+    """((n_fft, hop, win), ...) as a tuple of int triples, or None when it is not one"""
+    try:
+        res = tuple(tuple(int(v) for v in r) for r in resolutions)
+        same = all(len(r) == 3 and all(a == b for a, b in zip(r, q)) for r, q in zip(res, resolutions))
+    except (TypeError, ValueError):
+        return None
+    return res if same and len(res) == len(tuple(resolutions)) else None
+
+
+def mrstft_supported(shape, resolutions, eps=1e-8) -> bool:
+    """whether ``mrstft_loss`` takes (B, T, N) signals under these resolutions: 1 to 8 of them, n_fft a power of two from 256
+    to 2048, 1 <= win <= n_fft, hop >= 1, n_fft / 2 < T <= 2^30, fewer than 2^31 frames and at most 2^38 samples in all"""
+    res = _mrstft_resolutions(resolutions)
+    if res is None or not 1 <= len(res) <= MRSTFT_MAX_RES or len(shape) != 3 or min(shape) < 1:
+        return False
+    B, T, N = (int(s) for s in shape)
+    try:
+        if not float(eps) >= 0.0:
+            return False
+    except (TypeError, ValueError):
+        return False
+    if T > MRSTFT_MAX_T or B * T * N > 1 << 38:
+        return False
+    if any(n not in MRSTFT_NFFTS or hop < 1 or not 1 <= win <= n or T <= n // 2 for n, hop, win in res):
+        return False
+    return sum(B * N * (1 + T // hop) for _, hop, _ in res) < 1 << 31
+
+
+def _mrstft_consts(res, dev: torch.device):
+    """(windows, twiddles, the resolutions as a host int array) cached per (resolutions, device): the periodic Hann windows of
+    the resolutions, one behind the other, made on the host -- float64 like the twiddles under either precision of the
+    signals, since the kernels transform in double"""
+    key = (res, dev.index if dev.index is not None else torch.cuda.current_device())
+    ent = _mrstft_tables.get(key)
+    if ent is None:
+        w = torch.cat([torch.hann_window(win, dtype=torch.float64) for _, _, win in res]).to(dev)
+        flat = [v for r in res for v in r]
+        ent = _mrstft_tables[key] = (w, (ctypes.c_int * len(flat))(*flat))
+    return ent[0], twiddles(MRSTFT_NTW, torch.float64, dev), ent[1]
+
+
+class _MRSTFT(torch.autograd.Function):
+    """the multi-resolution STFT criterion, one node over the prediction: frame kernel, combine and final kernel forward
+    (keeping the four sums and the factors of dL/dM per resolution); frame kernel and overlap-add backward"""
+
+    @staticmethod
+    def forward(ctx, y, t, res, weights, eps):
+        dev = _require_gpu(y, t)
+        L = _lib.lib()
+        B, T, N = y.shape
+        w, tw, cres = _mrstft_consts(res, dev)
+        R = len(res)
+        blocks = L.fl_mrstft_blocks(B, T, N, R, cres)
+        partial = torch.empty(4 * blocks, dtype=torch.float64, device=dev)
+        keep = torch.empty(L.fl_mrstft_keep_doubles(), dtype=torch.float64, device=dev)
+        loss = _scalar_loss(y.dtype, dev)
+        with kernel_timer.span("mrstft_fwd"):
+            _lib.check(_fn("fl_mrstft_fwd", y.dtype)(y.data_ptr(), *y.stride(), t.data_ptr(), *t.stride(), B, T, N, R, cres,
+                                                     w.data_ptr(), tw.data_ptr(), weights[0], weights[1], weights[2], eps,
+                                                     partial.data_ptr(), keep.data_ptr(), loss.data_ptr(), _stream()), "mrstft_fwd")
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(y, t, keep)
+            ctx.cfg = (res, eps)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        y, t, keep = ctx.saved_tensors
+        res, eps = ctx.cfg
+        L = _lib.lib()
+        B, T, N = y.shape
+        w, tw, cres = _mrstft_consts(res, y.device)
+        R = len(res)
+        gframes = torch.empty(L.fl_mrstft_gframe_elems(B, T, N, R, cres), dtype=y.dtype, device=y.device)
+        gy = torch.empty((B, T, N), dtype=y.dtype, device=y.device)
+        g = _gloss_as(gloss, y.dtype)
+        with kernel_timer.span("mrstft_bwd"):
+            _lib.check(_fn("fl_mrstft_bwd", y.dtype)(y.data_ptr(), *y.stride(), t.data_ptr(), *t.stride(), B, T, N, R, cres,
+                                                     w.data_ptr(), tw.data_ptr(), eps, keep.data_ptr(), g.data_ptr(),
+                                                     gframes.data_ptr(), gy.data_ptr(), _stream()), "mrstft_bwd")
+        return gy, None, None, None, None
+
+
+def mrstft_loss(y_pred: torch.Tensor, y_true: torch.Tensor, resolutions=((1024, 120, 600), (2048, 240, 1200), (512, 50, 240)),
+                weights=(1.0, 1.0, 0.0), eps: float = 1e-8) -> torch.Tensor:
+    """The multi-resolution STFT criterion of (B, T, N) signals (flamo_amd.optimize.MultiResoSTFT has the definition): for each
+    resolution (n_fft, hop, win), the magnitude spectrograms M = sqrt(clamp(|X|^2, min=eps)) of every (batch, channel) column
+    of prediction and target -- periodic Hann window of ``win`` samples centred in the frame, reflect padding -- and
+    ``weights`` = (w_sc, w_log_mag, w_lin_mag) times |M_t - M_p|_F / |M_t|_F, mean |log M_p - log M_t| and mean |M_p - M_t|;
+    the mean over the resolutions.  One autograd node over the prediction, five launches in all (three forward, two backward)
+    whatever the number of resolutions; the signals are read through their strides, nothing is copied, nothing is read back.
+    The target takes no gradient.  Sizes: ``mrstft_supported``."""
+    _require_gpu(y_pred, y_true)
+    if y_pred.dim() != 3 or y_pred.dtype not in (torch.float32, torch.float64) or y_pred.numel() == 0:
+        raise ValueError(f"mrstft_loss: a non-empty real float32 / float64 (B, T, N) signal, got {tuple(y_pred.shape)} {y_pred.dtype}")
+    if tuple(y_true.shape) != tuple(y_pred.shape) or y_true.dtype != y_pred.dtype:
+        raise ValueError(f"mrstft_loss: prediction {tuple(y_pred.shape)} {y_pred.dtype} and target {tuple(y_true.shape)} "
+                         f"{y_true.dtype} differ")
+    if y_true.requires_grad:
+        raise ValueError("mrstft_loss: the target takes no gradient here (detach it, or use MultiResoSTFT's torch lines)")
+    res = _mrstft_resolutions(resolutions)
+    if res is None or not mrstft_supported(tuple(y_pred.shape), res, eps):
+        raise ValueError(f"mrstft_loss: resolutions {resolutions!r} on T = {y_pred.shape[1]}: 1 to {MRSTFT_MAX_RES} triples "
+                         f"(n_fft, hop, win) with n_fft a power of two from 256 to 2048, 1 <= win <= n_fft, hop >= 1, "
+                         f"n_fft / 2 < T <= 2^30, fewer than 2^31 frames in all, and eps >= 0")
+    try:
+        wts = tuple(float(v) for v in weights)
+    except (TypeError, ValueError):
+        wts = ()
+    if len(wts) != 3:
+        raise ValueError(f"mrstft_loss: weights must be three numbers (w_sc, w_log_mag, w_lin_mag), got {weights!r}")
+    return _MRSTFT.apply(y_pred, y_true, res, wts, float(eps))
+
+
 def mean_square(y: torch.Tensor) -> torch.Tensor:
     """(y ** 2).mean() of a real tensor in one streaming pass each way (forward: one read of y;
     backward: one read + one write), in whatever layout y is stored."""

@@ -181,6 +181,73 @@ class AveragePower(nn.Module):
         return window[:, None] * window[None, :]
 
 
+class MultiResoSTFT(nn.Module):
+    """Multi-resolution STFT criterion of (B, T, N) signals, the one examples/e8_fdn.py of the reference registers beside
+    ``sparsity_loss`` (there wrapped from the auraloss package, whose ``MultiResolutionSTFTLoss()`` defaults these are).
+    Every (batch, channel) column is one row.  For each resolution (n_fft, hop, win), with the periodic Hann window of ``win``
+    samples centred in the frame, reflect padding and M = sqrt(clamp(|X|^2, min=eps)) of the prediction (p) and the target (t):
+
+        sc  = |M_t - M_p|_F / |M_t|_F        (both norms over all rows, bins and frames at once)
+        log = mean |log M_p - log M_t|
+        lin = mean |M_p - M_t|
+
+    and the criterion is the mean over the resolutions of ``w_sc sc + w_log_mag log + w_lin_mag lin``.
+
+    Device float32 / float64 predictions against a gradient-free target of the same shape and dtype run on
+    ``ops.mrstft_loss`` (three launches forward, two backward for all resolutions, rows and both signals; the spectrograms
+    are never stored); host tensors, other dtypes, a target that takes a gradient and the parameter sets the kernels do not
+    take run the torch lines of ``_torch_forward`` and raise what ``torch.stft`` raises."""
+
+    def __init__(self, fft_sizes=(1024, 2048, 512), hop_sizes=(120, 240, 50), win_lengths=(600, 1200, 240), w_sc: float = 1.0,
+                 w_log_mag: float = 1.0, w_lin_mag: float = 0.0, eps: float = 1e-8, name: str = "MultiResoSTFT", device="cpu"):
+        super().__init__()
+        assert len(fft_sizes) == len(hop_sizes) == len(win_lengths) and len(fft_sizes) >= 1, \
+            "fft_sizes, hop_sizes and win_lengths must have the same, non-zero length"
+        self.fft_sizes = tuple(fft_sizes)
+        self.hop_sizes = tuple(hop_sizes)
+        self.win_lengths = tuple(win_lengths)
+        self.w_sc = w_sc
+        self.w_log_mag = w_log_mag
+        self.w_lin_mag = w_lin_mag
+        self.eps = eps
+        self.name = name
+        self.device = device
+
+    def resolutions(self):
+        return tuple(zip(self.fft_sizes, self.hop_sizes, self.win_lengths))
+
+    def _on_kernels(self, y_pred, y_true):
+        return (torch.is_tensor(y_pred) and torch.is_tensor(y_true) and y_pred.is_cuda and y_true.is_cuda
+                and y_pred.dtype in (torch.float32, torch.float64) and y_true.dtype == y_pred.dtype
+                and not y_true.requires_grad
+                and ops.mrstft_supported(tuple(y_pred.shape), self.resolutions(), self.eps))
+
+    def forward(self, y_pred, y_true):
+        if y_pred.dim() == 1:
+            y_pred, y_true = y_pred[None, :, None], y_true[None, :, None]
+        assert y_pred.shape == y_true.shape and y_true.dim() == 3, \
+            "y_pred and y_true must have the same shape (n_batch, n_samples, n_channels)"
+        if self._on_kernels(y_pred, y_true):
+            return ops.mrstft_loss(y_pred, y_true, self.resolutions(), (self.w_sc, self.w_log_mag, self.w_lin_mag), self.eps)
+        return self._torch_forward(y_pred, y_true)
+
+    def _torch_forward(self, y_pred, y_true):
+        """the definition in plain torch, on whatever device the tensors live"""
+        B, T, N = y_pred.shape
+        rows = [y.permute(0, 2, 1).reshape(B * N, T) for y in (y_pred, y_true)]
+        total = 0.0
+        for n_fft, hop, win in self.resolutions():
+            w = torch.hann_window(win, dtype=y_pred.dtype, device=y_pred.device)
+            Mp, Mt = (torch.sqrt(torch.clamp(X.real ** 2 + X.imag ** 2, min=self.eps))
+                      for X in (torch.stft(r, n_fft, hop, win, w, center=True, pad_mode="reflect", return_complex=True)
+                                for r in rows))
+            sc = torch.linalg.vector_norm(Mt - Mp) / torch.linalg.vector_norm(Mt)
+            log = torch.mean(torch.abs(torch.log(Mp) - torch.log(Mt)))
+            lin = torch.mean(torch.abs(Mp - Mt))
+            total = total + self.w_sc * sc + self.w_log_mag * log + self.w_lin_mag * lin
+        return total / len(self.fft_sizes)
+
+
 class masked_mse_loss(nn.Module):
     """Mean squared error over a random subset of the frequency bins, flamo/optimize/loss.py:106-167: the bins are shuffled and
     cut into sets of ``n_samples`` (``generate_partitions``), every call takes the next set, and when all are used the walk
