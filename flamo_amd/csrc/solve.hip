@@ -1002,7 +1002,9 @@ template <typename T, bool WS>
 __global__ void __launch_bounds__(256) solve_lds_kernel(const cx<T>* __restrict__ P, long p_pitch, int one_minus, int adjoint,
                                                         const cx<T>* __restrict__ R, long rs_b, long rs_n, long rs_k,
                                                         cx<T>* __restrict__ OUT, long os_b, long os_n, long os_k,
-                                                        int B, int M, int N, int K, int CB, cx<T>* __restrict__ ws) {
+                                                        int B, int M, int N, int K, int CB, cx<T>* __restrict__ ws,
+                                                        const cx<T>* __restrict__ l, long l_sn) {
+    // l: constant row scale of the materialised matrix (fl_solve_scaled_*: A = I - diag(l) P), N values l_sn apart; nullptr = none
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int NP = N + 1;
     cx<T>* Am = WS ? ws + (size_t)blockIdx.x * N * NP : reinterpret_cast<cx<T>*>(smem);             // [N][NP]
@@ -1014,7 +1016,9 @@ __global__ void __launch_bounds__(256) solve_lds_kernel(const cx<T>* __restrict_
   for (int f = blockIdx.x; f < M; f += gridDim.x) {
     for (int e = tid; e < N * N; e += 256) {
         const int i = e / N, j = e - i * N;
-        cx<T> v = adjoint ? conj(P[(size_t)(j * N + i) * p_pitch + f]) : P[(size_t)(i * N + j) * p_pitch + f];
+        cx<T> v = adjoint ? P[(size_t)(j * N + i) * p_pitch + f] : P[(size_t)(i * N + j) * p_pitch + f];
+        if (l) v = v * l[(long)(adjoint ? j : i) * l_sn];      // (uniform) the scale belongs to the row of P, ahead of I - .
+        if (adjoint) v = conj(v);
         if (one_minus) v = cx<T>((i == j ? (T)1 : (T)0) - v.x, -v.y);
         Am[i * NP + j] = v;
     }
@@ -1158,9 +1162,22 @@ static int solve_impl(const void* P, long p_pitch, const Dud<T>& dud, int one_mi
         }
     }
     FL_REQUIRE(B >= 0 && M >= 0 && N > 0 && K > 0 && (!P || p_pitch >= M), "solve: bad sizes (p_pitch >= M)");
+    // a materialised matrix takes the constant row scale l and no other factor of a Dud
+    FL_REQUIRE(!P || !(dud.l_sf || dud.U || dud.r || dud.l2 || dud.rhs_l2),
+               "solve: a materialised matrix takes a constant row scale and no other diagonal factor");
     const int nmax_lim = sizeof(T) == 8 ? 32 : 64;
     if (N > nmax_lim) {
         const int big = solve_lds_max_n<T>();
+        // beyond the register-resident kernels: what the path about to be taken cannot honour is refused, never dropped
+        if (dud.lu_out || dud.piv_out || dud.wadj) {
+            set_error("solve: N=%d: factors are kept by the register-resident kernels only (N <= %d for this precision)", N, nmax_lim);
+            return FL_ERR_UNSUPPORTED;
+        }
+        if (P && dud.l && N > big && !ws) {
+            set_error("solve_scaled: N=%d exceeds fl_solve_max_n (%d for this precision): the row-scaled loop has no workspace form", N,
+                      big);
+            return FL_ERR_UNSUPPORTED;
+        }
         if (P && N > big && N <= kSolveWsMaxN && ws) {
             if (B == 0 || M == 0) return FL_OK;
             const int slots = solve_ws_slots<T>(N, M);
@@ -1175,7 +1192,8 @@ static int solve_impl(const void* P, long p_pitch, const Dud<T>& dud, int one_mi
                 if (rc) return rc;
             }
             hipLaunchKernelGGL((solve_lds_kernel<T, true>), dim3(slots), dim3(256), lds, (hipStream_t)stream, (const cx<T>*)P, p_pitch, one_minus,
-                               adjoint, (const cx<T>*)R, rs_b, rs_n, rs_k, (cx<T>*)OUT, os_b, os_n, os_k, B, M, N, K, cb, (cx<T>*)ws);
+                               adjoint, (const cx<T>*)R, rs_b, rs_n, rs_k, (cx<T>*)OUT, os_b, os_n, os_k, B, M, N, K, cb, (cx<T>*)ws,
+                               dud.l, dud.l_sn);
             FL_CHECK_LAUNCH("solve_ws");
             return FL_OK;
         }
@@ -1195,7 +1213,8 @@ static int solve_impl(const void* P, long p_pitch, const Dud<T>& dud, int one_mi
         const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(solve_lds_kernel<T, false>), lds, true, done, "solve");
         if (rc) return rc;
         hipLaunchKernelGGL((solve_lds_kernel<T, false>), dim3(M), dim3(256), lds, (hipStream_t)stream, (const cx<T>*)P, p_pitch, one_minus, adjoint,
-                           (const cx<T>*)R, rs_b, rs_n, rs_k, (cx<T>*)OUT, os_b, os_n, os_k, B, M, N, K, cb, (cx<T>*)nullptr);
+                           (const cx<T>*)R, rs_b, rs_n, rs_k, (cx<T>*)OUT, os_b, os_n, os_k, B, M, N, K, cb, (cx<T>*)nullptr, dud.l,
+                           dud.l_sn);
         FL_CHECK_LAUNCH("solve_lds");
         return FL_OK;
     }

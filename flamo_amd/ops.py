@@ -1846,7 +1846,9 @@ class _SolveScaledLoop(torch.autograd.Function):
 def solve_scaled_loop(g: torch.Tensor, D: torch.Tensor, U: torch.Tensor, R: torch.Tensor) -> torch.Tensor:
     """Per bin f: (I - diag(g) D[f] U)^-1 R[:, f] -- a loop whose feedforward path is a per-bin matrix of delays followed
     by per-channel gains, around a constant mixing matrix (system.py:417-424 with fF = Series(Delay((N,N)), parallelGain(N)),
-    fB = Matrix: the active-acoustics structure, e8_active_acoustics.py).  D must not require a gradient."""
+    fB = Matrix: the active-acoustics structure, e8_active_acoustics.py).  D must not require a gradient.
+    N up to fl_solve_max_n (138 in complex64, 97 in complex128: fl_solve_scaled_* has no workspace form); a larger loop raises
+    -- materialise diag(g) D U and call ops.solve."""
     if D.requires_grad:
         raise ValueError("solve_scaled_loop: the per-bin factor must not require a gradient (use ops.solve)")
     cd = R.dtype

@@ -567,7 +567,9 @@ int fl_solve_ws_c128(const void* P, long p_pitch, int one_minus, int adjoint,
 /* fl_solve_* (one_minus) with a constant row scale of the materialised matrix: A_f = I - diag(l) P[f], l: N complex values
  * l_sn apart.  For loops whose feedforward path ends in per-channel gains (Series(Delay((N,N)), parallelGain(N)) around a
  * mixing matrix, the active-acoustics structure): P = D[f] U is formed once and the gains never make a pass over the
- * (M, N, N) tensor, forward or backward. */
+ * (M, N, N) tensor, forward or backward.  Sizes: 1 <= N <= fl_solve_max_n(f64) (138 / 97) -- the register-resident kernels
+ * and, above 64 (c64) / 32 (c128), the LDS kernel, which applies l where it loads the matrix.  There is no workspace form:
+ * a larger N is FL_ERR_UNSUPPORTED (form diag(l) P and call fl_solve_ws_*). */
 int fl_solve_scaled_c64(const void* P, long p_pitch, const void* l, long l_sn, int adjoint, const void* R, long rs_b, long rs_n,
                         long rs_k, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, int K, void* stream);
 int fl_solve_scaled_c128(const void* P, long p_pitch, const void* l, long l_sn, int adjoint, const void* R, long rs_b, long rs_n,
