@@ -4,15 +4,14 @@
 //   S[k][f] = |X[k][f]|,  X[.][f] = the length-1024 transform of the windowed frame f of the reflect-padded signal (hop 256)
 //   P[i][j] = sum_{a, b < 64} h[a] h[b] S[si i + a][sj j + b]          loss = |P2 - P1|_F / |P1|_F / |P2|_F
 //
-// The framed transform is one wavefront per frame: the 1024 real samples are 512 complex ones, 8 per lane, transformed by three
-// in-register radix-8 passes (regfft.h) with two exchanges through LDS, and split into the 513 bins of the real transform.  The
+// The framed transform is one wavefront per frame, the n_fft = 1024, hop = 256, full-window instance of framed.h in the
+// signal's precision: 512 complex values, 8 per lane, split into the 513 bins of the real transform.  The
 // spectrogram never reaches memory: the frame's magnitudes stay in LDS and are smoothed along frequency there, so that a frame
 // leaves I doubles (Q[f][i]); the combine smooths along the frames.  The backward pass rebuilds dL/dQ and dL/dS of a frame from
 // the kept P1, P2 and the three sums of squares, recomputes the frame's transform (cheaper than keeping 513 x F complex values),
 // runs the adjoint of the split and the inverse transform, and an overlap-add gathers the frames' gradients per sample.
 // Every sum has a fixed order; everything behind the magnitudes is a double in both precisions.
-#include "common.h"
-#include "regfft.h"
+#include "framed.h"
 #include "../../include/flamo_hip_avgpow.h"
 
 namespace fl {
@@ -20,7 +19,8 @@ namespace avgpow {
 
 constexpr int NFFT = 1024, HOP = 256, NB = NFFT / 2 + 1, HALF = NFFT / 2, WIN = 64;
 constexpr long T_MIN = (long)HOP * (WIN - 1), T_MAX = 1L << 30;      // J >= 1 needs F = 1 + T / 256 >= 64
-constexpr int ZLDS = HALF + HALF / 8;                                // 512 complex values, one pad per 8
+constexpr int PL = HALF / 64, ZLDS = HALF + 64;                      // framed.h: complex values per lane, its LDS array
+constexpr framed::Frame FRAME{HOP, NFFT, 0};                         // the window covers the whole frame
 constexpr int IMAX = NB - WIN + 1;                                   // rows of P at si = 1
 
 struct Plan {
@@ -40,83 +40,6 @@ static bool make_plan(long T, int si, int sj, Plan& p) {
     return true;
 }
 
-__device__ inline int zpad(int i) { return i + (i >> 3); }
-
-// sample j of the signal reflect-padded by HALF on each side (j counted from the first padded sample)
-template <typename T>
-__device__ inline T padded(const T* __restrict__ y, long stride, long Tn, long j) {
-    long t = j - HALF;
-    if (t < 0) t = -t;
-    if (t >= Tn) t = 2 * (Tn - 1) - t;
-    return y[t * stride];
-}
-
-// Z[k] = sum_n z[n] exp(-+2 pi i k n / 512) by one wavefront.  In: v[r] = z[lane + 64 r].  Out: A[zpad(k)] = Z[k], visible to
-// every lane.  n = 64 n1 + n2 and k = k1 + 8 (j1 + 8 j2): a radix-8 pass over n1, the twiddle W512^(n2 k1), and a 64-point
-// transform over n2 = 8 m1 + m2 per k1 (a pass over m1, W64^(m2 j1), a pass over m2).  tw[j] = exp(-2 pi i j / 1024).
-template <typename T, bool INV>
-__device__ inline void fft512(cx<T> (&v)[8], cx<T>* A, const cx<T>* __restrict__ tw, int lane) {
-    RegFFT<T, 8, INV>::run(v);
-#pragma unroll
-    for (int k1 = 0; k1 < 8; ++k1) {
-        if (k1 > 0) {
-            const cx<T> t = tw[2 * lane * k1];
-            v[k1] = mul_plain(v[k1], INV ? conj(t) : t);
-        }
-        A[zpad(k1 * 64 + lane)] = v[k1];
-    }
-    __syncthreads();
-    const int hi = lane >> 3, lo = lane & 7;          // (k1, m2), then (k1, j1)
-#pragma unroll
-    for (int m1 = 0; m1 < 8; ++m1) v[m1] = A[zpad(hi * 64 + 8 * m1 + lo)];
-    RegFFT<T, 8, INV>::run(v);
-#pragma unroll
-    for (int j1 = 1; j1 < 8; ++j1) {
-        const cx<T> t = tw[16 * lo * j1];
-        v[j1] = mul_plain(v[j1], INV ? conj(t) : t);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j1 = 0; j1 < 8; ++j1) A[zpad(hi * 64 + j1 * 8 + lo)] = v[j1];
-    __syncthreads();
-#pragma unroll
-    for (int m2 = 0; m2 < 8; ++m2) v[m2] = A[zpad(hi * 64 + lo * 8 + m2)];
-    RegFFT<T, 8, INV>::run(v);
-    __syncthreads();
-#pragma unroll
-    for (int j2 = 0; j2 < 8; ++j2) A[zpad(hi + 8 * lo + 64 * j2)] = v[j2];
-    __syncthreads();
-}
-
-// the windowed frame f as 512 complex values (even samples real, odd samples imaginary), transformed into A
-template <typename T>
-__device__ inline void frame_transform(const T* __restrict__ y, long stride, long Tn, long f, const T* __restrict__ w,
-                                       const cx<T>* __restrict__ tw, cx<T>* A, int lane) {
-    const cx<T>* w2 = reinterpret_cast<const cx<T>*>(w);
-    cx<T> v[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const int n = lane + 64 * r;
-        const long j = f * HOP + 2 * n;
-        const cx<T> ww = w2[n];
-        v[r] = cx<T>(padded(y, stride, Tn, j) * ww.x, padded(y, stride, Tn, j + 1) * ww.y);
-    }
-    fft512<T, false>(v, A, tw, lane);
-}
-
-// bin k (0 .. 512) of the real transform from the packed one: X[k] = E[k] + W1024^k O[k],
-// E = (Z[k] + conj Z[512 - k]) / 2, O = -i (Z[k] - conj Z[512 - k]) / 2
-template <typename T>
-__device__ inline cx<T> split_bin(const cx<T>* A, const cx<T>* __restrict__ tw, int k) {
-    if (k == HALF) {
-        const cx<T> z = A[0];
-        return cx<T>(z.x - z.y, (T)0);
-    }
-    const cx<T> a = A[zpad(k)], b = conj(A[zpad((HALF - k) & (HALF - 1))]);
-    const cx<T> e = (T)0.5 * (a + b), o = (T)0.5 * mul_mi(a - b);
-    return e + mul_plain(o, tw[k]);
-}
-
 // ---------------------------------------------------------------- forward: a frame's magnitudes, smoothed along frequency
 template <typename T>
 __global__ void __launch_bounds__(64) avgpow_frames_kernel(const T* __restrict__ yp, long sp, const T* __restrict__ yt, long st,
@@ -129,9 +52,9 @@ __global__ void __launch_bounds__(64) avgpow_frames_kernel(const T* __restrict__
     const int sig = blockIdx.x >= p.F ? 1 : 0;
     const long f = blockIdx.x - (sig ? p.F : 0);
     hd[lane] = (double)h[lane];
-    frame_transform<T>(sig ? yt : yp, sig ? st : sp, p.T, f, w, tw, A, lane);
+    [[clang::always_inline]] framed::frame_transform<T, T, PL, NFFT>(sig ? yt : yp, sig ? st : sp, p.T, f, FRAME, w, tw, A, lane);
     for (int k = lane; k < NB; k += 64) {
-        const cx<T> x = split_bin<T>(A, tw, k);
+        const cx<T> x = framed::split_bin<T, PL, NFFT>(A, tw, k);
         S[k] = hypot(x.x, x.y);
     }
     __syncthreads();
@@ -142,12 +65,6 @@ __global__ void __launch_bounds__(64) avgpow_frames_kernel(const T* __restrict__
         for (int a = 0; a < WIN; ++a) acc += hd[a] * (double)S[p.si * i + a];
         q[i] = acc;
     }
-}
-
-__device__ inline double wave_sum(double a) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) a += __shfl_xor(a, off, 64);
-    return a;
 }
 
 // ---------------------------------------------------------------- combine: smoothing along the frames, partial sums of squares
@@ -216,7 +133,7 @@ __global__ void __launch_bounds__(64) avgpow_final_kernel(const double* __restri
 template <typename T>
 __global__ void __launch_bounds__(64) avgpow_frames_bwd_kernel(const T* __restrict__ yp, long sp, Plan p, const T* __restrict__ w,
                                                                const T* __restrict__ h, const cx<T>* __restrict__ tw,
-                                                               const double* __restrict__ keep, cx<T>* __restrict__ gframes) {
+                                                               const double* __restrict__ keep, T* __restrict__ gframes) {
     __shared__ cx<T> A[ZLDS];
     __shared__ cx<T> Y[NB + 7];
     __shared__ double gQ[IMAX + 6];
@@ -242,41 +159,25 @@ __global__ void __launch_bounds__(64) avgpow_frames_bwd_kernel(const T* __restri
         }
         gQ[i] = acc;
     }
-    frame_transform<T>(yp, sp, p.T, f, w, tw, A, lane);      // (its barriers publish gQ)
-    // dL/dS[k] = sum_i h[k - si i] dL/dQ[i]; G = dL/dS X / |X|; the Hermitian spectrum whose inverse transform is
-    // Re sum_{k <= 512} G[k] exp(+2 pi i k n / 1024): G / 2 inside, Re G at the two ends
+    [[clang::always_inline]] framed::frame_transform<T, T, PL, NFFT>(yp, sp, p.T, f, FRAME, w, tw, A, lane);      // (its barriers publish gQ)
+    // dL/dS[k] = sum_i h[k - si i] dL/dQ[i]; G = dL/dS X / |X|, halved into the Hermitian spectrum of the inverse transform
     for (int k = lane; k < NB; k += 64) {
-        const cx<T> x = split_bin<T>(A, tw, k);
+        const cx<T> x = framed::split_bin<T, PL, NFFT>(A, tw, k);
         const T mag = hypot(x.x, x.y);
         const int ilo = k >= WIN ? (k - (WIN - 1) + p.si - 1) / p.si : 0;
         const int ihi = min(p.I - 1, k / p.si);
         double gs = 0.0;
         for (int i = ilo; i <= ihi; ++i) gs += hd[k - p.si * i] * gQ[i];
         cx<T> g((T)0, (T)0);
-        if (mag > (T)0) {
-            const T s = (T)(gs / (double)mag);
-            g = (k == 0 || k == HALF) ? cx<T>(s * x.x, (T)0) : cx<T>((T)0.5 * s * x.x, (T)0.5 * s * x.y);
-        }
+        if (mag > (T)0) g = framed::hermitian_half<T, PL>((T)(gs / (double)mag), x, k);
         Y[k] = g;
     }
     __syncthreads();
-    // v[m] = y[2 m] + i y[2 m + 1] = sum_{k < 512} ((Y[k] + conj Y[512 - k]) + i conj(W1024^k) (Y[k] - conj Y[512 - k])) exp(+2 pi i k m / 512)
-    cx<T> v[8];
+    cx<T> v[PL];
 #pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const int k = lane + 64 * r;
-        const cx<T> a = Y[k], b = conj(Y[HALF - k]);
-        v[r] = (a + b) + mul_i(mul_plain(a - b, conj(tw[k])));
-    }
-    fft512<T, true>(v, A, tw, lane);
-    const cx<T>* w2 = reinterpret_cast<const cx<T>*>(w);
-    cx<T>* out = gframes + f * HALF;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const int m = lane + 64 * r;
-        const cx<T> z = A[zpad(m)], ww = w2[m];
-        out[m] = cx<T>(z.x * ww.x, z.y * ww.y);
-    }
+    for (int r = 0; r < PL; ++r) v[r] = framed::unsplit<T, PL, NFFT>(Y, tw, lane + 64 * r);
+    framed::fft_wave<T, PL, NFFT, true>(v, A, tw, lane);
+    framed::store_frame_grad<T, T, PL>(A, w, FRAME, gframes + f * NFFT, lane);
 }
 
 // ---------------------------------------------------------------- overlap-add: a gather per sample, in a fixed order
@@ -285,21 +186,11 @@ __global__ void __launch_bounds__(256) avgpow_ola_kernel(const T* __restrict__ g
                                                         T* __restrict__ gy) {
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     if (t >= p.T) return;
+    // (the gather looks into the right margin for every t <= T - 2; before t = T - 513 the image lies beyond frame `last`
+    // and nothing is added)
     double acc = 0.0;
-    int cnt = 0;
-    // the frames f <= last that hold the padded sample j, first to last
-    auto gather = [&](long j) {
-        const long f0 = j >= NFFT ? (j - (NFFT - 1) + HOP - 1) / HOP : 0;
-        const long f1 = min(p.last, j / HOP);
-        for (long f = f0; f <= f1; ++f) {
-            acc += (double)gframes[f * NFFT + (j - f * HOP)];
-            ++cnt;
-        }
-    };
-    gather(t + HALF);                                                         // the sample itself
-    if (t >= 1 && t <= HALF) gather(HALF - t);                                // its image in the left margin
-    if (t >= p.T - HALF - 1 && t <= p.T - 2) gather(2 * (p.T - 1) - t + HALF);   // ... in the right margin
-    gy[t] = cnt ? (T)((double)gloss[0] * acc) : (T)0;
+    const bool any = framed::gather_sample(gframes, t, p.T, HALF, FRAME, p.last, acc);
+    gy[t] = any ? (T)((double)gloss[0] * acc) : (T)0;
 }
 
 }  // namespace avgpow
@@ -356,7 +247,7 @@ FL_ENTRY_F32_F64(fl_avgpow_bwd, (const void* yp, long sp, long Tn, int si, int s
     FL_REQUIRE((uintptr_t)w % (2 * sizeof(T)) == 0 && (uintptr_t)gframes % (2 * sizeof(T)) == 0,
                "avgpow_bwd: the window and the frame gradients must be aligned to two of their elements");
     hipLaunchKernelGGL((avgpow_frames_bwd_kernel<T>), dim3((unsigned)(p.last + 1)), dim3(64), 0, (hipStream_t)stream, (const T*)yp, sp, p,
-                       (const T*)w, (const T*)h, (const cx<T>*)tw, (const double*)keep, (cx<T>*)gframes);
+                       (const T*)w, (const T*)h, (const cx<T>*)tw, (const double*)keep, (T*)gframes);
     FL_CHECK_LAUNCH("avgpow_frames_bwd");
     hipLaunchKernelGGL((avgpow_ola_kernel<T>), dim3((unsigned)((Tn + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const T*)gframes, p,
                        (const T*)gloss, (T*)gy);

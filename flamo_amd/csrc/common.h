@@ -184,6 +184,13 @@ template <typename T> __host__ __device__ inline cx<T> cdiv(cx<T> a, cx<T> b) {
     }
 }
 
+// the sum of v over the 64 lanes, in every lane (a butterfly: the same order, so the same bits, in all of them)
+template <typename T> __device__ inline T wave_sum(T v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
 // Wavefront reduce-scatter of N per-lane values: after the call the lane holds in a[0..cnt) the
 // wavefront totals of the original entries off .. off+cnt-1.  Each halving step trades half of the
 // lane's values with its partner (N/2 shuffles instead of N); when the count turns odd the rest is

@@ -156,11 +156,6 @@ __device__ inline void store_block(const T* lds, T* base, const Shape& s, long t
     }
 }
 
-__device__ inline double wave_sum(double a) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) a += __shfl_xor(a, off, 64);
-    return a;
-}
 // sum of a[lo .. hi) over the wavefront, the same order whoever asks
 __device__ inline double wave_sum_range(const double* __restrict__ a, int lo, int hi, int lane) {
     double s = 0.0;

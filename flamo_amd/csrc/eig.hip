@@ -36,11 +36,6 @@ template <typename T> __device__ inline cx<T> csqrt_(cx<T> a) {
     }
     return cx<T>(re, im);
 }
-template <typename T> __device__ inline T wave_sum(T v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 template <typename T> struct Eps;
 template <> struct Eps<float> { static constexpr float v = 1.1920929e-07f; static constexpr float tiny = 1e-30f; };
 template <> struct Eps<double> { static constexpr double v = 2.220446049250313e-16; static constexpr double tiny = 1e-290; };

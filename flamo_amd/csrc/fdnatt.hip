@@ -30,12 +30,6 @@ __device__ inline void store_param(void* p, int f32, int i, double v) {
 // linear gain of a line of d samples under the slope s dB per sample: the reference forms s * d, then 10^(./20)
 __device__ inline double line_gain(double slope, double d) { return pow(10.0, slope * d / 20.0); }
 
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // dL/d(b, a) of section idx (of st per tap) from nblk blocks blk_stride elements apart, added in block order
 __device__ inline void sum_blocks(const double* __restrict__ gb, const double* __restrict__ ga, long blk_stride, int nblk, int idx,
                                   int st, double* B, double* A) {

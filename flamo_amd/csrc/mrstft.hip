@@ -11,35 +11,24 @@
 // signals together, whatever the number of resolutions: the frame kernels' grid is the list of all (resolution, row, frame)
 // triples, and the frame length is uniform per workgroup.
 //
-// Frames.  One wavefront per frame, as in avgpow.hip: the n_fft real samples are Nc = n_fft / 2 complex ones, P = Nc / 64 per
-// lane (2, 4, 8, 16 for n_fft = 256 .. 2048).  The window is applied while loading and only the samples under its support
-// [lpad, lpad + win) are read.  The packed transform is a Stockham walk of three passes, radix P x 8 x 8, every pass an
-// in-register transform of regfft.h: the first straight on the loaded values (lane j holds z[j + 64 r]), the two radix-8
-// passes on 8 P butterflies (P / 8 per lane; with P < 8 the lanes from 8 P on idle), with an exchange through LDS behind each.
-// The Nc + 1 bins of the real transform are split from the packed one bin by bin.  The spectrograms never reach memory: a
-// frame leaves four doubles (sum (M_t - M_p)^2, sum M_t^2, sum |log M_p - log M_t|, sum |M_p - M_t|), the combine adds them
-// per resolution in a fixed order (no atomics: two runs give the same bits), the final kernel forms the loss and the three
-// factors of dL/dM_p the backward pass needs.  The backward frame kernel recomputes both transforms, forms
-// dL/dX = dL/dM_p X / M_p (zero where |X|^2 <= eps), runs the adjoint of the split and the inverse walk, and writes the win
-// samples under the window; the overlap-add gathers per sample, resolution by resolution and frame by frame, with the
-// reflected margins folded back onto the interior samples they mirror.
+// Frames.  One wavefront per frame on the framed real transform of framed.h (the packed Stockham walk, its LDS padding and
+// register budget, the split into bins and its adjoint are described there), P = n_fft / 128 = 2, 4, 8, 16 complex values per
+// lane.  The spectrograms never reach memory: a frame leaves four doubles (sum (M_t - M_p)^2, sum M_t^2,
+// sum |log M_p - log M_t|, sum |M_p - M_t|), the combine adds them per resolution in a fixed order (no atomics: two runs give
+// the same bits), the final kernel forms the loss and the three factors of dL/dM_p the backward pass needs.  The backward
+// frame kernel recomputes both transforms, forms dL/dX = dL/dM_p X / M_p (zero where |X|^2 <= eps), runs the adjoint of the
+// split and the inverse walk, and writes the win samples under the window; the overlap-add gathers per sample, resolution by
+// resolution and frame by frame, with the reflected margins folded back onto the interior samples they mirror.
 //
 // Precision.  The signals, the frame gradients and the gradient have the signals' type; everything between is a double in
 // float32 too (see `C` below), so the two precisions run the same kernels and differ in their loads and stores.
 //
-// LDS.  A[Nc + 64] complex doubles, index i stored at i + (i >> log2 P): one pad per P values, so that the first pass's stores
-// (lane j writes j P + t: a stride of P + 1 values = 4 (P + 1) dwords, whose gcd with the 64 banks is 4 = the width of one
-// value) and the radix-8 passes' loads (consecutive j) both spread over all banks.  Sized for n_fft = 2048: 1088 values, 17 KB.
-// Beside it the forward kernel keeps the prediction's clamped |X|^2 (1025 doubles, 8 KB) and the backward kernel the
-// prediction's bins, then dL/dX (1025 complex doubles, 16 KB): 25 KB forward and 33 KB backward per wavefront, six and four
-// wavefronts per CU of its 160 KB.
-//
-// Registers, 16 per lane (n_fft = 2048): the 16 complex doubles of a pass are 64 VGPRs; a radix-16 transform of regfft.h holds
-// its input, the intermediate products and four-value temporaries at once, and the compiler reports 170 VGPRs for the forward
-// and 200 for the backward kernel, no scratch: under the 256 of two wavefronts per SIMD, and at four to six wavefronts per CU
-// it is LDS, not registers, that bounds the occupancy.
-#include "common.h"
-#include "regfft.h"
+// LDS.  The walk's A[Nc + 64] complex doubles, sized for n_fft = 2048: 1088 values, 17 KB.  Beside it the forward kernel keeps
+// the prediction's clamped |X|^2 (1025 doubles, 8 KB) and the backward kernel the prediction's bins, then dL/dX (1025 complex
+// doubles, 16 KB): 25 KB forward and 33 KB backward per wavefront, six and four wavefronts per CU of its 160 KB.  The
+// compiler reports 170 VGPRs for the forward and 200 for the backward kernel, no scratch: at four to six wavefronts per CU it
+// is LDS, not registers, that bounds the occupancy.
+#include "framed.h"
 #include "../../include/flamo_hip_mrstft.h"
 
 namespace fl {
@@ -55,8 +44,8 @@ constexpr int NC_MAX = NFFT_MAX / 2, ALDS = NC_MAX + 64, NB_MAX = NC_MAX + 1;
 constexpr long T_MAX = 1L << 30, BLOCKS_MAX = (1L << 31) - 1, SAMPLES_MAX = 1L << 38;
 constexpr int KEEP_STRIDE = 8, KEEP_LOSS = KEEP_STRIDE * MAXR, KEEP_DOUBLES = KEEP_LOSS + 1;
 
-struct Res {
-    int nfft, hop, win, lpad;
+struct Res : framed::Frame {
+    int nfft;
     long F;        // frames per row
     long blk0;     // first workgroup of the frame kernels
     long g0;       // first element in gframes
@@ -93,109 +82,6 @@ static bool make_plan(long B, long T, long N, int R, const int* res, Plan& p) {
     return true;
 }
 
-template <int P> struct Log2;
-template <> struct Log2<2> { static constexpr int v = 1; };
-template <> struct Log2<4> { static constexpr int v = 2; };
-template <> struct Log2<8> { static constexpr int v = 3; };
-template <> struct Log2<16> { static constexpr int v = 4; };
-
-template <int P>
-__device__ inline int zp(int i) { return i + (i >> Log2<P>::v); }
-
-__device__ inline double wave_sum(double a) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) a += __shfl_xor(a, off, 64);
-    return a;
-}
-
-// One radix-8 Stockham pass over the 64 P values in A, NS = the product of the radices before it: butterfly j reads
-// A[j + t 8 P], t < 8, multiplies by W_{8 NS}^(t (j mod NS)) and writes A[(j / NS) 8 NS + (j mod NS) + t NS].
-template <int P, int NS, bool INV>
-__device__ inline void pass8(cx<C>* A, const cx<C>* __restrict__ tw, int lane) {
-    constexpr int NBF = 8 * P, NI = P >= 8 ? P / 8 : 1, STEP = NTW / (8 * NS);
-    cx<C> u[NI][8];
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        const int j = lane + 64 * i;
-        if (j < NBF) {
-            const int jm = j & (NS - 1);
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                u[i][t] = A[zp<P>(j + t * NBF)];
-                if (t > 0) {
-                    const cx<C> w = tw[t * jm * STEP];
-                    u[i][t] = mul_plain(u[i][t], INV ? conj(w) : w);
-                }
-            }
-            RegFFT<C, 8, INV>::run(u[i]);
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        const int j = lane + 64 * i;
-        if (j < NBF) {
-            const int jm = j & (NS - 1), base = (j - jm) * 8 + jm;
-#pragma unroll
-            for (int t = 0; t < 8; ++t) A[zp<P>(base + t * NS)] = u[i][t];
-        }
-    }
-    __syncthreads();
-}
-
-// Z[k] = sum_n z[n] exp(-+2 pi i k n / (64 P)) by one wavefront.  In: v[r] = z[lane + 64 r].  Out: A[zp(k)] = Z[k], visible
-// to every lane.  tw[j] = exp(-2 pi i j / 2048).
-template <int P, bool INV>
-__device__ inline void fft_wave(cx<C> (&v)[P], cx<C>* A, const cx<C>* __restrict__ tw, int lane) {
-    RegFFT<C, P, INV>::run(v);
-#pragma unroll
-    for (int t = 0; t < P; ++t) A[zp<P>(lane * P + t)] = v[t];
-    __syncthreads();
-    pass8<P, P, INV>(A, tw, lane);
-    pass8<P, 8 * P, INV>(A, tw, lane);
-}
-
-// sample j of the row reflect-padded by `half` on each side (j counted from the first padded sample); T > half
-template <typename T>
-__device__ inline T padded(const T* __restrict__ y, long stride, long Tn, long j, int half) {
-    long t = j - half;
-    if (t < 0) t = -t;
-    if (t >= Tn) t = 2 * (Tn - 1) - t;
-    return y[t * stride];
-}
-
-// the windowed frame f as 64 P complex values (even samples real, odd samples imaginary), transformed into A; only the
-// samples under the window are read
-template <typename T, int P>
-__device__ inline void frame_transform(const T* __restrict__ y, long stride, long Tn, long f, const Res& q, const C* __restrict__ w,
-                                       const cx<C>* __restrict__ tw, cx<C>* A, int lane) {
-    cx<C> v[P];
-    const long j0 = f * q.hop;
-#pragma unroll
-    for (int r = 0; r < P; ++r) {
-        const int n = 2 * (lane + 64 * r) - q.lpad;      // place under the window of the even sample
-        C re = 0.0, im = 0.0;
-        if (n >= 0 && n < q.win) re = (C)padded(y, stride, Tn, j0 + n + q.lpad, 64 * P) * w[n];
-        if (n + 1 >= 0 && n + 1 < q.win) im = (C)padded(y, stride, Tn, j0 + n + 1 + q.lpad, 64 * P) * w[n + 1];
-        v[r] = cx<C>(re, im);
-    }
-    fft_wave<P, false>(v, A, tw, lane);
-}
-
-// bin k (0 .. Nc) of the real transform from the packed one: X[k] = E[k] + W_{2 Nc}^k O[k],
-// E = (Z[k] + conj Z[Nc - k]) / 2, O = -i (Z[k] - conj Z[Nc - k]) / 2
-template <int P>
-__device__ inline cx<C> split_bin(const cx<C>* A, const cx<C>* __restrict__ tw, int k) {
-    constexpr int NC = 64 * P;
-    if (k == NC) {
-        const cx<C> z = A[0];
-        return cx<C>(z.x - z.y, 0.0);
-    }
-    const cx<C> a = A[zp<P>(k)], b = conj(A[zp<P>((NC - k) & (NC - 1))]);
-    const cx<C> e = 0.5 * (a + b), o = 0.5 * mul_mi(a - b);
-    return e + mul_plain(o, tw[k * (NTW / (2 * NC))]);
-}
-
 __device__ inline double power(cx<C> x) { return x.x * x.x + x.y * x.y; }
 
 // (resolution, row, frame) of a workgroup
@@ -218,13 +104,13 @@ __device__ inline void frame_sums(const T* __restrict__ yp, long sp, const T* __
                                   const C* __restrict__ w, const cx<C>* __restrict__ tw, double eps, cx<C>* A, double* Sp,
                                   double* __restrict__ out, int lane) {
     constexpr int NC = 64 * P;
-    frame_transform<T, P>(yp, sp, Tn, f, q, w, tw, A, lane);
-    for (int k = lane; k <= NC; k += 64) Sp[k] = fmax(power(split_bin<P>(A, tw, k)), eps);
+    framed::frame_transform<T, C, P, NTW>(yp, sp, Tn, f, q, w, tw, A, lane);
+    for (int k = lane; k <= NC; k += 64) Sp[k] = fmax(power(framed::split_bin<C, P, NTW>(A, tw, k)), eps);
     __syncthreads();
-    frame_transform<T, P>(yt, st, Tn, f, q, w, tw, A, lane);
+    framed::frame_transform<T, C, P, NTW>(yt, st, Tn, f, q, w, tw, A, lane);
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
     for (int k = lane; k <= NC; k += 64) {
-        const double pt = fmax(power(split_bin<P>(A, tw, k)), eps), pp = Sp[k];
+        const double pt = fmax(power(framed::split_bin<C, P, NTW>(A, tw, k)), eps), pp = Sp[k];
         const double mp = sqrt(pp), mt = sqrt(pt), d = mt - mp;
         s0 += d * d;
         s1 += mt * mt;
@@ -316,42 +202,30 @@ __device__ inline void frame_grad(const T* __restrict__ yp, long sp, const T* __
                                   cx<C>* A, cx<C>* Y, T* __restrict__ out, int lane) {
     constexpr int NC = 64 * P;
     const double c0 = coef[4], c1 = coef[5], c2 = coef[6];
-    frame_transform<T, P>(yp, sp, Tn, f, q, w, tw, A, lane);
-    for (int k = lane; k <= NC; k += 64) Y[k] = split_bin<P>(A, tw, k);
+    framed::frame_transform<T, C, P, NTW>(yp, sp, Tn, f, q, w, tw, A, lane);
+    for (int k = lane; k <= NC; k += 64) Y[k] = framed::split_bin<C, P, NTW>(A, tw, k);
     __syncthreads();
-    frame_transform<T, P>(yt, st, Tn, f, q, w, tw, A, lane);
-    // G = dL/dM_p X / M_p; the Hermitian spectrum whose inverse transform is Re sum_{k <= Nc} G[k] exp(+2 pi i k n / n_fft):
-    // G / 2 inside, Re G at the two ends
+    framed::frame_transform<T, C, P, NTW>(yt, st, Tn, f, q, w, tw, A, lane);
+    // G = dL/dM_p X / M_p, halved into the Hermitian spectrum of the inverse transform
     for (int k = lane; k <= NC; k += 64) {
         const cx<C> x = Y[k];
         const double pp = power(x);
         cx<C> g(0.0, 0.0);
         if (pp > eps) {
-            const double pt = fmax(power(split_bin<P>(A, tw, k)), eps);
+            const double pt = fmax(power(framed::split_bin<C, P, NTW>(A, tw, k)), eps);
             const double mp = sqrt(pp), mt = sqrt(pt);
             const double sg = pp > pt ? 1.0 : (pp < pt ? -1.0 : 0.0);
             const double s = (c0 * (mp - mt) + c1 * sg / mp + c2 * sg) / mp;
-            g = (k == 0 || k == NC) ? cx<C>(s * x.x, 0.0) : cx<C>(0.5 * s * x.x, 0.5 * s * x.y);
+            g = framed::hermitian_half<C, P>(s, x, k);
         }
         Y[k] = g;
     }
     __syncthreads();
-    // v[m] = y[2 m] + i y[2 m + 1] = sum_{k < Nc} ((Y[k] + conj Y[Nc - k]) + i conj(W^k) (Y[k] - conj Y[Nc - k])) exp(+2 pi i k m / Nc)
     cx<C> v[P];
 #pragma unroll
-    for (int r = 0; r < P; ++r) {
-        const int k = lane + 64 * r;
-        const cx<C> a = Y[k], b = conj(Y[NC - k]);
-        v[r] = (a + b) + mul_i(mul_plain(a - b, conj(tw[k * (NTW / (2 * NC))])));
-    }
-    fft_wave<P, true>(v, A, tw, lane);
-#pragma unroll
-    for (int r = 0; r < P; ++r) {
-        const int m = lane + 64 * r, n = 2 * m - q.lpad;
-        const cx<C> z = A[zp<P>(m)];
-        if (n >= 0 && n < q.win) out[n] = (T)(z.x * w[n]);
-        if (n + 1 >= 0 && n + 1 < q.win) out[n + 1] = (T)(z.y * w[n + 1]);
-    }
+    for (int r = 0; r < P; ++r) v[r] = framed::unsplit<C, P, NTW>(Y, tw, lane + 64 * r);
+    framed::fft_wave<C, P, NTW, true>(v, A, tw, lane);
+    framed::store_frame_grad<T, C, P>(A, w, q, out, lane);
 }
 
 template <typename T>
@@ -390,17 +264,7 @@ __global__ void __launch_bounds__(256) mrstft_ola_kernel(const T* __restrict__ g
         const Res& q = p.r[r];
         const int half = q.nfft / 2;
         const T* g = gframes + q.g0 + row * q.F * q.win;
-        // the frames that hold the padded sample j under their window, first to last
-        auto gather = [&](long j) {
-            const long hi = j - q.lpad, lo = hi - q.win + 1;
-            if (hi < 0) return;
-            const long f0 = lo <= 0 ? 0 : (lo + q.hop - 1) / q.hop;
-            const long f1 = min(q.F - 1, hi / q.hop);
-            for (long f = f0; f <= f1; ++f) acc += (double)g[f * q.win + (hi - f * q.hop)];
-        };
-        gather(t + half);                                              // the sample itself
-        if (t >= 1 && t <= half) gather(half - t);                     // its image in the left margin
-        if (t <= p.T - 2) gather(2 * (p.T - 1) - t + half);            // ... in the right margin (frames beyond the last hold none)
+        framed::gather_sample(g, t, p.T, half, q, q.F - 1, acc);
     }
     const long b = row / p.N, c = row - b * p.N;
     gy[(b * p.T + t) * p.N + c] = (T)((double)gloss[0] * acc);
