@@ -20,9 +20,9 @@
 
 namespace fl {
 
-// kept factors, tiled by the BPB bins of a workgroup: element (s, k) of bin f; pivot row s of bin f
-__host__ __device__ inline long kept_lu_index(int f, int s, int k, int N, int BPB) { return (((long)(f / BPB) * N + s) * BPB + f % BPB) * N + k; }
+// kept factors, tiled by the BPB bins of a workgroup: pivot row s of bin f; element (s, k) of bin f (N values per pivot row)
 __host__ __device__ inline long kept_piv_index(int f, int s, int N, int BPB) { return ((long)(f / BPB) * N + s) * BPB + f % BPB; }
+__host__ __device__ inline long kept_lu_index(int f, int s, int k, int N, int BPB) { return kept_piv_index(f, s, N, BPB) * N + k; }
 
 template <typename T>
 __device__ inline cx<T> shfl_cx(cx<T> v, int src, int width) {
@@ -58,7 +58,7 @@ struct Dud {
     cx<T>* cz;
     long cz_sb;
     int rv_real, cw_real;
-    // Kept factors (fl_solve_scaled_keep_*: the shuffle kernel only): the LU factors as they stand in the lanes' registers after
+    // Kept factors (fl_solve_scaled_keep_*; solve_kernel, the shuffle kernel, is the only one that stores them): the LU factors as they stand in the lanes' registers after
     // the elimination (L below the diagonal, unit diagonal implied, U on and above it) in pivot order, and piv = the row of A that
     // became each pivot row, TILED by the workgroup's bins: element (s, k) of bin f at kept_lu_index = [f / BPB][s][f % BPB][k], a
     // workgroup's BPB = 256 / NMAX bins form one contiguous N^2 BPB block.  The forward kernel's lane stores ITS ROW as one
@@ -317,15 +317,11 @@ __global__ void __launch_bounds__(256) solve_kernel(
 // substitutions are the outer-product form of the forward kernel: the lane that finishes an unknown broadcasts it, the others
 // subtract their stored entry times it.  x[piv[s]] = v[s] on the way out.  HBM-bound: 8 N^2 bytes per bin, once.
 template <typename T, int NMAX>
-__global__ void __launch_bounds__(256) solve_kept_adjoint_kernel(const cx<T>* __restrict__ LU, const int* __restrict__ piv, int TB,
-                                                                 const cx<T>* __restrict__ R, long rs_b, long rs_n,
-                                                                 long rs_k, const void* __restrict__ rv, int rv_real,
-                                                                 const cx<T>* __restrict__ rsig, long rsig_sb,
+__global__ void __launch_bounds__(256) solve_kept_adjoint_kernel(const cx<T>* __restrict__ LU, const int* __restrict__ piv,
+                                                                 const cx<T>* __restrict__ R, long rs_b, long rs_n, long rs_k,
                                                                  cx<T>* __restrict__ OUT, long os_b, long os_n, long os_k,
                                                                  int B, int M, int N, int K) {
-    // TB: bins per tile of the kernel that stored the factors (its workgroup's bins: kept_lu_index)
-    // rv / rsig: rank-one right-hand side conj(rv[j]) rsig[b][f] (the output-gain row times the output's gradient: ops.fdn_core), or R
-    constexpr int BPB = 256 / NMAX;
+    constexpr int BPB = 256 / NMAX;      // as in solve_kernel, which stored the factors: its workgroup's bins are one tile (kept_lu_index)
     const int gi = threadIdx.x % NMAX;
     const int f = blockIdx.x * BPB + threadIdx.x / NMAX;
     if (f >= M) return;      // whole lane group leaves together
@@ -333,8 +329,8 @@ __global__ void __launch_bounds__(256) solve_kept_adjoint_kernel(const cx<T>* __
     cx<T> col[NMAX];         // col[s] = conj(factor[s][gi]): entry (gi, s) of U^H (s <= gi) / L^H (s > gi)
     {   // every load unconditional and in flight together (lanes / rows beyond N read a valid element and discard it: a guard per
         // load made each one a branch with its own wait -- 32 serial round trips per wavefront, 1.06 ms at N = 32, M = 192001)
-        const cx<T>* base = LU + kept_lu_index(f, 0, on ? gi : 0, N, TB);
-        const long sstride = (long)TB * N;
+        const cx<T>* base = LU + kept_lu_index(f, 0, on ? gi : 0, N, BPB);
+        const long sstride = (long)BPB * N;
 #pragma unroll
         for (int s = 0; s < NMAX; ++s) col[s] = base[(s < N ? s : 0) * sstride];
 #pragma unroll
@@ -343,9 +339,7 @@ __global__ void __launch_bounds__(256) solve_kept_adjoint_kernel(const cx<T>* __
             col[s] = cx<T>(keep ? col[s].x : (T)0, keep ? -col[s].y : (T)0);
         }
     }
-    const int dst = on ? piv[kept_piv_index(f, gi, N, TB)] : 0;
-    cx<T> gvc(0, 0);
-    if (rv) gvc = conj(gain_at<T>(rv, rv_real, on ? gi : 0));
+    const int dst = on ? piv[kept_piv_index(f, gi, N, BPB)] : 0;
     cx<T> dinv(0, 0);
 #pragma unroll
     for (int s = 0; s < NMAX; ++s) {      // the lane's own diagonal of U^H (a select chain: the register index is the lane)
@@ -356,9 +350,7 @@ __global__ void __launch_bounds__(256) solve_kept_adjoint_kernel(const cx<T>* __
     const int ncols = B * K;
     for (int c = 0; c < ncols; ++c) {
         const int b = c / K, kk = c - b * K;
-        cx<T> y(0, 0);
-        if (rv) y = gvc * rsig[(long)b * rsig_sb + f];
-        else y = R[(long)b * rs_b + (long)(on ? gi : 0) * rs_n + (long)kk * rs_k + f];
+        cx<T> y = R[(long)b * rs_b + (long)(on ? gi : 0) * rs_n + (long)kk * rs_k + f];
         y = cx<T>(on ? y.x : (T)0, on ? y.y : (T)0);
         // U^H z = b: z_s = b_s / conj(U[s][s]) in lane s; lanes j > s subtract conj(U[s][j]) z_s
 #pragma unroll
@@ -779,34 +771,6 @@ __global__ void __launch_bounds__(256) solve_inplace_kernel(
         dinv[SK].y = (gi == LK) ? inv.y : dinv[SK].y;
     });
 
-    if (dud.lu_out) {      // (uniform) the factors and the pivot order are kept for the adjoint system (see Dud): rows are in pivot order already
-#pragma unroll
-        for (int s = 0; s < RPL; ++s) {
-            const int pr = s * LANES + gi;
-            if (pr < N) {
-                cx<T>* lo = dud.lu_out + kept_lu_index(f, pr, 0, N, BPB);
-                if ((N & 1) == 0 || sizeof(T) == 8) {
-                    typedef T v4 __attribute__((ext_vector_type(16 / sizeof(T))));
-                    constexpr int PER = 16 / sizeof(cx<T>);
-#pragma unroll
-                    for (int k = 0; k < NMAX; k += PER) {
-                        if (k < N) {
-                            v4 q;
-                            if constexpr (PER == 2) q = v4{row[s][k].x, row[s][k].y, row[s][k + 1].x, row[s][k + 1].y};
-                            else q = v4{row[s][k].x, row[s][k].y};
-                            *reinterpret_cast<v4*>(lo + k) = q;
-                        }
-                    }
-                } else {
-#pragma unroll
-                    for (int k = 0; k < NMAX; ++k)
-                        if (k < N) lo[k] = row[s][k];
-                }
-                dud.piv_out[kept_piv_index(f, pr, N, BPB)] = orig[s];
-            }
-        }
-    }
-
     // ---- w = A^-H cw^H from the factors just formed (see Dud::wadj).  P A = L U with the rows in pivot order: A^H = U^H L^H P, so
     // U^H z = cw^H, L^H u = z, w[orig[p]] = u[p].  Lane (slot s, lane g) holds row p = s LANES + g of the factors, i.e. COLUMN p of
     // U^H and L^H: unknown k is a dot product over the lanes -- sum_p conj(row_p[k]) z_p, the not-yet-known entries still zero, so
@@ -963,6 +927,10 @@ static int launch_solve(const void* P, long p_pitch, const Dud<T>& dud, int one_
                         void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, int K, hipStream_t st) {
     // every kernel takes the same arguments; a workgroup's 256 lanes are `lanes` per bin
     auto launch = [&](auto kern, int lanes) {
+        if ((dud.lu_out || dud.piv_out) && kern != &solve_kernel<T, NMAX>) {      // refused, never dropped
+            set_error("solve: N=%d: factors are kept by the shuffle kernel only (fl_solve_scaled_keep_*), not by the in-place kernels", N);
+            return FL_ERR_UNSUPPORTED;
+        }
         hipLaunchKernelGGL(kern, dim3(cdiv_i(M, 256 / lanes)), dim3(256), 0, st, (const cx<T>*)P, p_pitch, dud, one_minus, adjoint,
                            (const cx<T>*)R, rs_b, rs_n, rs_k, (cx<T>*)OUT, os_b, os_n, os_k, B, M, N, K);
         FL_CHECK_LAUNCH("solve");
@@ -1540,19 +1508,15 @@ static int solve_scaled_keep_impl(const void* P, long p_pitch, const void* l, lo
 }
 template <typename T>
 static int solve_kept_adjoint_impl(const void* LU, const void* piv, const void* R, long rs_b, long rs_n,
-                                   long rs_k, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, int K, void* stream,
-                                   int tile_bins = 0, const void* rv = nullptr, int rv_real = 0, const void* rsig = nullptr,
-                                   long rsig_sb = 0) {
-    FL_REQUIRE(LU && piv && (R || (rv && rsig)) && OUT, "solve_kept_adjoint: null pointer");
+                                   long rs_k, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, int K, void* stream) {
+    FL_REQUIRE(LU && piv && R && OUT, "solve_kept_adjoint: null pointer");
     FL_REQUIRE(B >= 0 && M >= 0 && N > 0 && K > 0, "solve_kept_adjoint: bad sizes");
-    FL_REQUIRE(!rv || K == 1, "solve_kept_adjoint: the rank-one right-hand side has one column per batch item");
     FL_REQUIRE(N <= (sizeof(T) == 8 ? 32 : 64), "solve_kept_adjoint: N exceeds the register-resident kernels (%d)", sizeof(T) == 8 ? 32 : 64);
     if (B == 0 || M == 0) return FL_OK;
     solve_dispatch<T>(N, [&](auto nm) {
         constexpr int NM = decltype(nm)::value;
         hipLaunchKernelGGL((solve_kept_adjoint_kernel<T, NM>), dim3(cdiv_i(M, 256 / NM)), dim3(256), 0, (hipStream_t)stream, (const cx<T>*)LU,
-                           (const int*)piv, tile_bins > 0 ? tile_bins : 256 / NM, (const cx<T>*)R, rs_b, rs_n, rs_k, rv, rv_real,
-                           (const cx<T>*)rsig, rsig_sb, (cx<T>*)OUT, os_b, os_n, os_k, B, M, N, K);
+                           (const int*)piv, (const cx<T>*)R, rs_b, rs_n, rs_k, (cx<T>*)OUT, os_b, os_n, os_k, B, M, N, K);
     });
     FL_CHECK_LAUNCH("solve_kept_adjoint");
     return FL_OK;
@@ -1584,11 +1548,6 @@ size_t fl_solve_kept_piv_elems(int N, int M, int f64) {
 }
 // the FDN form, forward system, with w = A^-H cw^H beside OUT and cz (Dud::wadj): float32, 4 < N <= 16
 int fl_solve_fdn_wadj_supported(int N) { return (N > 4 && N <= 16 && g_solve_variant == 0) ? 1 : 0; }
-// the FDN form (fl_solve_fdn_*) with kept factors: 8 < N <= 16 on the two-rows-per-lane kernel (its workgroup's 32 bins are a tile)
-int fl_solve_fdn_keep_tile(int N, int f64) {
-    (void)f64;
-    return (N > 8 && N <= 16 && g_solve_variant == 0) ? 32 : 0;
-}
 int fl_solve_dud_grads_blocks(int M, int N) { return dud_grads_blocks(M, N); }
 }
 
@@ -1675,13 +1634,6 @@ FL_ENTRY_C64_C128(fl_solve_kept_adjoint, (const void* LU, const void* piv, const
                   (LU, piv, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream)) {
     return solve_kept_adjoint_impl<T>(LU, piv, R, rs_b, rs_n, rs_k, OUT, os_b, os_n, os_k, B, M, N, K, stream);
 }
-// A^-H (conj(rv) . rs) from factors kept by fl_solve_fdn_keep_* (tile_bins = fl_solve_fdn_keep_tile)
-FL_ENTRY_C64_C128(fl_solve_kept_adjoint_rank1, (const void* LU, const void* piv, int tile_bins, const void* rv, int rv_real, const void* rs,
-                                                long rs_sb, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N, void* stream),
-                  (LU, piv, tile_bins, rv, rv_real, rs, rs_sb, OUT, os_b, os_n, os_k, B, M, N, stream)) {
-    FL_REQUIRE(rv && rs && tile_bins > 0, "solve_kept_adjoint_rank1: null pointer / tile");
-    return solve_kept_adjoint_impl<T>(LU, piv, nullptr, 0, 0, 0, OUT, os_b, os_n, os_k, B, M, N, 1, stream, tile_bins, rv, rv_real, rs, rs_sb);
-}
 FL_ENTRY_C64_C128(fl_solve_dud, (const void* l, long l_sn, long l_sf, const void* U, const void* r, long r_sn, long r_sf, int adjoint,
                                  const void* R, long rs_b, long rs_n, long rs_k, void* OUT, long os_b, long os_n, long os_k, int B, int M,
                                  int N, int K, void* stream),
@@ -1756,18 +1708,5 @@ FL_ENTRY_C64_C128(fl_solve_fdn_wadj, (const void* l, long l_sn, long l_sf, const
     FL_REQUIRE(fl_solve_fdn_wadj_supported(N), "solve_fdn_wadj: 4 < N <= 16 on the default kernels (fl_solve_fdn_wadj_supported)");
     Dud<T> d = dud_fdn<T>(l, l_sn, l_sf, l2, l2_sn, l2_sf, U, r, r_sn, r_sf, 1, rv, rv_real, rs, rs_sb, cw, cw_real, cz, cz_sb);
     d.wadj = (cx<T>*)wadj; d.wadj_sn = wadj_sn;
-    return solve_impl<T>(nullptr, 0, d, 1, 0, nullptr, 0, 0, 0, OUT, os_b, os_n, os_k, B, M, N, 1, stream);
-}
-// the FDN form, forward system, with kept factors (fl_solve_fdn_keep_tile)
-FL_ENTRY_C64_C128(fl_solve_fdn_keep, (const void* l, long l_sn, long l_sf, const void* l2, long l2_sn, long l2_sf, const void* U, const void* r,
-                                      long r_sn, long r_sf, const void* rv, int rv_real, const void* rs, long rs_sb, const void* cw,
-                                      int cw_real, void* cz, long cz_sb, void* OUT, long os_b, long os_n, long os_k, int B, int M, int N,
-                                      void* LU, void* piv, void* stream),
-                  (l, l_sn, l_sf, l2, l2_sn, l2_sf, U, r, r_sn, r_sf, rv, rv_real, rs, rs_sb, cw, cw_real, cz, cz_sb, OUT, os_b, os_n, os_k, B,
-                   M, N, LU, piv, stream)) {
-    FL_REQUIRE(U && l2 && rv && rs && (!cz || cw) && LU && piv, "solve_fdn_keep: null pointer");
-    FL_REQUIRE(fl_solve_fdn_keep_tile(N, sizeof(T) == 8) > 0, "solve_fdn_keep: 8 < N <= 16 on the default kernels (fl_solve_fdn_keep_tile)");
-    Dud<T> d = dud_fdn<T>(l, l_sn, l_sf, l2, l2_sn, l2_sf, U, r, r_sn, r_sf, 1, rv, rv_real, rs, rs_sb, cw, cw_real, cz, cz_sb);
-    d.lu_out = (cx<T>*)LU; d.piv_out = (int*)piv;
     return solve_impl<T>(nullptr, 0, d, 1, 0, nullptr, 0, 0, 0, OUT, os_b, os_n, os_k, B, M, N, 1, stream);
 }

@@ -1625,14 +1625,6 @@ def _fdn_in_solve(real, N) -> bool:
     return FDN_GAINS_IN_SOLVE and N <= (32 if real == torch.float32 else 16)
 
 
-# The FDN's forward solve CAN keep its LU factors (8 N^2 bytes per bin: 197 MB at 16 channels, nfft = 192000) for the backward
-# pass's adjoint system (fl_solve_fdn_keep_* / fl_solve_kept_adjoint_rank1_*; 8 < N <= 16) -- measured and left OFF: at N = 16 the
-# two passes over the factors (stores + 39 us on the forward kernel, 43.5 us for the substitution, both at HBM rate) cost more
-# than the elimination they replace (66 us): 0.339 against 0.311 ms on the replayed FDN step.  The elimination grows with N^3, the
-# factors with N^2: the scaled loop keeps them above 16 channels (KEEP_LU), where it wins 1.8 ms at N = 32.  Tests run both.
-KEEP_LU_FDN = False
-
-
 # A one-output FDN's backward right-hand side is the output-gain row times a scalar per (batch item, bin): its adjoint solution is
 # w[f] gy[b][f] with w = A^-H c^H formed by the FORWARD launch from its own factors (fl_solve_fdn_wadj_c64; float32, 4 < N <= 16) --
 # the backward pass then runs no solve.  False: the adjoint system is factored and solved by a launch of its own.
@@ -1643,7 +1635,6 @@ FDN_ADJOINT_IN_FORWARD_F64 = True      # (float64: the forward kernel with w run
 def _fdn_route(real, N, needs_grad) -> str:
     """How ops.fdn_core reaches the solve kernels, chosen once in the forward pass:
     "wadj"     fl_solve_fdn_wadj_*: the forward launch also leaves w = A^-H c^H; the backward pass runs no solve
-    "keep"     fl_solve_fdn_keep_*: the forward launch keeps its factors; the adjoint is fl_solve_kept_adjoint_rank1_*
     "in_solve" fl_solve_fdn_* forward and adjoint: the gains inside the kernels, a second elimination for the adjoint
     "layered"  fl_solve_dud2_* between separate launches for b x, c OUT and c^H gy"""
     if not _fdn_in_solve(real, N):
@@ -1652,23 +1643,19 @@ def _fdn_route(real, N, needs_grad) -> str:
     if needs_grad and FDN_ADJOINT_IN_FORWARD and (real == torch.float32 or FDN_ADJOINT_IN_FORWARD_F64) and \
             L.fl_solve_fdn_wadj_supported(N):
         return "wadj"
-    if needs_grad and KEEP_LU_FDN and L.fl_solve_fdn_keep_tile(N, int(real == torch.float64)) > 0:
-        return "keep"
     return "in_solve"
 
 
-def _solve_fdn_call(name, span, head, gain, sig, N, cw=None, contracts=True, post=()):
+def _solve_fdn_call(name, span, head, gain, sig, N, cw=None, post=()):
     """(OUT (B, M, N), z (B, M, 1) | None) from an entry ``name``_c64 / _c128 that builds its right-hand side gain . sig in the
     kernel.  gain, cw: contiguous N-vectors, real or complex; sig: planar one-channel signal (B, M, 1); z = cw . OUT.
-    fn(*head, gain, sig, [cw, z -- the entries that can contract], OUT and its strides, B, M, N, *post, stream)."""
+    fn(*head, gain, sig, cw, z, OUT and its strides, B, M, N, *post, stream)."""
     B, M, _, K, ss_b, _, _ = _bnk(sig)
     assert K == 1
     OUT = _empty_planar((B, M, N), sig.dtype, sig.device)
     _, _, _, _, os_b, os_n, os_k = _bnk(OUT)
     z = _empty_planar((B, M, 1), sig.dtype, sig.device) if cw is not None else None
-    contract = ()
-    if contracts:
-        contract = ((None, 0, None, 0) if cw is None else (cw.data_ptr(), int(not cw.is_complex()), z.data_ptr(), _bnk(z)[4]))
+    contract = (None, 0, None, 0) if cw is None else (cw.data_ptr(), int(not cw.is_complex()), z.data_ptr(), _bnk(z)[4])
     fn = _fn(name, _rdtype(sig), True)
     with kernel_timer.span(span):
         _lib.check(fn(*head, gain.data_ptr(), int(not gain.is_complex()), sig.data_ptr(), ss_b, *contract, OUT.data_ptr(), os_b,
@@ -1679,31 +1666,16 @@ def _solve_fdn_call(name, span, head, gain, sig, N, cw=None, contracts=True, pos
 def _solve_fdn_launch(l, l2, U, r, adjoint, gain, sig, cw, route="in_solve"):
     """OUT = A^-1 (l2 . (gain sig)) [forward] or A^-H (conj(gain) sig) [adjoint]; with cw (forward) also z = cw . OUT.
     -> (OUT, z | None, extra): what the route's forward launch leaves for the backward pass -- "wadj": (W,) with W (1, M, N)
-    planar = A^-H cw^H; "keep": (LU, piv), the factors for _solve_fdn_kept_adjoint_launch; else ()."""
-    N, M, f64 = U.shape[0], sig.shape[1], int(_rdtype(sig) == torch.float64)
+    planar = A^-H cw^H; else ()."""
+    N, M = U.shape[0], sig.shape[1]
     loop = _loop_args(l, l2, U, r)
     if route == "wadj":
         assert not adjoint and cw is not None
         W = _empty_planar((1, M, N), sig.dtype, sig.device)
         OUT, z = _solve_fdn_call("fl_solve_fdn_wadj", "solve_dud", loop, gain, sig, N, cw, post=(W.data_ptr(), _bnk(W)[5]))
         return OUT, z, (W,)
-    if route == "keep":
-        assert not adjoint
-        tile = _lib.lib().fl_solve_fdn_keep_tile(N, f64)
-        nt = (M + tile - 1) // tile
-        LU = torch.empty(nt * tile * N * N, dtype=sig.dtype, device=sig.device)
-        piv = torch.empty(nt * tile * N, dtype=torch.int32, device=sig.device)
-        OUT, z = _solve_fdn_call("fl_solve_fdn_keep", "solve_dud", loop, gain, sig, N, cw, post=(LU.data_ptr(), piv.data_ptr()))
-        return OUT, z, (LU, piv)
     OUT, z = _solve_fdn_call("fl_solve_fdn", "solve_dud_adj" if adjoint else "solve_dud", (*loop, int(adjoint)), gain, sig, N, cw)
     return OUT, z, ()
-
-
-def _solve_fdn_kept_adjoint_launch(LU, piv, gain, sig, N):
-    """A^-H (conj(gain) sig) from the factors the forward solve kept"""
-    tile = _lib.lib().fl_solve_fdn_keep_tile(N, int(_rdtype(sig) == torch.float64))
-    return _solve_fdn_call("fl_solve_kept_adjoint_rank1", "solve_dud_adj", (LU.data_ptr(), piv.data_ptr(), int(tile)), gain, sig, N,
-                           contracts=False)[0]
 
 
 class _FdnCore(torch.autograd.Function):
@@ -1730,7 +1702,7 @@ class _FdnCore(torch.autograd.Function):
             y, extra = _apply_const(cc, False, OUT), ()
         else:
             OUT, y, extra = _solve_fdn_launch(lp, l2p, Uc, rp, False, bc, Xp, cc, route=route)
-        ctx.save_for_backward(lp, l2p, Uc, rp, OUT, Xp, bc, cc, *extra)     # extra: (W,) on "wadj", (LU, piv) on "keep"
+        ctx.save_for_backward(lp, l2p, Uc, rp, OUT, Xp, bc, cc, *extra)     # extra: (W,) on "wadj"
         return y
 
     @staticmethod
@@ -1741,8 +1713,6 @@ class _FdnCore(torch.autograd.Function):
         gR = Wadj = None
         if route == "wadj":   # A^-H c^H gy = w gy with w from the forward launch: formed inside the gradient kernel, no solve, no tensor
             Wadj, = extra
-        elif route == "keep":        # A^-H c^H gy from the forward solve's factors: a substitution, no second elimination
-            gR = _solve_fdn_kept_adjoint_launch(*extra, cc, gyp, Uc.shape[0])
         elif route == "in_solve":
             gR, _, _ = _solve_fdn_launch(lp, l2p, Uc, rp, True, cc, gyp, None)                        # A^-H c^H gy
         else:
@@ -1771,7 +1741,8 @@ def fdn_core(b, c, l, l2, U, r, X):
 
 # The scaled loop's forward solve keeps its LU factors for the backward pass's adjoint system when the elimination dominates the
 # solve (N > KEEP_LU_MIN_N) and the factors fit the budget: 8 N^2 bytes per bin in HBM (1.6 GB at the 32 x 32 chain of nfft =
-# 384000) against a second (2/3) N^3 elimination per bin.  False / a smaller budget: the adjoint system is factored again.
+# 384000) against a second (2/3) N^3 elimination per bin.  The elimination grows with N^3, the factors with N^2: above 16 channels
+# keeping them wins 1.8 ms at N = 32.  False / a smaller budget: the adjoint system is factored again.
 KEEP_LU = True
 KEEP_LU_MIN_N = 16
 KEEP_LU_MAX_BYTES = 16 << 30

@@ -96,7 +96,7 @@ def test_signatures_of_the_real_header_pinned_rows():
     longest parameter list."""
     from flamo_amd import _lib
     S = _lib._SIGNATURES
-    assert len(S) == 188 and _lib.EXPORTS == tuple(S)
+    assert len(S) == 183 and _lib.EXPORTS == tuple(S)
     assert S["fl_version"] == (_i, [])
     assert S["fl_last_error"] == (ctypes.c_char_p, [])
     assert S["fl_fft_plan"] == (_i, [_i, _i, _ip, _ip])
@@ -121,7 +121,7 @@ def test_precision_pairs_have_one_signature():
     float_eval = {"fl_sos_response_rc_c64", "fl_geq_response_rc_c64"}
     pairs = [(n, n[:-len(lo)] + hi) for lo, hi in (("_f32", "_f64"), ("_c64", "_c128")) for n in S if n.endswith(lo)]
     pairs = [(n, m) for n, m in pairs if m in S]
-    assert len(pairs) >= 60 and float_eval <= {n for n, _ in pairs}
+    assert len(pairs) >= 58 and float_eval <= {n for n, _ in pairs}
     for n, m in pairs:
         res, args = S[n]
         if n in float_eval:
@@ -205,18 +205,18 @@ def test_solve_variant_hook_accepts_only_the_remaining_codes():
     elimination, 10 + t: pivot threshold 2^-t) and unknown ones are errors with a message."""
     from flamo_amd import _lib
     L = _lib.lib()
-    probes = lambda: (L.fl_solve_fdn_wadj_supported(16), L.fl_solve_fdn_keep_tile(16, 0))  # noqa: E731
+    probes = lambda: L.fl_solve_fdn_wadj_supported(16)  # noqa: E731
     try:
-        for ok, want in ((0, (1, 32)), (1, (0, 0)), (4, (0, 0))):
+        for ok, want in ((0, 1), (1, 0), (4, 0)):
             assert L.fl_debug_set_solve_variant(ok) == 0, ok
             assert probes() == want, ok
         for bad in (3, 5, 10, 11, 12, 2, -1):
             assert L.fl_debug_set_solve_variant(bad) == -1, bad
             assert f"got {bad})".encode() in L.fl_last_error(), bad      # this call's own message, not an earlier one
-            assert probes() == (0, 0), bad                              # a refused call changes no state (still code 4)
+            assert probes() == 0, bad                                   # a refused call changes no state (still code 4)
     finally:
         assert L.fl_debug_set_solve_variant(0) == 0
-    assert probes() == (1, 32)
+    assert probes() == 1
 
 
 def test_ops_fail_loudly_without_gpu_tensors():

@@ -1124,17 +1124,15 @@ def test_scaled_loop_adjoint_from_kept_factors(gpu, N, K):
 @pytest.mark.parametrize("N", [5, 6, 8, 9, 12, 13, 16])
 @pytest.mark.parametrize("kind", ["damped", "exchanges"])
 def test_fdn_adjoint_from_kept_factors(gpu, N, kind):
-    """ops.fdn_core's backward system A^H x = c^H g (8 < N <= 16) three ways: x = w g with w = A^-H c^H computed by the FORWARD
-    launch from its own factors (fl_solve_fdn_wadj_c64: float32 default, no solve in the backward pass), a substitution over
-    factors the forward solve kept (fl_solve_fdn_keep_* + fl_solve_kept_adjoint_rank1_*), and a second elimination
-    (fl_solve_fdn_* adjoint) -- output and every gradient against LAPACK autograd
+    """ops.fdn_core's backward system A^H x = c^H g (4 < N <= 16) two ways: x = w g with w = A^-H c^H computed by the FORWARD
+    launch from its own factors (fl_solve_fdn_wadj_*: the default, no solve in the backward pass), and a second elimination
+    (fl_solve_fdn_* adjoint, ops.FDN_ADJOINT_IN_FORWARD = False) -- output and every gradient of BOTH against LAPACK autograd
     in float64 on the materialised system (flamo/processor/system.py:420-425 between the two gains), for damped loops (no row
     moves) and loops that exchange rows at every step (the pivot order travels with the factors), odd and even N, batch 1 and
-    3, and against the re-factoring route it replaces (ops.KEEP_LU_FDN = False)."""
+    3, and the two routes against each other."""
     from flamo_amd import _lib, ops
     torch.manual_seed(7 * N + (kind == "exchanges"))
     M = 391
-    assert _lib.lib().fl_solve_fdn_keep_tile(N, 0) == (32 if N > 8 else 0)      # (ops.KEEP_LU_FDN is off by default: measured slower)
     assert _lib.lib().fl_solve_fdn_wadj_supported(N) == 1
     for cd, tol in ((torch.complex128, 1e-11), (torch.complex64, 3e-5)):
         rd = torch.float64 if cd == torch.complex128 else torch.float32
@@ -1161,13 +1159,9 @@ def test_fdn_adjoint_from_kept_factors(gpu, N, kind):
             Yr = (out * cR.to(torch.complex128).squeeze(0)).sum(-1, keepdim=True)
             want = torch.autograd.grad(torch.sum(torch.real(Yr * torch.conj(C64))), ref_in)
             res = {}
-            # three routes to A^-H c^H gy: w gy with w from the forward launch (float32 default) / a substitution over kept factors /
-            # a second elimination
-            routes = (("forward", (True, False)), ("kept", (False, True)), ("refactor", (False, False)))
-            if N <= 8:
-                routes = (routes[0], routes[2])          # (factors are kept above 8 channels only)
-            for route, (in_fwd, keep) in routes:
-                ops.FDN_ADJOINT_IN_FORWARD, ops.KEEP_LU_FDN = in_fwd, keep
+            # two routes to A^-H c^H gy: w gy with w from the forward launch (the default) / a second elimination
+            for route, in_fwd in (("forward", True), ("refactor", False)):
+                ops.FDN_ADJOINT_IN_FORWARD = in_fwd
                 try:
                     dev_in = [b64.to(gpu, rd), c64.to(gpu, rd), l64.to(gpu, cd), U64.to(gpu, cd), r64.to(gpu, cd), X64.to(gpu, cd)]
                     dev_in = [t.requires_grad_(True) for t in dev_in]
@@ -1177,20 +1171,16 @@ def test_fdn_adjoint_from_kept_factors(gpu, N, kind):
                     torch.cuda.synchronize()
                     used = set(ops.kernel_timer.summary())
                 finally:
-                    ops.FDN_ADJOINT_IN_FORWARD, ops.KEEP_LU_FDN = True, False
+                    ops.FDN_ADJOINT_IN_FORWARD = True
                     ops.kernel_timer.enabled = False
                 res[route] = [Y.detach()] + list(got)
                 # the forward route runs no adjoint solve at all
                 assert ("solve_dud_adj" in used) == (route != "forward"), (route, used)
             tag = f"fdn_kept/{kind}_N{N}_B{B}_{str(cd)[-3:]}"
             names = ("Y", "g_b", "g_c", "g_l", "g_U", "g_r", "g_X")
-            for route in [r for r in ("forward", "kept") if r in res]:
+            for route in ("forward", "refactor"):
                 for name, a, w in zip(names, res[route], [Yr.detach()] + list(want)):
                     w = w.real if (not a.is_complex() and w.is_complex()) else w
                     check_close(f"{tag}/{route}/{name}", a.cpu().to(w.dtype), w, tol * scale, max_tol=float("inf"))
-            for route in [r for r in ("forward", "kept") if r in res]:
-                # ("kept": the same forward kernel with the factor stores -- identical; "forward": an instantiation of its own)
-                if route == "kept":
-                    assert torch.equal(res[route][0], res["refactor"][0])
-                for a, b in zip(res[route], res["refactor"]):                # rounding apart
-                    assert relerr(a, b) < tol * scale
+            for a, b in zip(res["forward"], res["refactor"]):                # (the forward kernel with w is an instantiation of its own)
+                assert relerr(a, b) < tol * scale                            # rounding apart

@@ -251,4 +251,4 @@ def test_header_declares_what_the_library_exports():
             assert hasattr(handle, s), f"{s} declared in include/flamo_hip_fdnatt.h but not exported"
     for name, (res, args) in _lib._SIGNATURES_FDNATT.items():
         assert res is ctypes.c_int and args[-1] is ctypes.c_void_p, name
-    assert not set(syms) & set(_lib.EXPORTS) and len(_lib.EXPORTS) == 188
+    assert not set(syms) & set(_lib.EXPORTS) and len(_lib.EXPORTS) == 183
