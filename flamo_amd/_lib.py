@@ -1,7 +1,8 @@
 """ctypes binding of libflamo_hip.so.  The C ABI is declared in include/flamo_hip.h (and, for the energy-decay-curve and the
-average-power criteria, the FDN attenuation designs and the multi-resolution STFT criterion, include/flamo_hip_edc.h,
-include/flamo_hip_avgpow.h, include/flamo_hip_fdnatt.h and include/flamo_hip_mrstft.h), and the restype / argtypes of every entry
-point are read from those headers at import (_parse_header): no signature is written a second time here.
+average-power criteria, the FDN attenuation designs, the multi-resolution STFT and the energy-decay-relief criteria,
+include/flamo_hip_edc.h, include/flamo_hip_avgpow.h, include/flamo_hip_fdnatt.h, include/flamo_hip_mrstft.h and
+include/flamo_hip_edr.h), and the restype / argtypes of every entry point are read from those headers at import
+(_parse_header): no signature is written a second time here.
 
 The shared library is built in-tree (``flamo_amd/libflamo_hip.so``) by ``build()`` /
 ``make -C flamo_amd/csrc``.  There is NO fallback: if the library is missing or a tensor is
@@ -24,6 +25,7 @@ HEADER_EDC_PATH = os.path.join(os.path.dirname(_HERE), "include", "flamo_hip_edc
 HEADER_AVGPOW_PATH = os.path.join(os.path.dirname(_HERE), "include", "flamo_hip_avgpow.h")      # ... of csrc/avgpow.hip
 HEADER_FDNATT_PATH = os.path.join(os.path.dirname(_HERE), "include", "flamo_hip_fdnatt.h")      # the designs of csrc/fdnatt.hip
 HEADER_MRSTFT_PATH = os.path.join(os.path.dirname(_HERE), "include", "flamo_hip_mrstft.h")      # the criterion of csrc/mrstft.hip
+HEADER_EDR_PATH = os.path.join(os.path.dirname(_HERE), "include", "flamo_hip_edr.h")      # ... of csrc/edr.hip
 
 _lock = threading.Lock()
 _lib = None
@@ -103,6 +105,9 @@ _SIGNATURES_FDNATT = _read_header(HEADER_FDNATT_PATH)
 # ... and those of include/flamo_hip_mrstft.h
 _SIGNATURES_MRSTFT = _read_header(HEADER_MRSTFT_PATH)
 
+# ... and those of include/flamo_hip_edr.h
+_SIGNATURES_EDR = _read_header(HEADER_EDR_PATH)
+
 
 def build(force: bool = False) -> str:
     """Compile every HIP source for gfx950 into flamo_amd/libflamo_hip.so (hipcc cross-compiles
@@ -141,7 +146,7 @@ def lib(pair_ok: bool = False) -> C.CDLL:
                     )
                 handle = C.CDLL(LIB_PATH)
                 for name, (res, args) in (*_SIGNATURES.items(), *_SIGNATURES_EDC.items(), *_SIGNATURES_AVGPOW.items(),
-                                           *_SIGNATURES_FDNATT.items(), *_SIGNATURES_MRSTFT.items()):
+                                           *_SIGNATURES_FDNATT.items(), *_SIGNATURES_MRSTFT.items(), *_SIGNATURES_EDR.items()):
                     fn = getattr(handle, name)  # AttributeError if the symbol is missing
                     fn.restype = res
                     fn.argtypes = args

@@ -1,5 +1,5 @@
-// The framed real transform of the short-time criteria (avgpow.hip, mrstft.hip), one wavefront per frame: the wave-level pieces
-// only -- the kernels, their plans and LDS arrays are the callers'.
+// The framed real transform of the short-time criteria (avgpow.hip, mrstft.hip, edr.hip), one wavefront per frame: the
+// wave-level pieces only -- the kernels, their plans and LDS arrays are the callers'.
 //
 // The n_fft = 128 P real samples of a frame are Nc = 64 P complex ones (even samples real, odd samples imaginary), P = 2, 4, 8,
 // 16 per lane.  The window is applied while loading and only the samples under its support [lpad, lpad + win) are read.  The

@@ -3094,6 +3094,156 @@ def mrstft_loss(y_pred: torch.Tensor, y_true: torch.Tensor, resolutions=((1024, 
     return _MRSTFT.apply(y_pred, y_true, res, wts, float(eps))
 
 
+EDR_BANDS, EDR_FMIN = 64, 20.0                       # the reference's mel filter bank (optimize/loss.py:623-635)
+_edr_tables = {}
+
+
+def mel_basis(sample_rate, nfft: int, n_mels: int = 64, fmin: float = 20.0, fmax=None) -> torch.Tensor:
+    """The (n_mels, nfft / 2 + 1) mel filter bank in the librosa / Slaney form (``htk=False``, ``norm=1``) as a float64 host
+    matrix: n_mels + 2 points equally spaced in mel from mel(fmin) to mel(fmax) (``fmax`` = sample_rate / 2 when None), mel(f) =
+    f / (200 / 3) under 1000 Hz and 15 + ln(f / 1000) / (ln(6.4) / 27) above, mapped back to Hz as m_0 .. m_{n_mels + 1};
+    W[j, k] = max(0, min((f_k - m_j) / (m_{j+1} - m_j), (m_{j+2} - f_k) / (m_{j+2} - m_{j+1}))) 2 / (m_{j+2} - m_j) on the bin
+    frequencies f_k = linspace(0, sample_rate / 2, nfft / 2 + 1).  The table the kernels of ``edr_loss`` read is this matrix."""
+    fmax = sample_rate / 2 if fmax is None else fmax
+    f_sp, logstep = 200.0 / 3.0, np.log(6.4) / 27.0
+
+    def to_mel(f):
+        return f / f_sp if f < 1000.0 else 15.0 + np.log(f / 1000.0) / logstep
+
+    mels = np.linspace(to_mel(float(fmin)), to_mel(float(fmax)), n_mels + 2)
+    hz = np.where(mels >= 15.0, 1000.0 * np.exp(logstep * (mels - 15.0)), f_sp * mels)
+    bins = np.linspace(0.0, sample_rate / 2, nfft // 2 + 1)
+    up = (bins[None, :] - hz[:-2, None]) / (hz[1:-1] - hz[:-2])[:, None]
+    down = (hz[2:, None] - bins[None, :]) / (hz[2:] - hz[1:-1])[:, None]
+    W = np.maximum(0.0, np.minimum(up, down)) * (2.0 / (hz[2:] - hz[:-2]))[:, None]
+    return torch.from_numpy(W)
+
+
+def _edr_mel_tables(W: np.ndarray):
+    """(melidx int32, melw float64, nnz) of include/flamo_hip_edr.h from the host matrix: per band the span of its non-zero
+    bins and its weights packed behind one another, per bin the lower of the two consecutive bands that hold it and its two
+    weights"""
+    n_mels, nb = W.shape
+    start, count, packed = np.zeros(n_mels, np.int32), np.zeros(n_mels, np.int32), []
+    for j in range(n_mels):
+        nz = np.nonzero(W[j])[0]
+        if nz.size:
+            start[j], count[j] = nz[0], nz[-1] - nz[0] + 1
+            packed.append(W[j, nz[0]:nz[-1] + 1])
+    offset = (np.cumsum(count) - count).astype(np.int32)
+    nnz = int(count.sum())
+    band, bw = np.zeros(nb, np.int32), np.zeros((nb, 2))
+    for k in range(nb):
+        js = np.nonzero(W[:, k])[0]
+        if js.size > 2 or (js.size == 2 and js[1] != js[0] + 1):
+            raise ValueError(f"mel basis: bin {k} lies in the bands {js.tolist()}, not in at most two consecutive ones")
+        if js.size:
+            band[k] = min(int(js[0]), n_mels - 2)
+            for j in js:
+                bw[k, j - band[k]] = W[j, k]
+    melidx = np.concatenate([start, count, offset, band]).astype(np.int32)
+    melw = np.concatenate(packed + [bw.reshape(-1)])
+    return melidx, melw, nnz
+
+
+def edr_supported(shape, nfft, hop, win) -> bool:
+    """whether ``edr_loss`` takes (B, T, N) signals under these frames: nfft a power of two from 256 to 2048,
+    1 <= win <= nfft, hop >= 1, nfft / 2 < T <= 2^30, fewer than 2^31 frames and at most 2^38 samples in all"""
+    try:
+        dims, frame = tuple(int(s) for s in shape), tuple(int(v) for v in (nfft, hop, win))
+        same = all(a == b for a, b in zip(dims + frame, tuple(shape) + (nfft, hop, win)))
+    except (TypeError, ValueError):
+        return False
+    if not same or len(dims) != 3 or max(map(abs, dims)) >= 1 << 62 or max(map(abs, frame)) >= 1 << 31:
+        return False
+    return _lib.lib().fl_edr_frames(*dims, *frame) >= 0      # the library's own support query: one statement of the sizes
+
+
+def _edr_consts(sample_rate, nfft, win, dev: torch.device):
+    """(window, twiddles, melidx, melw, nnz) cached per (sample_rate, nfft, win, device): the periodic Hann window and the mel
+    tables, made on the host in float64 under either precision of the signals"""
+    key = (sample_rate, nfft, win, dev.index if dev.index is not None else torch.cuda.current_device())
+    ent = _edr_tables.get(key)
+    if ent is None:
+        melidx, melw, nnz = _edr_mel_tables(mel_basis(sample_rate, nfft, EDR_BANDS, EDR_FMIN, sample_rate // 2).numpy())
+        L = _lib.lib()
+        assert melidx.size == L.fl_edr_mel_ints(nfft) and melw.size == L.fl_edr_mel_doubles(nfft, nnz)
+        ent = _edr_tables[key] = (torch.hann_window(win, dtype=torch.float64).to(dev), torch.from_numpy(melidx).to(dev),
+                                  torch.from_numpy(melw).to(dev), nnz)
+    return (ent[0], twiddles(MRSTFT_NTW, torch.float64, dev)) + ent[1:]
+
+
+class _EDR(torch.autograd.Function):
+    """the mel energy-decay-relief criterion, one node over the prediction: frame kernel, relief and final kernel forward
+    (keeping the prediction's band energies, the per-entry factors of dL/dE and 1 / D); prefix, frame kernel and overlap-add
+    backward"""
+
+    @staticmethod
+    def forward(ctx, y, t, nfft, hop, win, sample_rate, energy_norm):
+        dev = _require_gpu(y, t)
+        L = _lib.lib()
+        B, T, N = y.shape
+        w, tw, melidx, melw, nnz = _edr_consts(sample_rate, nfft, win, dev)
+        n = L.fl_edr_band_doubles(B, T, N, nfft, hop, win)
+        mel = torch.empty(2 * n, dtype=torch.float64, device=dev)
+        kept = torch.empty(n, dtype=torch.float64, device=dev) if ctx.needs_input_grad[0] else None
+        rowsum = torch.empty(2 * B * N, dtype=torch.float64, device=dev)
+        keep = torch.empty(L.fl_edr_keep_doubles(), dtype=torch.float64, device=dev)
+        loss = _scalar_loss(y.dtype, dev)
+        with kernel_timer.span("edr_fwd"):
+            _lib.check(_fn("fl_edr_fwd", y.dtype)(y.data_ptr(), *y.stride(), t.data_ptr(), *t.stride(), B, T, N, nfft, hop, win,
+                                                  w.data_ptr(), tw.data_ptr(), melidx.data_ptr(), melw.data_ptr(), nnz,
+                                                  int(energy_norm), torch.finfo(y.dtype).eps, mel.data_ptr(), _ptr(kept),
+                                                  rowsum.data_ptr(), keep.data_ptr(), loss.data_ptr(), _stream()), "edr_fwd")
+        if kept is not None:
+            ctx.save_for_backward(y, mel, kept, keep)
+            ctx.cfg = (nfft, hop, win, sample_rate)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        y, mel, kept, keep = ctx.saved_tensors
+        nfft, hop, win, sample_rate = ctx.cfg
+        L = _lib.lib()
+        B, T, N = y.shape
+        w, tw, melidx, melw, nnz = _edr_consts(sample_rate, nfft, win, y.device)
+        gmel = torch.empty_like(kept)
+        gframes = torch.empty(L.fl_edr_gframe_elems(B, T, N, nfft, hop, win), dtype=y.dtype, device=y.device)
+        gy = torch.empty((B, T, N), dtype=y.dtype, device=y.device)
+        g = _gloss_as(gloss, y.dtype)
+        with kernel_timer.span("edr_bwd"):
+            _lib.check(_fn("fl_edr_bwd", y.dtype)(y.data_ptr(), *y.stride(), B, T, N, nfft, hop, win, w.data_ptr(), tw.data_ptr(),
+                                                  melidx.data_ptr(), melw.data_ptr(), nnz, mel.data_ptr(), kept.data_ptr(),
+                                                  keep.data_ptr(), g.data_ptr(), gmel.data_ptr(), gframes.data_ptr(),
+                                                  gy.data_ptr(), _stream()), "edr_bwd")
+        return gy, None, None, None, None, None, None
+
+
+def edr_loss(y_pred: torch.Tensor, y_true: torch.Tensor, nfft: int = 1024, hop: int = 480, win: int = 960,
+             sample_rate: int = 48000, energy_norm: bool = False) -> torch.Tensor:
+    """The mel energy-decay-relief criterion of (B, T, N) signals (flamo_amd.optimize.edr_loss has the definition): of every
+    (batch, channel) column of prediction and target the power spectrogram -- periodic Hann window of ``win`` samples centred
+    in frames of ``nfft``, reflect padding -- projected on ``mel_basis(sample_rate, nfft)``, the backward integral over frames
+    of the squared band energies in dB (with ``energy_norm`` referred to its first frame), and sum |edr_t - edr_p| /
+    sum |edr_t|.  One autograd node over the prediction, six launches in all (three forward, three backward); the signals are
+    read through their strides, nothing is copied, nothing is read back.  The target takes no gradient.  Sizes:
+    ``edr_supported``."""
+    _require_gpu(y_pred, y_true)
+    if y_pred.dim() != 3 or y_pred.dtype not in (torch.float32, torch.float64) or y_pred.numel() == 0:
+        raise ValueError(f"edr_loss: a non-empty real float32 / float64 (B, T, N) signal, got {tuple(y_pred.shape)} {y_pred.dtype}")
+    if tuple(y_true.shape) != tuple(y_pred.shape) or y_true.dtype != y_pred.dtype:
+        raise ValueError(f"edr_loss: prediction {tuple(y_pred.shape)} {y_pred.dtype} and target {tuple(y_true.shape)} "
+                         f"{y_true.dtype} differ")
+    if y_true.requires_grad:
+        raise ValueError("edr_loss: the target takes no gradient here (detach it, or use optimize.edr_loss's torch lines)")
+    if not edr_supported(tuple(y_pred.shape), nfft, hop, win):
+        raise ValueError(f"edr_loss: frames (nfft, hop, win) = {(nfft, hop, win)!r} on T = {y_pred.shape[1]}: nfft a power of "
+                         f"two from 256 to 2048, 1 <= win <= nfft, hop >= 1, nfft / 2 < T <= 2^30 and fewer than 2^31 frames in all")
+    if not (isinstance(sample_rate, (int, float)) and math.isfinite(sample_rate) and sample_rate // 2 > EDR_FMIN):
+        raise ValueError(f"edr_loss: sample_rate must be a number with sample_rate // 2 > {EDR_FMIN:g} Hz, got {sample_rate!r}")
+    return _EDR.apply(y_pred, y_true, int(nfft), int(hop), int(win), sample_rate, bool(energy_norm))
+
+
 def mean_square(y: torch.Tensor) -> torch.Tensor:
     """(y ** 2).mean() of a real tensor in one streaming pass each way (forward: one read of y;
     backward: one read + one write), in whatever layout y is stored."""

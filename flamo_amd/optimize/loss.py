@@ -1,6 +1,7 @@
 """``mse_loss`` and ``sparsity_loss`` of the reference (flamo/optimize/loss.py:12-103) on the library's kernels -- the two
 criteria of the colorless-FDN training (examples/e8_colorless_fdn.py:137-138) -- and its broadband ``edc_loss``
-(loss.py:674-809) and ``AveragePower`` (loss.py:462-549), the criteria of a fit to a measured room impulse response.
+(loss.py:674-809), ``AveragePower`` (loss.py:462-549) and mel-band ``edr_loss`` (loss.py:553-670), the criteria of a fit to a
+measured room impulse response.
 
 The reference's training loop calls ``criterion(estimations, targets)`` (flamo/optimize/trainer.py:179-189); with
 ``flamo_amd.optimize.mse_loss`` in that list the loop runs unedited and the criterion costs one streaming pass over the
@@ -246,6 +247,103 @@ class MultiResoSTFT(nn.Module):
             lin = torch.mean(torch.abs(Mp - Mt))
             total = total + self.w_sc * sc + self.w_log_mag * log + self.w_lin_mag * lin
         return total / len(self.fft_sizes)
+
+
+class edr_loss(nn.Module):
+    """Energy decay relief criterion, flamo/optimize/loss.py:553-670 (Mezza et al., DAFx24): the frequency-dependent decay of
+    (B, T, N) signals on 64 mel bands.  Every (batch, channel) column is one row -- for N = 1 the reference's layout exactly;
+    for N > 1 the reference reshapes (B, T, N) to (B N, T) without a permute and mixes channels into time, which is not
+    reproduced here.  With ``win_length`` = int(0.020 sample_rate), hop = int(win_length (1 - overlap)), the periodic Hann
+    window centred in frames of ``nfft`` samples and reflect padding:
+
+        P   = |X|^2                                   the power spectrogram, (rows, nfft / 2 + 1, F), F = 1 + T // hop
+        m   = W P                                     W = ops.mel_basis(sample_rate, nfft): 64 bands from 20 Hz to sample_rate // 2
+        E   = sum_{f' >= f} m[f']^2                   the backward integral over frames
+        edr = 10 log10 E   (``energy_norm``: 10 log10 (E / E[0]))
+        loss = sum |edr_t - edr_p| / sum |edr_t|      over all rows, bands and frames at once
+
+    and where the TARGET's E is exactly 0 (its edr is -inf) both entries are replaced by finfo(dtype).eps: 0 to the numerator,
+    eps to the denominator, no gradient.  The reference forms P as sqrt(re^2 + im^2) ** 2 (nnAudio), the same value wherever
+    |X| > 0; |X|^2 taken directly has the gradient 0 at an exact zero.
+
+    Same constructor, defaults and attributes as the reference's class (plus ``win_length``, which it sets too), and its
+    methods but ``get_edr``, which there calls a ``filterbank`` method the class does not have.
+
+    Device float32 / float64 predictions against a gradient-free target of the same shape and dtype run on ``ops.edr_loss``
+    (three launches forward, three backward; the spectrograms are never stored); host tensors, other dtypes, a target that
+    takes a gradient and the frame lengths the kernels do not take run the torch lines of ``_torch_forward``."""
+
+    def __init__(self, nfft: int = 1024, overlap: float = 0.5, sample_rate: int = 48000, energy_norm: bool = False,
+                 device: str = "cpu", name: str = "EDR"):
+        super().__init__()
+        self.nfft = nfft
+        self.overlap = overlap
+        self.sample_rate = sample_rate
+        self.energy_norm = energy_norm
+        self.win_length = int(0.020 * self.sample_rate)
+        self.name = name
+        self.device = device
+
+    def hop_length(self):
+        return int(self.win_length * (1 - self.overlap))
+
+    def discard_last_n_percent(self, x, n_percent):
+        """x (B, T, N) without its last n_percent of samples"""
+        last_id = int(np.round((1 - n_percent / 100) * x.shape[1]))
+        return x[:, 0:last_id, :]
+
+    def schroeder_backward_int(self, x):
+        """(E, Z) of x (..., F, N): E[..., f, c] = sum_{f' >= f} x[..., f', c]^2 divided by Z, Z = its maximum over f
+        (``energy_norm``) or ones"""
+        out = torch.flip(torch.cumsum(torch.flip(x, dims=[-2]) ** 2, dim=-2), dims=[-2])
+        if self.energy_norm:
+            norm_vals = torch.max(out, dim=-2, keepdim=True)[0]
+        else:
+            norm_vals = torch.ones(out.shape, device=out.device, dtype=out.dtype)
+        return out / norm_vals, norm_vals
+
+    def mel_stft(self, x):
+        """the mel power spectrogram (rows, 64, F) of x (rows, T), in x's dtype"""
+        window = torch.hann_window(self.win_length, periodic=True, dtype=x.dtype, device=x.device)
+        X = torch.stft(x, self.nfft, self.hop_length(), self.win_length, window, center=True, pad_mode="reflect",
+                       return_complex=True)
+        W = ops.mel_basis(self.sample_rate, self.nfft, 64, 20.0, self.sample_rate // 2).to(device=x.device, dtype=x.dtype)
+        return torch.matmul(W, X.real ** 2 + X.imag ** 2)
+
+    def _on_kernels(self, y_pred, y_true):
+        return (torch.is_tensor(y_pred) and torch.is_tensor(y_true) and y_pred.is_cuda and y_true.is_cuda
+                and y_pred.dtype in (torch.float32, torch.float64) and y_true.dtype == y_pred.dtype
+                and not y_true.requires_grad and self.sample_rate // 2 > ops.EDR_FMIN
+                and ops.edr_supported(tuple(y_pred.shape), self.nfft, self.hop_length(), self.win_length))
+
+    def forward(self, y_pred, y_true):
+        if len(y_pred.shape) == 1:
+            y_pred = y_pred.unsqueeze(0).unsqueeze(-1)
+            y_true = y_true.unsqueeze(0).unsqueeze(-1)
+        assert (y_pred.shape == y_true.shape) & (len(y_true.shape) == 3), \
+            "y_pred and y_true must have the same shape (n_batch, n_samples, n_channels)"
+        if self._on_kernels(y_pred, y_true):
+            return ops.edr_loss(y_pred, y_true, self.nfft, self.hop_length(), self.win_length, self.sample_rate, self.energy_norm)
+        return self._torch_forward(y_pred, y_true)
+
+    def _torch_forward(self, y_pred, y_true):
+        """the definition in plain torch, on whatever device the tensors live"""
+        B, T, N = y_pred.shape
+        edr = []
+        for y in (y_pred, y_true):
+            m = self.mel_stft(y.permute(0, 2, 1).reshape(B * N, T))                      # (rows, 64, F)
+            E = torch.flip(torch.cumsum(torch.flip(m, dims=[-1]) ** 2, dim=-1), dims=[-1])
+            # (a silent band has E[0] = 0: it is divided by 1, stays 0 and is clipped below, not 0 / 0)
+            E0 = torch.where(E[..., :1] == 0, torch.ones_like(E[..., :1]), E[..., :1])
+            edr.append((E, E / E0 if self.energy_norm else E))
+        (Ep, xp), (Et, xt) = edr
+        clip = Et == 0
+        one = torch.ones_like(xt)
+        eps = torch.full_like(xt, torch.finfo(xt.dtype).eps)
+        # (the logarithm only ever sees the clipped entries as 1: no 0 * inf reaches the gradient)
+        edr_p = torch.where(clip, eps, 10 * torch.log10(torch.where(clip, one, xp)))
+        edr_t = torch.where(clip, eps, 10 * torch.log10(torch.where(clip, one, xt)))
+        return torch.sum(torch.abs(edr_t - edr_p)) / torch.sum(torch.abs(edr_t))
 
 
 class masked_mse_loss(nn.Module):
