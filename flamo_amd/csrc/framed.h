@@ -9,6 +9,17 @@
 // split from the packed one bin by bin; the way back is the adjoint of the split (unsplit), the inverse walk and the windowed
 // store, and an overlap-add that gathers per sample with the reflected margins folded back onto the samples they mirror.
 //
+// n_fft = 128 (P = 1, for melmss.hip) is the same walk with an empty first pass: 1 x 8 x 8, eight lanes busy in each radix-8
+// pass, A[128] with every value at twice its index.
+//
+// n_fft = 4096 (P = 32) does not fit one wavefront: 32 complex doubles per lane are 128 VGPRs before a radix-32's temporaries,
+// beside the 200 the P = 16 backward kernel already needs.  The WIDE walk below gives a frame to a workgroup of WIDE_NT = 256
+// threads (four wavefronts) instead: four passes, radix (P / 8) x 8 x 8 x 8, the first on values as they are loaded (two
+// butterflies per thread, never more than four values held), then 8 P radix-8 butterflies per pass, one per thread, with an
+// LDS exchange behind each -- one exchange more than the three-pass walk, the 8 values of one butterfly per thread, no scratch.
+// It also takes P = 16 (2 x 8 x 8 x 8, half the threads busy in the radix-8 passes), so that a caller can run 2048 and 4096
+// in one launch of one workgroup size.  split_bin, unsplit and hermitian_half serve both walks.
+//
 // Template parameters: T the signals' type, C the transform's (window, twiddles and LDS have it), NTW the length of the
 // caller's twiddle table, tw[j] = exp(-2 pi i j / NTW), a multiple of n_fft.
 //
@@ -37,6 +48,8 @@ struct Frame {
 };
 
 template <int P> struct Log2;
+template <> struct Log2<1> { static constexpr int v = 0; };
+template <> struct Log2<32> { static constexpr int v = 5; };
 template <> struct Log2<2> { static constexpr int v = 1; };
 template <> struct Log2<4> { static constexpr int v = 2; };
 template <> struct Log2<8> { static constexpr int v = 3; };
@@ -183,6 +196,85 @@ __device__ inline bool gather_sample(const T* __restrict__ g, long t, long Tn, i
     if (t >= 1 && t <= half) gather(half - t);                 // its image in the left margin
     if (t <= Tn - 2) gather(2 * (Tn - 1) - t + half);          // ... in the right margin (frames beyond the last hold none)
     return any;
+}
+
+// ---------------------------------------------------------------- the wide walk: one frame per workgroup of WIDE_NT threads
+constexpr int WIDE_NT = 256;
+
+// One radix-8 Stockham pass over the 64 P values in A, one butterfly per thread (8 P <= WIDE_NT of them); indices as in pass8.
+template <typename C, int P, int NTW, int NS, bool INV>
+__device__ inline void pass8_wide(cx<C>* A, const cx<C>* __restrict__ tw, int tid) {
+    constexpr int NBF = 8 * P, STEP = NTW / (8 * NS);
+    static_assert(NBF <= WIDE_NT, "one butterfly per thread");
+    cx<C> u[8];
+    const int jm = tid & (NS - 1);
+    if (tid < NBF) {
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            u[t] = A[zp<P>(tid + t * NBF)];
+            if (t > 0) {
+                const cx<C> w = tw[t * jm * STEP];
+                u[t] = mul_plain(u[t], INV ? conj(w) : w);
+            }
+        }
+        RegFFT<C, 8, INV>::run(u);
+    }
+    __syncthreads();
+    if (tid < NBF) {
+        const int base = (tid - jm) * 8 + jm;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) A[zp<P>(base + t * NS)] = u[t];
+    }
+    __syncthreads();
+}
+
+// Z[k] = sum_n z[n] exp(-+2 pi i k n / (64 P)) by WIDE_NT threads, P = 16 or 32.  In: z(n), a callable every thread may ask
+// for any n < 64 P (it must not read A).  Out: A[zp(k)] = Z[k], visible to every thread.  The caller has a barrier between
+// its last read of A and this call.
+template <typename C, int P, int NTW, bool INV, class Z>
+__device__ inline void fft_wide(Z&& z, cx<C>* A, const cx<C>* __restrict__ tw, int tid) {
+    static_assert(P == 16 || P == 32, "the wide walk is (P / 8) x 8 x 8 x 8");
+    static_assert(NTW % (128 * P) == 0, "the twiddle table must hold the n_fft-th roots");
+    constexpr int R0 = P / 8, NB0 = 64 * P / R0;      // 512 first-pass butterflies: z[j + 512 t], t < R0, to A[j R0 + t]
+    for (int j = tid; j < NB0; j += WIDE_NT) {
+        cx<C> v[R0];
+#pragma unroll
+        for (int t = 0; t < R0; ++t) v[t] = z(j + t * NB0);
+        RegFFT<C, R0, INV>::run(v);
+#pragma unroll
+        for (int t = 0; t < R0; ++t) A[zp<P>(j * R0 + t)] = v[t];
+    }
+    __syncthreads();
+    pass8_wide<C, P, NTW, R0, INV>(A, tw, tid);
+    pass8_wide<C, P, NTW, 8 * R0, INV>(A, tw, tid);
+    pass8_wide<C, P, NTW, 64 * R0, INV>(A, tw, tid);
+}
+
+// frame_transform by WIDE_NT threads
+template <typename T, typename C, int P, int NTW>
+__device__ inline void frame_transform_wide(const T* __restrict__ y, long stride, long Tn, long f, const Frame& q, const C* __restrict__ w,
+                                            const cx<C>* __restrict__ tw, cx<C>* A, int tid) {
+    const long j0 = f * q.hop;
+    fft_wide<C, P, NTW, false>(
+        [&](int m) {
+            const int n = 2 * m - q.lpad;      // place under the window of the even sample
+            C re = 0, im = 0;
+            if (n >= 0 && n < q.win) re = (C)padded(y, stride, Tn, j0 + n + q.lpad, 64 * P) * w[n];
+            if (n + 1 >= 0 && n + 1 < q.win) im = (C)padded(y, stride, Tn, j0 + n + 1 + q.lpad, 64 * P) * w[n + 1];
+            return cx<C>(re, im);
+        },
+        A, tw, tid);
+}
+
+// store_frame_grad by WIDE_NT threads
+template <typename T, typename C, int P>
+__device__ inline void store_frame_grad_wide(const cx<C>* A, const C* __restrict__ w, const Frame& q, T* __restrict__ out, int tid) {
+    for (int m = tid; m < 64 * P; m += WIDE_NT) {
+        const int n = 2 * m - q.lpad;
+        const cx<C> z = A[zp<P>(m)];
+        if (n >= 0 && n < q.win) out[n] = (T)(z.x * w[n]);
+        if (n + 1 >= 0 && n + 1 < q.win) out[n + 1] = (T)(z.y * w[n + 1]);
+    }
 }
 
 }  // namespace framed

@@ -3244,6 +3244,179 @@ def edr_loss(y_pred: torch.Tensor, y_true: torch.Tensor, nfft: int = 1024, hop: 
     return _EDR.apply(y_pred, y_true, int(nfft), int(hop), int(win), sample_rate, bool(energy_norm))
 
 
+MELMSS_MAX_RES, MELMSS_NFFTS, MELMSS_NTW = 8, (128, 256, 512, 1024, 2048, 4096), 4096      # what csrc/melmss.hip takes
+MELMSS_NORMS = {"fro": 2, 2: 2, 1: 1}                                                      # ``p`` -> the kernels' norm
+_melmss_host_tables = {}
+_melmss_tables = {}
+
+
+def _melmss_frames(nfft, overlap):
+    """((n_fft, hop), ...) with hop = int(n_fft (1 - overlap)) as a tuple of int pairs, or None when ``nfft`` is not a
+    sequence of integers or ``overlap`` not a number"""
+    try:
+        ns = tuple(int(n) for n in nfft)
+        same = len(ns) == len(tuple(nfft)) and all(a == b for a, b in zip(ns, nfft))
+        hops = tuple(int(n * (1 - overlap)) for n in ns)
+    except (TypeError, ValueError, OverflowError):
+        return None
+    if not same or any(abs(v) >= 1 << 31 for v in ns + hops):
+        return None
+    return tuple(zip(ns, hops))
+
+
+def _melmss_norm(p):
+    try:
+        return MELMSS_NORMS.get(p)
+    except TypeError:
+        return None
+
+
+def _melmss_host(sample_rate, nffts):
+    """per resolution the (melidx, melw, nnz) of ``_edr_mel_tables`` for mel_basis(sample_rate, n_fft, n_fft // 8, 0,
+    sample_rate // 2), cached; a ValueError when a bin lies in more than two, or in two not consecutive, bands"""
+    key = (sample_rate, nffts)
+    ent = _melmss_host_tables.get(key)
+    if ent is None:
+        ent = _melmss_host_tables[key] = tuple(
+            _edr_mel_tables(mel_basis(sample_rate, n, n // 8, 0.0, sample_rate // 2).numpy()) for n in nffts)
+    return ent
+
+
+def mel_mss_supported(shape, nfft=MELMSS_NFFTS, overlap=0.75, sample_rate=48000, p="fro") -> bool:
+    """whether ``mel_mss_loss`` takes (B, T, N) signals under these resolutions: 1 to 8 of them, n_fft a power of two from 128
+    to 4096, hop = int(n_fft (1 - overlap)) >= 1, n_fft / 2 < T <= 2^30, fewer than 2^31 frames and at most 2^38 samples in
+    all, ``p`` in "fro", 2, 1, and a sample rate whose mel bases keep every bin in at most two consecutive bands"""
+    frames = _melmss_frames(nfft, overlap)
+    try:
+        dims = tuple(int(s) for s in shape)
+        same = all(a == b for a, b in zip(dims, tuple(shape)))
+    except (TypeError, ValueError):
+        return False
+    if frames is None or not same or len(dims) != 3 or max(map(abs, dims)) >= 1 << 62 or not 1 <= len(frames) <= MELMSS_MAX_RES:
+        return False
+    if _melmss_norm(p) is None:
+        return False
+    if not (isinstance(sample_rate, (int, float)) and math.isfinite(sample_rate) and sample_rate // 2 > 0):
+        return False
+    flat = [v for n, hop in frames for v in (n, hop, 0)]
+    # the library's own support query: one statement of the sizes
+    if _lib.lib().fl_melmss_frames(*dims, len(frames), (ctypes.c_int * len(flat))(*flat)) < 0:
+        return False
+    try:
+        _melmss_host(sample_rate, tuple(n for n, _ in frames))
+    except ValueError:
+        return False
+    return True
+
+
+def _melmss_consts(frames, sample_rate, dev: torch.device):
+    """(windows, twiddles, melidx, melw, the resolutions as a host int array of (n_fft, hop, nnz)) cached per (resolutions,
+    sample_rate, device): the periodic Hann windows and the mel tables of the resolutions, one behind the other, made on the
+    host in float64 under either precision of the signals"""
+    key = (frames, sample_rate, dev.index if dev.index is not None else torch.cuda.current_device())
+    ent = _melmss_tables.get(key)
+    if ent is None:
+        host = _melmss_host(sample_rate, tuple(n for n, _ in frames))
+        flat = [v for (n, hop), (_, _, nnz) in zip(frames, host) for v in (n, hop, nnz)]
+        cres = (ctypes.c_int * len(flat))(*flat)
+        melidx = np.concatenate([h[0] for h in host])
+        melw = np.concatenate([h[1] for h in host])
+        L = _lib.lib()
+        assert melidx.size == L.fl_melmss_mel_ints(len(frames), cres) and melw.size == L.fl_melmss_mel_doubles(len(frames), cres)
+        w = torch.cat([torch.hann_window(n, dtype=torch.float64) for n, _ in frames])
+        ent = _melmss_tables[key] = (w.to(dev), torch.from_numpy(melidx).to(dev), torch.from_numpy(melw).to(dev), cres)
+    return (ent[0], twiddles(MELMSS_NTW, torch.float64, dev)) + ent[1:]
+
+
+class _MelMSS(torch.autograd.Function):
+    """the mel multi-scale spectral criterion, one node over the prediction: the frame kernels of the two size classes,
+    combine and final kernel forward (keeping the five sums and the two factors of dL/dm_p per resolution); the frame kernels
+    and the overlap-add backward"""
+
+    @staticmethod
+    def forward(ctx, y, t, frames, sample_rate, opts):
+        dev = _require_gpu(y, t)
+        L = _lib.lib()
+        B, T, N = y.shape
+        w, tw, melidx, melw, cres = _melmss_consts(frames, sample_rate, dev)
+        R = len(frames)
+        norm, log_term, alpha, apply_mask, threshold, ne = opts
+        partial = torch.empty(5 * L.fl_melmss_frames(B, T, N, R, cres), dtype=torch.float64, device=dev)
+        keep = torch.empty(L.fl_melmss_keep_doubles(), dtype=torch.float64, device=dev)
+        loss = _scalar_loss(y.dtype, dev)
+        with kernel_timer.span("melmss_fwd"):
+            _lib.check(_fn("fl_melmss_fwd", y.dtype)(y.data_ptr(), *y.stride(), t.data_ptr(), *t.stride(), B, T, N, R, cres,
+                                                     w.data_ptr(), tw.data_ptr(), melidx.data_ptr(), melw.data_ptr(), norm,
+                                                     log_term, alpha, apply_mask, threshold, ne, partial.data_ptr(),
+                                                     keep.data_ptr(), loss.data_ptr(), _stream()), "melmss_fwd")
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(y, t, keep)
+            ctx.cfg = (frames, sample_rate, opts)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        y, t, keep = ctx.saved_tensors
+        frames, sample_rate, opts = ctx.cfg
+        L = _lib.lib()
+        B, T, N = y.shape
+        w, tw, melidx, melw, cres = _melmss_consts(frames, sample_rate, y.device)
+        R = len(frames)
+        norm, log_term, _, apply_mask, threshold, ne = opts
+        gframes = torch.empty(L.fl_melmss_gframe_elems(B, T, N, R, cres), dtype=y.dtype, device=y.device)
+        gy = torch.empty((B, T, N), dtype=y.dtype, device=y.device)
+        g = _gloss_as(gloss, y.dtype)
+        with kernel_timer.span("melmss_bwd"):
+            _lib.check(_fn("fl_melmss_bwd", y.dtype)(y.data_ptr(), *y.stride(), t.data_ptr(), *t.stride(), B, T, N, R, cres,
+                                                     w.data_ptr(), tw.data_ptr(), melidx.data_ptr(), melw.data_ptr(), norm,
+                                                     log_term, apply_mask, threshold, ne, keep.data_ptr(), g.data_ptr(),
+                                                     gframes.data_ptr(), gy.data_ptr(), _stream()), "melmss_bwd")
+        return gy, None, None, None, None
+
+
+def mel_mss_loss(y_pred: torch.Tensor, y_true: torch.Tensor, nfft=MELMSS_NFFTS, overlap: float = 0.75, sample_rate: int = 48000,
+                 p="fro", log_term: bool = False, alpha: float = 1.0, apply_mask: bool = False, threshold: float = 5.0,
+                 noise_energy=None) -> torch.Tensor:
+    """The mel multi-scale spectral criterion of (B, T, N) signals (flamo_amd.optimize.mel_mss_loss has the definition): for
+    every n_fft of ``nfft`` the power spectrogram of every (batch, channel) column of prediction and target -- periodic Hann
+    window of n_fft samples, hop int(n_fft (1 - overlap)), reflect padding -- projected on ``mel_basis(sample_rate, n_fft,
+    n_fft // 8, 0, sample_rate // 2)``, and |(m_t - m_p) mask|_p / Nn, with ``log_term`` plus ``alpha`` times the same of the
+    logarithms; the sum over the resolutions.  ``apply_mask`` drops the entries whose target stands less than ``threshold`` dB
+    over ``noise_energy``, a number > 0 here (optimize.mel_mss_loss derives it when it is None).  One autograd node over the
+    prediction, at most seven launches in all (four forward, three backward) whatever the number of resolutions; the signals
+    are read through their strides, nothing is copied, nothing is read back.  The target takes no gradient.  Sizes:
+    ``mel_mss_supported``."""
+    _require_gpu(y_pred, y_true)
+    if y_pred.dim() != 3 or y_pred.dtype not in (torch.float32, torch.float64) or y_pred.numel() == 0:
+        raise ValueError(f"mel_mss_loss: a non-empty real float32 / float64 (B, T, N) signal, got {tuple(y_pred.shape)} {y_pred.dtype}")
+    if tuple(y_true.shape) != tuple(y_pred.shape) or y_true.dtype != y_pred.dtype:
+        raise ValueError(f"mel_mss_loss: prediction {tuple(y_pred.shape)} {y_pred.dtype} and target {tuple(y_true.shape)} "
+                         f"{y_true.dtype} differ")
+    if y_true.requires_grad:
+        raise ValueError("mel_mss_loss: the target takes no gradient here (detach it, or use optimize.mel_mss_loss's torch lines)")
+    norm = _melmss_norm(p)
+    if norm is None:
+        raise ValueError(f"mel_mss_loss: p must be 'fro', 2 or 1, got {p!r}")
+    if not (isinstance(sample_rate, (int, float)) and math.isfinite(sample_rate) and sample_rate // 2 > 0):
+        raise ValueError(f"mel_mss_loss: sample_rate must be a number with sample_rate // 2 > 0, got {sample_rate!r}")
+    frames = _melmss_frames(nfft, overlap)
+    if frames is None or not mel_mss_supported(tuple(y_pred.shape), nfft, overlap, sample_rate, p):
+        raise ValueError(f"mel_mss_loss: resolutions nfft = {nfft!r}, overlap = {overlap!r} on T = {y_pred.shape[1]}: 1 to "
+                         f"{MELMSS_MAX_RES} n_fft, each a power of two from 128 to 4096 with hop = int(n_fft (1 - overlap)) >= 1, "
+                         f"n_fft / 2 < T <= 2^30, fewer than 2^31 frames in all, and mel bases with every bin in at most two "
+                         f"consecutive bands")
+    try:
+        alpha, threshold = float(alpha), float(threshold)
+        ne = 1.0 if not apply_mask else float(noise_energy)
+    except (TypeError, ValueError):
+        ne = float("nan")
+    if not ne > 0.0:
+        raise ValueError(f"mel_mss_loss: apply_mask needs a noise_energy > 0 (a number: the class derives it from the target "
+                         f"when it is None), got {noise_energy!r}")
+    opts = (norm, int(bool(log_term)), alpha, int(bool(apply_mask)), threshold, ne)
+    return _MelMSS.apply(y_pred, y_true, frames, sample_rate, opts)
+
+
 def mean_square(y: torch.Tensor) -> torch.Tensor:
     """(y ** 2).mean() of a real tensor in one streaming pass each way (forward: one read of y;
     backward: one read + one write), in whatever layout y is stored."""

@@ -1,11 +1,13 @@
 """``mse_loss`` and ``sparsity_loss`` of the reference (flamo/optimize/loss.py:12-103) on the library's kernels -- the two
 criteria of the colorless-FDN training (examples/e8_colorless_fdn.py:137-138) -- and its broadband ``edc_loss``
 (loss.py:674-809), ``AveragePower`` (loss.py:462-549) and mel-band ``edr_loss`` (loss.py:553-670), the criteria of a fit to a
-measured room impulse response.
+measured room impulse response, and ``mel_mss_loss`` (loss.py:169-296), the criterion of its loss profiles.
 
 The reference's training loop calls ``criterion(estimations, targets)`` (flamo/optimize/trainer.py:179-189); with
 ``flamo_amd.optimize.mse_loss`` in that list the loop runs unedited and the criterion costs one streaming pass over the
 prediction each way (``ops.mse``) instead of torch's sum / sub / pow / mean kernels and their backward."""
+import math
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -344,6 +346,120 @@ class edr_loss(nn.Module):
         edr_p = torch.where(clip, eps, 10 * torch.log10(torch.where(clip, one, xp)))
         edr_t = torch.where(clip, eps, 10 * torch.log10(torch.where(clip, one, xt)))
         return torch.sum(torch.abs(edr_t - edr_p)) / torch.sum(torch.abs(edr_t))
+
+
+class mel_mss_loss(nn.Module):
+    """Multi-scale spectral criterion on the mel scale, flamo/optimize/loss.py:169-296: the criterion of the reference's loss
+    profiles (examples/e9_loss_profile.py).  Every (batch, channel) column of the (B, T, N) signals is one row -- for N = 1 the
+    reference's layout exactly; for N > 1 the reference reshapes (B, T, N) to (B N, T) without a permute and mixes channels
+    into time, which is not reproduced here (as in ``edr_loss``).  For every n_fft of ``nfft``, with hop = int(n_fft (1 -
+    overlap)), the periodic Hann window of n_fft samples and reflect padding (nnAudio's MelSpectrogram at its defaults):
+
+        P    = |X|^2                                  the power spectrogram, (rows, n_fft / 2 + 1, F), F = 1 + T // hop
+        m    = W P                                    W = ops.mel_basis(sample_rate, n_fft, n_fft // 8, 0, sample_rate // 2)
+        mask = 1, Nn = numel(m_t)                     or, with ``apply_mask``, with ne = ``noise_energy``:
+               SNR = 10 log10(max(m_t^2, 1.01 ne) - ne) - 10 log10(ne),  mask = 0 where SNR < threshold,  Nn = sum mask
+        loss += |(m_t - m_p) mask|_p / Nn
+        loss += alpha |(log m_t - log m_p) mask|_p / Nn                                                   (``log_term``)
+
+    summed (not averaged) over the resolutions; p = "fro" is the square root of the sum of squares over everything at once.
+    Nothing is clamped: a band that is exactly 0 in either signal makes the log term non-finite, as in the reference.
+    ``energy_norm`` divides both signals by their 2-norm over the whole tensor first.
+
+    ``noise_energy`` None (or 0) is replaced at the first resolution of the first masked call by
+    mean(m_t[:, :, -int(0.01 sample_rate / hop)]^2) -- frame 0 when that integer is 0 -- and then KEPT on the module, as a
+    number, for every later resolution and call: the reference's statefulness.  Deriving it reads one number back from the
+    device, once; pass ``noise_energy`` when the step is captured in a graph.
+
+    Same constructor, defaults and attributes as the reference's class.  Device float32 / float64 predictions against a
+    gradient-free target of the same shape and dtype run on ``ops.mel_mss_loss`` (at most four launches forward and three
+    backward for all resolutions; the mel spectrograms are never stored); host tensors, other dtypes, a target that takes a
+    gradient, other ``p`` and the resolutions the kernels do not take run the torch lines of ``_torch_forward``."""
+
+    def __init__(self, nfft=[128, 256, 512, 1024, 2048, 4096], overlap: float = 0.75, sample_rate: int = 48000,
+                 energy_norm: bool = False, device="cpu", name: str = "MelMSS", apply_mask: bool = False, threshold: float = 5,
+                 p="fro", log_term: bool = False, alpha: float = 1.0, noise_energy=None):
+        super().__init__()
+        self.nfft = nfft
+        self.overlap = overlap
+        self.sample_rate = sample_rate
+        self.energy_norm = energy_norm
+        self.name = name
+        self.device = device
+        self.apply_mask = apply_mask
+        self.threshold = threshold
+        self.p = p
+        self.log_term = log_term
+        self.alpha = alpha
+        self.noise_energy = noise_energy
+
+    def hop_length(self, nfft):
+        return int(nfft * (1 - self.overlap))
+
+    def mel_stft(self, x, nfft):
+        """the mel power spectrogram (rows, nfft // 8, F) of x (rows, T), in x's dtype"""
+        window = torch.hann_window(nfft, periodic=True, dtype=x.dtype, device=x.device)
+        X = torch.stft(x, nfft, self.hop_length(nfft), nfft, window, center=True, pad_mode="reflect", return_complex=True)
+        W = ops.mel_basis(self.sample_rate, nfft, nfft // 8, 0.0, self.sample_rate // 2).to(device=x.device, dtype=x.dtype)
+        return torch.matmul(W, X.real ** 2 + X.imag ** 2)
+
+    def _noise(self, m_true, nfft):
+        """``noise_energy``, derived from the target's mel spectrogram at this resolution when there is none yet, and kept"""
+        if not self.noise_energy:
+            frame = -int(0.01 * self.sample_rate / self.hop_length(nfft))
+            self.noise_energy = float(torch.mean(m_true.detach()[:, :, frame] ** 2))
+        return float(self.noise_energy)
+
+    @staticmethod
+    def _rows(y):
+        B, T, N = y.shape
+        return y.permute(0, 2, 1).reshape(B * N, T)
+
+    def _on_kernels(self, y_pred, y_true):
+        return (torch.is_tensor(y_pred) and torch.is_tensor(y_true) and y_pred.is_cuda and y_true.is_cuda
+                and y_pred.dtype in (torch.float32, torch.float64) and y_true.dtype == y_pred.dtype
+                and not y_true.requires_grad
+                and ops.mel_mss_supported(tuple(y_pred.shape), self.nfft, self.overlap, self.sample_rate, self.p))
+
+    def forward(self, y_pred, y_true):
+        if len(y_pred.shape) == 1:
+            y_pred = y_pred.unsqueeze(0).unsqueeze(-1)
+            y_true = y_true.unsqueeze(0).unsqueeze(-1)
+        assert (y_pred.shape == y_true.shape) & (len(y_true.shape) == 3), \
+            "y_pred and y_true must have the same shape (n_batch, n_samples, n_channels)"
+        if not self._on_kernels(y_pred, y_true):
+            return self._torch_forward(y_pred, y_true)
+        if self.energy_norm:
+            y_pred = y_pred / torch.norm(y_pred, p=2)
+            y_true = y_true / torch.norm(y_true, p=2)
+        ne = None
+        if self.apply_mask:
+            first = self.nfft[0]
+            ne = self._noise(self.mel_stft(self._rows(y_true), first), first) if not self.noise_energy else float(self.noise_energy)
+        return ops.mel_mss_loss(y_pred, y_true, self.nfft, self.overlap, self.sample_rate, self.p, self.log_term, self.alpha,
+                                self.apply_mask, self.threshold, ne)
+
+    def _torch_forward(self, y_pred, y_true):
+        """the definition in plain torch, on whatever device the tensors live"""
+        if self.energy_norm:
+            y_pred = y_pred / torch.norm(y_pred, p=2)
+            y_true = y_true / torch.norm(y_true, p=2)
+        rows_p, rows_t = self._rows(y_pred), self._rows(y_true)
+        loss = 0
+        for nfft in self.nfft:
+            m_p, m_t = self.mel_stft(rows_p, nfft), self.mel_stft(rows_t, nfft)
+            mask = torch.ones_like(m_t)
+            if self.apply_mask:
+                ne = self._noise(m_t, nfft)
+                snr = 10 * torch.log10(torch.clamp(m_t ** 2, min=ne * 1.01) - ne) - 10 * math.log10(ne)
+                mask[snr < self.threshold] = 0
+                n = torch.sum(mask)
+            else:
+                n = torch.numel(m_t)
+            loss = loss + torch.norm((m_t - m_p) * mask, p=self.p) / n
+            if self.log_term:
+                loss = loss + self.alpha * torch.norm((torch.log(m_t) - torch.log(m_p)) * mask, p=self.p) / n
+        return loss
 
 
 class masked_mse_loss(nn.Module):
