@@ -2877,6 +2877,165 @@ def edc_loss(y_pred: torch.Tensor, y_true: torch.Tensor, energy_norm: bool = Fal
     return _EDCLoss.apply(y_pred, t, bool(energy_norm), bool(convergence), bool(clip))
 
 
+FILTERBANK_MAX_BANDS, FILTERBANK_MAX_ROOTS = 34, 16      # what csrc/filterbank.hip takes: bands, zeros or poles of a band
+
+
+def filterbank_supported(bank) -> bool:
+    """whether the band-split kernels take this ``auxiliary.filterbank.FilterBank``: 1 to 34 bands of at most 16 zeros and 16
+    poles each (Butterworth band-passes up to order 8) -- the library's own support query"""
+    _, K, most, _ = bank.band_constants()
+    return bool(_lib.lib().fl_filterbank_supports(int(K), int(most)))
+
+
+def _filterbank_consts(bank, dev: torch.device):
+    """(records on the device, K): the bands' float64 records (include/flamo_hip_filterbank.h), uploaded once per (device, state
+    of the bank) and kept on the bank, whose setters drop them.  Never uploaded during a graph capture: a copy from pageable
+    host memory cannot be captured, so the bank has to have run on the device before."""
+    state, K, _, rec = bank.band_constants()
+    key = dev.index if dev.index is not None else torch.cuda.current_device()
+    ent = bank._device_consts.get(key)
+    if ent is None or ent[0] != state:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("filterbank: the bank's constants are not on the device yet and nothing is uploaded during a graph "
+                               "capture -- run the bank once on this device before capturing")
+        assert rec.size == _lib.lib().fl_filterbank_const_elems(K)
+        ent = bank._device_consts[key] = (state, torch.from_numpy(rec).to(dev))
+    return ent[1], K
+
+
+def _irfft_vjp(gy: torch.Tensor, nfft: int) -> torch.Tensor:
+    """the cotangent of X under y = irfft(X, nfft): _Irfft's backward launch, or autograd through the chirp-z route"""
+    if fft_plan_ok(nfft, gy.dtype):
+        return _rfft_any(gy, nfft, 1.0 / nfft, 0.0, 1)
+    with torch.enable_grad():      # (linear: the cotangent does not depend on where the graph is recorded)
+        X = torch.zeros((gy.shape[0], nfft // 2 + 1, *gy.shape[2:]), dtype=_cdtype(gy.dtype), device=gy.device).requires_grad_(True)
+        (g,) = torch.autograd.grad(_irfft_chirp(X, nfft, 1.0 / nfft, 0.0), [X], gy)
+    return g
+
+
+def _rfft_vjp(gX: torch.Tensor, nfft: int) -> torch.Tensor:
+    """the cotangent of x (nfft samples) under X = rfft(x, nfft): _Rfft's backward launch, or autograd through the chirp-z route"""
+    real = _rdtype(gX)
+    if fft_plan_ok(nfft, real):
+        return _irfft_launch(to_planar(gX), nfft, nfft, nfft, 1.0, 0.0, 1)
+    with torch.enable_grad():
+        x = torch.zeros((gX.shape[0], nfft, *gX.shape[2:]), dtype=real, device=gX.device).requires_grad_(True)
+        (g,) = torch.autograd.grad(_rfft_chirp(x, nfft, 1.0, 0.0), [x], gX)
+    return g
+
+
+class _FilterBank(torch.autograd.Function):
+    """the filter bank, one node over the signal: rfft at length T, the band split (one launch), irfft at length 2 (T // 2);
+    backward the three adjoints in turn.  Linear: nothing but the sizes is kept."""
+
+    @staticmethod
+    def forward(ctx, x, bank):
+        dev = _require_gpu(x)
+        consts, K = _filterbank_consts(bank, dev)
+        B, T, N = x.shape
+        M, real = T // 2 + 1, x.dtype
+        Tp = 2 * (T // 2)
+        # (the launches of _Rfft / _Irfft themselves where the length has a plan: no node inside this one)
+        X = _rfft_any(x, T, 1.0, 0.0, 0) if fft_plan_ok(T, real) else to_planar(_rfft_chirp(x, T, 1.0, 0.0))      # memory (B, N, pitch)
+        Y = _empty_rows((B, N, K), M, _cdtype(real), dev)              # memory (B, N, K, pitch): what the inverse transform reads
+        with kernel_timer.span("filterbank_fwd"):
+            _lib.check(_fn("fl_filterbank_fwd", real)(X.data_ptr(), _lead_pitch(X.movedim(1, -1)), B * N, M, consts.data_ptr(), K,
+                                                     Y.data_ptr(), _pitch(M), _stream()), "filterbank_fwd")
+        ctx.cfg = (bank, T)
+        Yv = Y.movedim(-1, 1)
+        if fft_plan_ok(Tp, real):
+            return _irfft_launch(Yv, Tp, Tp, Tp, 1.0 / Tp, 0.0, 0)     # (B, T', N, K), a view of signal-planar memory
+        return _irfft_chirp(Yv, Tp, 1.0 / Tp, 0.0)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        bank, T = ctx.cfg
+        B, Tp, N, K = gy.shape
+        M, real, dev = T // 2 + 1, gy.dtype, gy.device
+        consts, _ = _filterbank_consts(bank, dev)
+        gY = to_planar(_irfft_vjp(gy, Tp).resolve_conj())              # memory (B, N, K, pitch)
+        gX = _empty_rows((B, N), M, _cdtype(real), dev)
+        with kernel_timer.span("filterbank_bwd"):
+            _lib.check(_fn("fl_filterbank_bwd", real)(gY.data_ptr(), _lead_pitch(gY.movedim(1, -1)), B * N, M, consts.data_ptr(), K,
+                                                     gX.data_ptr(), _pitch(M), _stream()), "filterbank_bwd")
+        return _rfft_vjp(gX.movedim(-1, 1), T), None
+
+
+def filterbank(x: torch.Tensor, bank) -> torch.Tensor:
+    """``auxiliary.filterbank.FilterBank`` on a device float32 / float64 signal (B, T, N): (B, T', N, K) with T' = 2 (T // 2),
+    the K band signals last -- irfft(H_j(w_k) rfft(x)) with the responses on the grid w_k = pi k / (T // 2 + 1), a circular
+    convolution.  One autograd node over ``x``: the library's real transforms (``rfft`` at T, ``irfft`` at T', the chirp-z route
+    where a length has no plan) around ONE band-split launch each way (csrc/filterbank.hip), which evaluates the responses from
+    the bands' zeros and poles where it needs them -- no (K, M) response tensor is ever written.  The split reads what the
+    forward transform writes and writes what the inverse one reads (signal-planar, bins contiguous): nothing is transposed, and
+    the result is the (B, T', N, K) view of planar memory that ``edc_loss`` takes as it is (``.flatten(2)`` is a view too).
+    1 to 34 bands of at most 16 poles; anything else is a ValueError (``filterbank_supported``)."""
+    if not (torch.is_tensor(x) and x.is_cuda):
+        raise ValueError("filterbank: a tensor on a ROCm device (FilterBank's torch lines take host tensors)")
+    if x.dim() != 3 or x.dtype not in (torch.float32, torch.float64) or x.numel() == 0:
+        raise ValueError(f"filterbank: a non-empty real float32 / float64 (B, T, N) signal, got {tuple(x.shape)} {x.dtype}")
+    if x.shape[1] < 2 or x.shape[1] > 1 << 30:
+        raise ValueError(f"filterbank: 2 <= T <= 2^30, got T = {x.shape[1]}")
+    _, K, most, _ = bank.band_constants()
+    if not filterbank_supported(bank):
+        raise ValueError(f"filterbank: 1 to {FILTERBANK_MAX_BANDS} bands of at most {FILTERBANK_MAX_ROOTS} zeros and poles each "
+                         f"(orders up to 8), got {K} bands with up to {most}")
+    if x.shape[0] * x.shape[2] * K >= 1 << 31 or x.shape[0] * x.shape[2] > 262140:
+        raise ValueError(f"filterbank: too many signals ({x.shape[0] * x.shape[2]} of {K} bands)")
+    return _FilterBank.apply(x, bank)
+
+
+class _SubbandEDC(torch.autograd.Function):
+    """the subband energy-decay-curve criterion, one node over the prediction: the _FilterBank and _EDCLoss nodes recorded
+    inside, on float64 copies of float32 signals"""
+
+    @staticmethod
+    def forward(ctx, y, t, bank, energy_norm, convergence, clip):
+        need = ctx.needs_input_grad[0]
+        with torch.enable_grad() if need else torch.no_grad():
+            yw = y.detach().to(torch.float64)
+            if need:
+                yw.requires_grad_(True)
+            loss = edc_loss(filterbank(yw, bank).flatten(2), filterbank(t.to(torch.float64), bank).flatten(2),
+                            energy_norm=energy_norm, convergence=convergence, clip=clip)
+        if need:
+            ctx.inner = (yw, loss)
+        return loss.detach().to(y.dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gloss):
+        yw, loss = ctx.inner
+        (g,) = torch.autograd.grad(loss, [yw], gloss.to(loss.dtype), retain_graph=True)
+        return g.to(gloss.dtype), None, None, None, None, None
+
+
+def subband_edc_loss(y_pred: torch.Tensor, y_true: torch.Tensor, bank, energy_norm: bool = False, convergence: bool = False,
+                     clip: bool = False) -> torch.Tensor:
+    """``edc_loss`` of the band signals of the full signals: edc_loss(filterbank(y_pred).flatten(2), filterbank(y_true).flatten(2))
+    -- every (channel, band) pair is a column of the broadband criterion, whose own discard of the last 0.5 % removes the end
+    of the band signals.  ``filterbank`` followed by the unchanged fl_edc_* kernels, one autograd node over the prediction; the
+    target takes no gradient.
+
+    float32 signals are widened once and carried in float64 from the transform to the loss (the loss and the gradient come
+    back in float32).  The criterion reads every band signal down to the end of its decay, 60 to 110 dB under its peak, and
+    divides by the energy that is left there; a float32 real transform rounds at 6e-8 of the PEAK, and its split step mirrors
+    that rounding from the head of a response into its tail, where it is 1e-3 of a sample.  Measured on (2, 960, 3) decaying
+    noise with the float32 transforms: gradient 5.1e-3 (l2) from the float64 statement, where the float32 torch lines stand at
+    3.7e-4; the float32 band split itself is as exact as they are (``filterbank`` in float32: 1.8e-7 on the band signals)."""
+    t = y_true.detach()
+    if not (torch.is_tensor(y_pred) and torch.is_tensor(t)) or tuple(t.shape) != tuple(y_pred.shape) or t.dtype != y_pred.dtype:
+        raise ValueError(f"subband_edc_loss: prediction {tuple(y_pred.shape)} {y_pred.dtype} and target {tuple(t.shape)} {t.dtype} differ")
+    if not (y_pred.is_cuda and t.is_cuda):
+        raise ValueError("subband_edc_loss: tensors on a ROCm device (the class's torch lines take host tensors)")
+    if y_pred.dim() != 3 or y_pred.dtype not in (torch.float32, torch.float64) or y_pred.numel() == 0:
+        raise ValueError(f"subband_edc_loss: a non-empty real float32 / float64 (B, T, N) signal, got {tuple(y_pred.shape)} {y_pred.dtype}")
+    if not filterbank_supported(bank):
+        raise ValueError(f"subband_edc_loss: 1 to {FILTERBANK_MAX_BANDS} bands of at most {FILTERBANK_MAX_ROOTS} zeros and poles each")
+    return _SubbandEDC.apply(y_pred, t, bank, bool(energy_norm), bool(convergence), bool(clip))
+
+
 AVGPOW_NFFT, AVGPOW_HOP, AVGPOW_WIN = 1024, 256, 64      # frame length, hop and smoothing window of the reference's class
 AVGPOW_MIN_T = AVGPOW_HOP * (AVGPOW_WIN - 1)             # 64 frames: one column of the smoothed spectrogram
 _avgpow_windows = {}
