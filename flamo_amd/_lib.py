@@ -1,7 +1,7 @@
 """ctypes binding of libflamo_hip.so.  The C ABI is declared in include/flamo_hip.h (and, for the energy-decay-curve and the
 average-power criteria, the FDN attenuation designs, the multi-resolution STFT, the energy-decay-relief and the mel multi-scale spectral criteria,
 include/flamo_hip_edc.h, include/flamo_hip_avgpow.h, include/flamo_hip_fdnatt.h, include/flamo_hip_mrstft.h,
-include/flamo_hip_edr.h and include/flamo_hip_melmss.h, and for the band split of the filter bank include/flamo_hip_filterbank.h), and the restype / argtypes of every entry point are read from those headers at import
+include/flamo_hip_edr.h, include/flamo_hip_melmss.h and include/flamo_hip_mss.h, and for the band split of the filter bank include/flamo_hip_filterbank.h), and the restype / argtypes of every entry point are read from those headers at import
 (_parse_header): no signature is written a second time here.
 
 The shared library is built in-tree (``flamo_amd/libflamo_hip.so``) by ``build()`` /
@@ -27,6 +27,7 @@ HEADER_FDNATT_PATH = os.path.join(os.path.dirname(_HERE), "include", "flamo_hip_
 HEADER_MRSTFT_PATH = os.path.join(os.path.dirname(_HERE), "include", "flamo_hip_mrstft.h")      # the criterion of csrc/mrstft.hip
 HEADER_EDR_PATH = os.path.join(os.path.dirname(_HERE), "include", "flamo_hip_edr.h")      # ... of csrc/edr.hip
 HEADER_MELMSS_PATH = os.path.join(os.path.dirname(_HERE), "include", "flamo_hip_melmss.h")      # ... of csrc/melmss.hip
+HEADER_MSS_PATH = os.path.join(os.path.dirname(_HERE), "include", "flamo_hip_mss.h")      # ... of csrc/mss.hip
 HEADER_FILTERBANK_PATH = os.path.join(os.path.dirname(_HERE), "include", "flamo_hip_filterbank.h")      # the band split of csrc/filterbank.hip
 
 _lock = threading.Lock()
@@ -113,6 +114,9 @@ _SIGNATURES_EDR = _read_header(HEADER_EDR_PATH)
 # ... and those of include/flamo_hip_melmss.h
 _SIGNATURES_MELMSS = _read_header(HEADER_MELMSS_PATH)
 
+# ... and those of include/flamo_hip_mss.h
+_SIGNATURES_MSS = _read_header(HEADER_MSS_PATH)
+
 # ... and those of include/flamo_hip_filterbank.h
 _SIGNATURES_FILTERBANK = _read_header(HEADER_FILTERBANK_PATH)
 
@@ -155,7 +159,8 @@ def lib(pair_ok: bool = False) -> C.CDLL:
                 handle = C.CDLL(LIB_PATH)
                 for name, (res, args) in (*_SIGNATURES.items(), *_SIGNATURES_EDC.items(), *_SIGNATURES_AVGPOW.items(),
                                            *_SIGNATURES_FDNATT.items(), *_SIGNATURES_MRSTFT.items(), *_SIGNATURES_EDR.items(),
-                                           *_SIGNATURES_MELMSS.items(), *_SIGNATURES_FILTERBANK.items()):
+                                           *_SIGNATURES_MELMSS.items(), *_SIGNATURES_MSS.items(),
+                                           *_SIGNATURES_FILTERBANK.items()):
                     fn = getattr(handle, name)  # AttributeError if the symbol is missing
                     fn.restype = res
                     fn.argtypes = args

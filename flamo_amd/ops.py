@@ -3576,6 +3576,218 @@ def mel_mss_loss(y_pred: torch.Tensor, y_true: torch.Tensor, nfft=MELMSS_NFFTS, 
     return _MelMSS.apply(y_pred, y_true, frames, sample_rate, opts)
 
 
+MSS_MAX_RES, MSS_NFFTS, MSS_FMIN, MSS_CHUNK = 8, (128, 256, 512, 1024, 2048, 4096), 20, 64      # what csrc/mss.hip takes
+MSS_FORMS = {None: 0, "yamamoto": 1, "magenta": 2}                                              # ``form`` -> the kernels' form
+_mss_host_tables = {}
+_mss_tables = {}
+
+
+def _mss_rate(sample_rate):
+    """the sample rate as an int when it is an integral number >= 80 (fmax = sample_rate // 2 at least 20 Hz over fmin = 20
+    Hz: a positive bin spacing), else None"""
+    if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, float)) or not math.isfinite(sample_rate):
+        return None
+    if sample_rate != int(sample_rate) or sample_rate < 4 * MSS_FMIN:
+        return None
+    return int(sample_rate)
+
+
+def mss_cycles(sample_rate, nfft, k, j):
+    """frac(beta_k j / n_fft) in float64 for integer tensors ``k`` (bins) and ``j`` (samples) that broadcast: the phase, in
+    cycles, of entry (j, k) of the basis of nnAudio's STFT with freq_scale="linear", fmin = 20, fmax = sample_rate // 2, whose
+    K = n_fft // 2 + 1 bins sit at beta_k = a + k s, a = 20 n_fft / sample_rate, s = (sample_rate // 2 - 20) (n_fft /
+    sample_rate) / K.  For an integral sample rate beta_k j / n_fft = j (20 K + k h) / (sample_rate K), h = sample_rate // 2 -
+    20, and the fraction is taken in integers: exact before the one division.  (beta_k j / n_fft reaches 2048 cycles; rounded as
+    a float64 product it would be off by 3e-12 rad.)  Any other sample rate takes the float64 product."""
+    K = nfft // 2 + 1
+    sr = _mss_rate(sample_rate)
+    if sr is None:
+        a = MSS_FMIN * nfft / sample_rate
+        s = (sample_rate // 2 - MSS_FMIN) * (nfft / sample_rate) / K
+        c = (a + k.to(torch.float64) * s) * j.to(torch.float64) / nfft
+        return c - torch.floor(c)
+    Q = sr * K
+    num = (j.to(torch.int64) * (MSS_FMIN * K + k.to(torch.int64) * (sr // 2 - MSS_FMIN))) % Q
+    return num.to(torch.float64) / Q
+
+
+def mss_basis(sample_rate, nfft, device=None):
+    """(cos, sin) of 2 pi beta_k j / n_fft as two float64 (K, n_fft) matrices (see ``mss_cycles``): bin k of a frame x is
+    sum_j x_j (cos - i sin)[k, j]"""
+    k = torch.arange(nfft // 2 + 1, device=device)[:, None]
+    j = torch.arange(nfft, device=device)[None, :]
+    ang = (2 * math.pi) * mss_cycles(sample_rate, nfft, k, j)
+    return torch.cos(ang), torch.sin(ang)
+
+
+def _mss_frames(nfft, overlap):
+    return _melmss_frames(nfft, overlap)
+
+
+def _mss_host(sample_rate, n):
+    """the tables of one resolution as include/flamo_hip_mss.h lays them out, a float64 vector, cached per (sample_rate,
+    n_fft): the periodic Hann window, then as (re, im) pairs fseed[k, m] = exp(-i theta_k 64 m), fstep[k, c] = exp(-i theta_k
+    c), bseed[j, m] = exp(+i theta_{64 m} j) and bstep[j, c] = exp(+i (theta_c - theta_0) j), c = 0 .. 4"""
+    key = (sample_rate, n)
+    ent = _mss_host_tables.get(key)
+    if ent is None:
+        K, sr = n // 2 + 1, _mss_rate(sample_rate)
+        NJ, NK = -(-n // MSS_CHUNK), -(-K // MSS_CHUNK)
+        k, j = torch.arange(K)[:, None], torch.arange(n)[:, None]
+        five = torch.arange(5)[None, :]
+
+        def unit(cycles, sign):
+            ang = (2 * math.pi) * cycles
+            return torch.stack((torch.cos(ang), sign * torch.sin(ang)), dim=-1).reshape(-1)
+
+        Q = sr * K
+        shift = ((five * j * (sr // 2 - MSS_FMIN)) % Q).to(torch.float64) / Q          # (theta_c - theta_0) j / 2 pi
+        ent = _mss_host_tables[key] = torch.cat([
+            torch.hann_window(n, dtype=torch.float64),
+            unit(mss_cycles(sr, n, k, MSS_CHUNK * torch.arange(NJ)[None, :]), -1.0),
+            unit(mss_cycles(sr, n, k, five), -1.0),
+            unit(mss_cycles(sr, n, MSS_CHUNK * torch.arange(NK)[None, :], j), 1.0),
+            unit(shift, 1.0)])
+    return ent
+
+
+def _mss_norm(p):
+    return _melmss_norm(p)
+
+
+def _mss_form(form):
+    try:
+        return MSS_FORMS.get(form)
+    except TypeError:
+        return None
+
+
+def mss_supported(shape, nfft=MSS_NFFTS, overlap=0.75, sample_rate=48000, p="fro", form=None) -> bool:
+    """whether ``mss_loss`` takes (B, T, N) signals under these resolutions: 1 to 8 of them, n_fft a multiple of 4 from 16 to
+    4096 (no power of two is asked for), hop = int(n_fft (1 - overlap)) >= 1, n_fft / 2 < T <= 2^30, fewer than 2^31 frames,
+    2^24 workgroups per launch and 2^32 samples in all, an integral sample rate >= 80, ``p`` in "fro", 2, 1 and ``form`` None, "yamamoto" or
+    "magenta" """
+    frames = _mss_frames(nfft, overlap)
+    try:
+        dims = tuple(int(s) for s in shape)
+        same = all(a == b for a, b in zip(dims, tuple(shape)))
+    except (TypeError, ValueError):
+        return False
+    if frames is None or not same or len(dims) != 3 or max(map(abs, dims)) >= 1 << 62 or not 1 <= len(frames) <= MSS_MAX_RES:
+        return False
+    if _mss_norm(p) is None or _mss_form(form) is None or _mss_rate(sample_rate) is None:
+        return False
+    flat = [v for pair in frames for v in pair]
+    # the library's own support query: one statement of the sizes
+    return _lib.lib().fl_mss_frames(*dims, len(frames), (ctypes.c_int * len(flat))(*flat)) >= 0
+
+
+def _mss_consts(frames, sample_rate, dev: torch.device):
+    """(the tables of the resolutions one behind the other on the device, the resolutions as a host int array of (n_fft,
+    hop)), cached per (resolutions, sample_rate, device); made on the host in float64 under either precision of the signals"""
+    key = (frames, sample_rate, dev.index if dev.index is not None else torch.cuda.current_device())
+    ent = _mss_tables.get(key)
+    if ent is None:
+        flat = [v for pair in frames for v in pair]
+        cres = (ctypes.c_int * len(flat))(*flat)
+        tab = torch.cat([_mss_host(sample_rate, n) for n, _ in frames])
+        assert tab.numel() == _lib.lib().fl_mss_table_doubles(len(frames), cres)
+        ent = _mss_tables[key] = (tab.to(dev), cres)
+    return ent
+
+
+class _MSS(torch.autograd.Function):
+    """the linear multi-scale spectral criterion, one node over the prediction: tile kernel, combine and final kernel forward
+    (keeping, when the prediction takes a gradient, its transform and the target's magnitudes per resolution -- the dense
+    transform is not recomputed); the adjoint tile kernel and the overlap-add backward"""
+
+    @staticmethod
+    def forward(ctx, y, t, frames, sample_rate, opts):
+        dev = _require_gpu(y, t)
+        L = _lib.lib()
+        B, T, N = y.shape
+        tab, cres = _mss_consts(frames, sample_rate, dev)
+        R = len(frames)
+        norm, form, log_term, alpha, apply_mask, threshold, ne = opts
+        planes = int(bool(ctx.needs_input_grad[0]))
+        partial = torch.empty(L.fl_mss_partial_doubles(B, T, N, R, cres), dtype=torch.float64, device=dev)
+        keep = torch.empty(L.fl_mss_keep_doubles(B, T, N, R, cres, planes), dtype=torch.float64, device=dev)
+        loss = _scalar_loss(y.dtype, dev)
+        with kernel_timer.span("mss_fwd"):
+            _lib.check(_fn("fl_mss_fwd", y.dtype)(y.data_ptr(), *y.stride(), t.data_ptr(), *t.stride(), B, T, N, R, cres,
+                                                  tab.data_ptr(), norm, form, log_term, alpha, apply_mask, threshold, ne, planes,
+                                                  partial.data_ptr(), keep.data_ptr(), loss.data_ptr(), _stream()), "mss_fwd")
+        if planes:
+            ctx.save_for_backward(keep)
+            ctx.cfg = (tuple(y.shape), y.dtype, frames, sample_rate, opts)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        (keep,) = ctx.saved_tensors
+        shape, dtype, frames, sample_rate, opts = ctx.cfg
+        L = _lib.lib()
+        B, T, N = shape
+        dev = keep.device
+        tab, cres = _mss_consts(frames, sample_rate, dev)
+        R = len(frames)
+        norm, form, log_term, _, apply_mask, threshold, ne = opts
+        gframes = torch.empty(L.fl_mss_gframe_elems(B, T, N, R, cres), dtype=dtype, device=dev)
+        gy = torch.empty((B, T, N), dtype=dtype, device=dev)
+        g = _gloss_as(gloss, dtype)
+        with kernel_timer.span("mss_bwd"):
+            _lib.check(_fn("fl_mss_bwd", dtype)(B, T, N, R, cres, tab.data_ptr(), norm, form, log_term, apply_mask, threshold, ne,
+                                                keep.data_ptr(), g.data_ptr(), gframes.data_ptr(), gy.data_ptr(), _stream()),
+                       "mss_bwd")
+        return gy, None, None, None, None
+
+
+def mss_loss(y_pred: torch.Tensor, y_true: torch.Tensor, nfft=MSS_NFFTS, overlap: float = 0.75, sample_rate: int = 48000,
+             p="fro", log_term: bool = False, alpha: float = 1.0, apply_mask: bool = False, threshold: float = 5.0,
+             noise_energy=None, form=None) -> torch.Tensor:
+    """The multi-scale spectral criterion on the linear frequency scale of (B, T, N) signals (flamo_amd.optimize.loss.mss_loss
+    has the definition): for every n_fft of ``nfft`` the magnitudes of a framed DFT of every (batch, channel) column of
+    prediction and target -- periodic Hann window of n_fft samples, hop int(n_fft (1 - overlap)), reflect padding -- at the
+    n_fft // 2 + 1 fractional bin positions of ``mss_cycles``, and the plain (``form`` None: |(M_t - M_p) mask|_p / Nn, with
+    ``log_term`` plus ``alpha`` times the same of the logarithms), the "yamamoto" or the "magenta" form; the sum over the
+    resolutions.  ``apply_mask`` drops the entries whose target stands less than ``threshold`` dB over ``noise_energy``, a
+    number > 0 here (optimize.loss.mss_loss derives it when it is None).  One autograd node over the prediction, five launches
+    in all (three forward, two backward) whatever the resolutions; the transform is a dense float64 product on the matrix
+    cores, kept for the backward pass when the prediction takes a gradient (3 (n_fft / 2 + 1) doubles per frame); the signals
+    are read through their strides, nothing is copied, nothing is read back.  The target takes no gradient.  Sizes:
+    ``mss_supported``."""
+    _require_gpu(y_pred, y_true)
+    if y_pred.dim() != 3 or y_pred.dtype not in (torch.float32, torch.float64) or y_pred.numel() == 0:
+        raise ValueError(f"mss_loss: a non-empty real float32 / float64 (B, T, N) signal, got {tuple(y_pred.shape)} {y_pred.dtype}")
+    if tuple(y_true.shape) != tuple(y_pred.shape) or y_true.dtype != y_pred.dtype:
+        raise ValueError(f"mss_loss: prediction {tuple(y_pred.shape)} {y_pred.dtype} and target {tuple(y_true.shape)} "
+                         f"{y_true.dtype} differ")
+    if y_true.requires_grad:
+        raise ValueError("mss_loss: the target takes no gradient here (detach it, or use optimize.loss.mss_loss's torch lines)")
+    norm, kform = _mss_norm(p), _mss_form(form)
+    if norm is None:
+        raise ValueError(f"mss_loss: p must be 'fro', 2 or 1, got {p!r}")
+    if kform is None:
+        raise ValueError(f"mss_loss: form must be None, 'yamamoto' or 'magenta', got {form!r}")
+    if _mss_rate(sample_rate) is None:
+        raise ValueError(f"mss_loss: sample_rate must be an integral number >= 80, got {sample_rate!r}")
+    frames = _mss_frames(nfft, overlap)
+    if frames is None or not mss_supported(tuple(y_pred.shape), nfft, overlap, sample_rate, p, form):
+        raise ValueError(f"mss_loss: resolutions nfft = {nfft!r}, overlap = {overlap!r} on T = {y_pred.shape[1]}: 1 to "
+                         f"{MSS_MAX_RES} n_fft, each a multiple of 4 from 16 to 4096 with hop = int(n_fft (1 - overlap)) >= 1, "
+                         f"n_fft / 2 < T <= 2^30 and fewer than 2^31 frames in all")
+    try:
+        alpha, threshold = float(alpha), float(threshold)
+        ne = 1.0 if not apply_mask else float(noise_energy)
+    except (TypeError, ValueError):
+        ne = float("nan")
+    if not (ne > 0.0 and math.isfinite(ne)):
+        raise ValueError(f"mss_loss: apply_mask needs a finite noise_energy > 0 (a number: the class derives it from the target "
+                         f"when it is None), got {noise_energy!r}")
+    opts = (norm, kform, int(bool(log_term)), alpha, int(bool(apply_mask)), threshold, ne)
+    return _MSS.apply(y_pred, y_true, frames, _mss_rate(sample_rate), opts)
+
+
 def mean_square(y: torch.Tensor) -> torch.Tensor:
     """(y ** 2).mean() of a real tensor in one streaming pass each way (forward: one read of y;
     backward: one read + one write), in whatever layout y is stored."""
