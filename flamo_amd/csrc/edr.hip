@@ -11,8 +11,8 @@
 // Launches: THREE forward (frames, relief, final) and THREE backward (prefix, frames, overlap-add), whatever B, N and T.
 //
 // Frames.  One wavefront per (row, frame) on the framed real transform of framed.h, both signals one after the other.  The
-// frame's |X|^2 goes to LDS and lane j sums the taps of band j from there (a start / count / offset triple per band and the
-// non-zero weights of W packed band after band): 64 doubles per frame and signal reach memory, the spectrogram never does.
+// frame's |X|^2 goes to LDS and lane j sums the taps of band j from there (mel_project of criterion.h, which also states the
+// table's format): 64 doubles per frame and signal reach memory, the spectrogram never does.
 // The frame length is a template argument here (one resolution per call), so the LDS of a workgroup is that of its n_fft.
 //
 // Relief.  One workgroup of 16 wavefronts per row, lane = band, so every step of a walk is one coalesced 512-byte load per
@@ -39,7 +39,7 @@
 // Resources (the compiler's report for gfx950, n_fft = 2048): LDS A[1088] complex doubles (17 KB) + 1025 doubles of |X|^2
 // (8 KB) = 25 KB forward, A + 1025 complex doubles of bins / dL/dX (16 KB) = 33 KB backward, as mrstft.hip's (the frame's 64
 // values of dL/dm sit in A between the transform and the inverse walk); the VGPR counts are in DESIGN 4.6; no scratch.
-#include "framed.h"
+#include "criterion.h"
 #include "../../include/flamo_hip_edr.h"
 
 namespace fl {
@@ -48,66 +48,32 @@ namespace edr {
 using C = double;
 
 constexpr int NFFT_MIN = 256, NFFT_MAX = 2048, NTW = 2048, BANDS = 64;
-constexpr long T_MAX = 1L << 30, BLOCKS_MAX = (1L << 31) - 1, SAMPLES_MAX = 1L << 38;
+constexpr long BLOCKS_MAX = (1L << 31) - 1, SAMPLES_MAX = 1L << 38;
 constexpr int KEEP_INVD = 0, KEEP_DOUBLES = 1;      // what the backward entry reads again: 1 / D
 constexpr int RW = 16;      // wavefronts per row in the relief and prefix kernels
+
+using framed::Strides;
+using framed::Mel;      // 64 bands here
+using framed::power;
+using framed::row_offset;
 
 struct Plan : framed::Frame {
     int nfft;
     long B, T, N, rows, F, blocks;
 };
-struct Strides {
-    long b, t, c;
-};
-// the mel basis on the device: idx = start[64], count[64], offset[64] (band j holds the bins start .. start + count - 1, its
-// weights at w[offset ..]), then band[n_fft/2 + 1] (bin k lies in the bands band[k] and band[k] + 1 only);
-// w = the nnz packed weights, then the two weights of every bin
-struct Mel {
-    const int* idx;
-    const double* w;
-    int nnz;
-};
 
 static bool make_plan(long B, long T, long N, int nfft, int hop, int win, Plan& p) {
-    if (B < 1 || N < 1 || T < 1 || T > T_MAX) return false;
-    if (B > SAMPLES_MAX / T || B * T > SAMPLES_MAX / N) return false;
+    if (!framed::signal_sizes(B, T, N, SAMPLES_MAX)) return false;
     if (nfft < NFFT_MIN || nfft > NFFT_MAX || (nfft & (nfft - 1)) || hop < 1 || win < 1 || win > nfft || T <= nfft / 2) return false;
     p.nfft = nfft; p.hop = hop; p.win = win; p.lpad = (nfft - win) / 2;
     p.B = B; p.T = T; p.N = N; p.rows = B * N;
-    p.F = 1 + T / hop;
-    if (p.F > BLOCKS_MAX / p.rows) return false;
+    p.F = framed::frames_per_row(T, hop, p.rows, BLOCKS_MAX);
+    if (p.F < 0) return false;
     p.blocks = p.rows * p.F;
     return true;
 }
 
-__device__ inline double power(cx<C> x) { return x.x * x.x + x.y * x.y; }
-
-__device__ inline long row_offset(const Plan& p, long row, Strides s) {
-    const long b = row / p.N, c = row - b * p.N;
-    return b * s.b + c * s.c;
-}
-
 // ---------------------------------------------------------------- forward frames: 64 band energies per frame and signal
-// band `lane` of the |X|^2 in Sp; the table's entries are clamped to the arrays they index
-template <int P>
-__device__ inline double project(const double* Sp, const Mel& mel, int lane) {
-    constexpr int NC = 64 * P;
-    const int start = min(max(mel.idx[lane], 0), NC);
-    int count = min(max(mel.idx[BANDS + lane], 0), NC + 1 - start);
-    const int off = mel.idx[2 * BANDS + lane];
-    if (off < 0 || off > mel.nnz - count) count = 0;
-    const double* w = mel.w + off;
-    const double* s = Sp + start;
-    double a0 = 0.0, a1 = 0.0;
-    int i = 0;
-    for (; i + 1 < count; i += 2) {
-        a0 = fma(w[i], s[i], a0);
-        a1 = fma(w[i + 1], s[i + 1], a1);
-    }
-    if (i < count) a0 = fma(w[i], s[i], a0);
-    return a0 + a1;
-}
-
 template <typename T, int P>
 __global__ void __launch_bounds__(64) edr_frames_kernel(const T* __restrict__ yp, Strides sp, const T* __restrict__ yt, Strides st, Plan p,
                                                         const C* __restrict__ w, const cx<C>* __restrict__ tw, Mel mel,
@@ -120,12 +86,12 @@ __global__ void __launch_bounds__(64) edr_frames_kernel(const T* __restrict__ yp
     framed::frame_transform<T, C, P, NTW>(yp + row_offset(p, row, sp), sp.t, p.T, f, p, w, tw, A, lane);
     for (int k = lane; k <= NC; k += 64) Sp[k] = power(framed::split_bin<C, P, NTW>(A, tw, k));
     __syncthreads();
-    melout[(long)blockIdx.x * BANDS + lane] = project<P>(Sp, mel, lane);
+    melout[(long)blockIdx.x * BANDS + lane] = framed::mel_project<64 * P, BANDS>(Sp, mel, lane);
     __syncthreads();
     framed::frame_transform<T, C, P, NTW>(yt + row_offset(p, row, st), st.t, p.T, f, p, w, tw, A, lane);
     for (int k = lane; k <= NC; k += 64) Sp[k] = power(framed::split_bin<C, P, NTW>(A, tw, k));
     __syncthreads();
-    melout[(p.blocks + (long)blockIdx.x) * BANDS + lane] = project<P>(Sp, mel, lane);
+    melout[(p.blocks + (long)blockIdx.x) * BANDS + lane] = framed::mel_project<64 * P, BANDS>(Sp, mel, lane);
 }
 
 // ---------------------------------------------------------------- relief: the backward integral over frames, dB, the row's sums
@@ -278,7 +244,8 @@ __global__ void __launch_bounds__(64) edr_frames_bwd_kernel(const T* __restrict_
     framed::store_frame_grad<T, C, P>(A, w, p, gframes + (long)blockIdx.x * p.win, lane);
 }
 
-// overlap-add: a gather per sample, in a fixed order
+// overlap-add: a gather per sample, in a fixed order (its own kernel: the plan is the one resolution's Frame itself, not the
+// list of them that criterion.h's ola_kernel walks)
 template <typename T>
 __global__ void __launch_bounds__(256) edr_ola_kernel(const T* __restrict__ gframes, Plan p, const T* __restrict__ gloss, T* __restrict__ gy) {
     const long e = (long)blockIdx.x * 256 + threadIdx.x;

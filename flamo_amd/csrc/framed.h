@@ -1,5 +1,6 @@
 // The framed real transform of the short-time criteria (avgpow.hip, mrstft.hip, edr.hip), one wavefront per frame: the
-// wave-level pieces only -- the kernels, their plans and LDS arrays are the callers'.
+// wave-level pieces only -- the kernels, their plans and LDS arrays are the callers'.  (What the criteria on (B, T, N) signals
+// share around it -- rows, the mel projection, the combine, the multi-resolution overlap-add -- is criterion.h.)
 //
 // The n_fft = 128 P real samples of a frame are Nc = 64 P complex ones (even samples real, odd samples imaginary), P = 2, 4, 8,
 // 16 per lane.  The window is applied while loading and only the samples under its support [lpad, lpad + win) are read.  The

@@ -20,21 +20,21 @@
 // first.
 //
 // Forward frames.  Both signals one after the other: the frame's |X|^2 goes to LDS and thread j sums the taps of the bands j,
-// j + (threads), ... from there (a start / count / offset triple per band, the non-zero weights packed band after band).  The
-// prediction's band energies wait in registers (two per thread at most) for the target's; a frame leaves five doubles, sum
-// mask d^2, sum mask |d|, the same two of the log difference and sum mask -- the mel spectrograms never reach memory.  The
-// combine adds them per resolution in a fixed order (no atomics: two runs give the same bits), the final kernel forms the loss
-// and the two factors of dL/dm_p per resolution.
+// j + (threads), ... from there (mel_project of criterion.h, which also states the table's format).  The prediction's band
+// energies wait in registers (two per thread at most) for the target's; a frame leaves five doubles, sum mask d^2, sum mask
+// |d|, the same two of the log difference and sum mask -- the mel spectrograms never reach memory.  The combine of
+// criterion.h adds them per resolution in a fixed order (no atomics: two runs give the same bits), the final kernel forms the
+// loss and the two factors of dL/dm_p per resolution.
 //
 // Backward frames.  Both transforms are recomputed, the target's first: a signal's bins go to Y, their |X|^2 into the walk's
 // array (free between a transform and the next walk), the band energies to registers; after the second pass Y holds the
 // prediction's bins.  dL/dm_p is formed per band and laid beside the |X|^2; dL/dP[k] is gathered from the at most two
 // (consecutive) bands that hold bin k, dL/dX = 2 X dL/dP through the Hermitian split, the adjoint of the split, the inverse
-// walk and the windowed store.  The overlap-add gathers per sample, resolution by resolution, with the reflected margins
-// folded back.
+// walk and the windowed store.  The overlap-add of criterion.h gathers per sample, resolution by resolution, with the
+// reflected margins folded back.
 //
-// In both frame kernels the two signals run through ONE loop body (`both_signals`), so that a prediction equal to the target
-// gives band energies equal to the bit, and with them an exact 0 for the loss and for sign(m_t - m_p).
+// In both frame kernels the two signals run through ONE loop body (`both_signals` of criterion.h), so that a prediction equal
+// to the target gives band energies equal to the bit, and with them an exact 0 for the loss and for sign(m_t - m_p).
 //
 // Precision.  As in mrstft.hip and edr.hip: the signals, the frame gradients and the gradient have the signals' type,
 // everything between is a double in float32 too -- the mask decision and the signs of the 1-norm are those of the float64
@@ -42,7 +42,7 @@
 //
 // Resources (the compiler's report for gfx950 is in DESIGN 4.6): LDS forward A + |X|^2 = 9 + 4 KB (short) and 33 + 16 KB
 // (long), backward A + Y = 9 + 8 KB and 33 + 32 KB; no scratch.
-#include "framed.h"
+#include "criterion.h"
 #include "../../include/flamo_hip_melmss.h"
 
 namespace fl {
@@ -52,9 +52,17 @@ using C = double;
 
 constexpr int MAXR = 8, NFFT_MIN = 128, NFFT_SHORT = 1024, NFFT_MAX = 4096, NTW = 4096;
 constexpr int NT_SHORT = 64, NT_LONG = framed::WIDE_NT;
-constexpr long T_MAX = 1L << 30, BLOCKS_MAX = (1L << 31) - 1, SAMPLES_MAX = 1L << 38;
+constexpr long BLOCKS_MAX = (1L << 31) - 1, SAMPLES_MAX = 1L << 38;
 constexpr int NSUM = 5;      // sum mask d^2, sum mask |d|, the same two of the log difference, sum mask
 constexpr int KEEP_STRIDE = 8, KEEP_C0 = 5, KEEP_C1 = 6, KEEP_LOSS = KEEP_STRIDE * MAXR, KEEP_DOUBLES = KEEP_LOSS + 1;
+
+using framed::Strides;
+using framed::Mel;      // of one resolution, n_fft / 8 bands
+using framed::power;
+using framed::sign;
+using framed::row_offset;
+using framed::snr_mask;
+using framed::both_signals;
 
 struct Res : framed::Frame {
     int nfft, nnz;
@@ -71,18 +79,9 @@ struct Plan {
     long B, T, N, rows, frames, gelems, blocks[2], melints, meldoubles;
     Res r[MAXR];
 };
-struct Strides {
-    long b, t, c;
-};
 struct Opt {
     int norm, log_term, apply_mask;
     double alpha, threshold, ne;
-};
-// the mel basis of one resolution on the device (the format of edr.hip, n_fft / 8 bands)
-struct Mel {
-    const int* idx;
-    const double* w;
-    int nnz;
 };
 
 static bool is_long(int nfft) { return nfft > NFFT_SHORT; }
@@ -108,15 +107,14 @@ static bool make_tables(int R, const int* res, Plan& p) {
 }
 
 static bool make_plan(long B, long T, long N, int R, const int* res, Plan& p) {
-    if (!make_tables(R, res, p) || B < 1 || N < 1 || T < 1 || T > T_MAX) return false;
-    if (B > SAMPLES_MAX / T || B * T > SAMPLES_MAX / N) return false;
+    if (!make_tables(R, res, p) || !framed::signal_sizes(B, T, N, SAMPLES_MAX)) return false;
     p.B = B; p.T = T; p.N = N; p.rows = B * N;
     long frames = 0, g = 0;
     for (int r = 0; r < R; ++r) {
         Res& q = p.r[r];
         if (T <= q.nfft / 2) return false;
-        q.F = 1 + T / q.hop;
-        if (q.F > BLOCKS_MAX / p.rows) return false;
+        q.F = framed::frames_per_row(T, q.hop, p.rows, BLOCKS_MAX);
+        if (q.F < 0) return false;
         q.fr0 = frames; q.g0 = g;
         frames += p.rows * q.F;
         if (frames > BLOCKS_MAX) return false;
@@ -137,8 +135,6 @@ static bool make_plan(long B, long T, long N, int R, const int* res, Plan& p) {
     return true;
 }
 
-__device__ inline double power(cx<C> x) { return x.x * x.x + x.y * x.y; }
-
 // (resolution, row, frame) of a workgroup of the size class LONG: the resolution of the class that starts last at or before it
 template <bool LONG>
 __device__ inline void locate(const Plan& p, long blk, int& r, long& row, long& f) {
@@ -154,11 +150,6 @@ __device__ inline void locate(const Plan& p, long blk, int& r, long& row, long& 
     f = local - row * p.r[r].F;
 }
 
-__device__ inline long row_offset(const Plan& p, long row, Strides s) {
-    const long b = row / p.N, c = row - b * p.N;
-    return b * s.b + c * s.c;
-}
-
 template <int P> struct Shape {
     static constexpr bool LONG = P >= 16;
     static constexpr int NC = 64 * P, NT = LONG ? NT_LONG : NT_SHORT, NM = 16 * P;      // bins - 1, threads, bands
@@ -172,66 +163,20 @@ __device__ inline void transform(const T* __restrict__ y, long stride, long Tn, 
     else framed::frame_transform<T, C, P, NTW>(y, stride, Tn, f, q, w, tw, A, tid);
 }
 
-// band j of the |X|^2 in Sp; the table's entries are clamped to the arrays they index
-template <int P>
-__device__ inline double project(const double* Sp, const Mel& mel, int j) {
-    constexpr int NC = Shape<P>::NC, NM = Shape<P>::NM;
-    const int start = min(max(mel.idx[j], 0), NC);
-    int count = min(max(mel.idx[NM + j], 0), NC + 1 - start);
-    const int off = mel.idx[2 * NM + j];
-    if (off < 0 || off > mel.nnz - count) count = 0;
-    const double* w = mel.w + off;
-    const double* s = Sp + start;
-    double a0 = 0.0, a1 = 0.0;
-    int i = 0;
-    for (; i + 1 < count; i += 2) {
-        a0 = fma(w[i], s[i], a0);
-        a1 = fma(w[i + 1], s[i + 1], a1);
-    }
-    if (i < count) a0 = fma(w[i], s[i], a0);
-    return a0 + a1;
-}
-
-// 1 where the target's band energy stands `threshold` dB over the noise energy, else 0 (a NaN keeps its entry, as the
-// comparison SNR < threshold of the definition does)
-__device__ inline double snr_mask(double mt, const Opt& o) {
-    if (!o.apply_mask) return 1.0;
-    const double snr = 10.0 * log10(fmax(mt * mt, o.ne * 1.01) - o.ne) - 10.0 * log10(o.ne);
-    return snr < o.threshold ? 0.0 : 1.0;
-}
-
-__device__ inline double sign(double d) { return d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : 0.0); }
-
-// Runs body(0, .) and then body(1, .) as ONE loop body that is not unrolled, and hands back the NB values each left: the
-// first signal's in `first`, the second's in `second`.  A prediction equal to the target must give band energies equal to
-// the bit -- the loss and, for the 1-norm, sign(m_t - m_p) are exact zeros then -- and two inlined copies of the same
-// source are not held to that: where a product is fused into an addition is decided copy by copy.
-template <int NB, class Body>
-__device__ inline void both_signals(double (&first)[NB], double (&second)[NB], Body&& body) {
-#pragma clang loop unroll(disable)
-    for (int sig = 0; sig < 2; ++sig) {
-        if (sig) {
-#pragma unroll
-            for (int i = 0; i < NB; ++i) first[i] = second[i];
-        }
-        body(sig, second);
-    }
-}
-
 // ---------------------------------------------------------------- forward: the five sums of a frame
 template <typename T, int P>
 __device__ inline void frame_sums(const T* __restrict__ yp, long sp, const T* __restrict__ yt, long st, long Tn, long f, const Res& q,
                                   const C* __restrict__ w, const cx<C>* __restrict__ tw, const Mel& mel, const Opt& o, cx<C>* A,
                                   double* Sp, double (*red)[4], double* __restrict__ out, int tid) {
     constexpr int NC = Shape<P>::NC, NT = Shape<P>::NT, NM = Shape<P>::NM, NB = Shape<P>::NB;
-    // one body for both signals (see the note at `both_signals`): the prediction, then the target
+    // one body for both signals (see the note at `both_signals`, criterion.h): the prediction, then the target
     double mp[NB], mt[NB];
     both_signals<NB>(mp, mt, [&](int sig, double (&m)[NB]) {
         transform<T, P>(sig ? yt : yp, sig ? st : sp, Tn, f, q, w, tw, A, tid);
         for (int k = tid; k <= NC; k += NT) Sp[k] = power(framed::split_bin<C, P, NTW>(A, tw, k));
         __syncthreads();
 #pragma unroll
-        for (int i = 0; i < NB; ++i) m[i] = tid + NT * i < NM ? project<P>(Sp, mel, tid + NT * i) : 0.0;
+        for (int i = 0; i < NB; ++i) m[i] = tid + NT * i < NM ? framed::mel_project<NC, NM>(Sp, mel, tid + NT * i) : 0.0;
         __syncthreads();
     });
     double s[NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0};
@@ -300,27 +245,6 @@ melmss_frames_kernel(const T* __restrict__ yp, Strides sp, const T* __restrict__
     }
 }
 
-// ---------------------------------------------------------------- combine: one workgroup per resolution, a fixed order
-__global__ void __launch_bounds__(256) melmss_combine_kernel(const double* __restrict__ partial, Plan p, double* __restrict__ keep) {
-    __shared__ double red[NSUM][4];
-    const int r = blockIdx.x;
-    const long n = p.rows * p.r[r].F;
-    const double* q = partial + NSUM * p.r[r].fr0;
-    double s[NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    for (long i = threadIdx.x; i < n; i += 256) {
-#pragma unroll
-        for (int c = 0; c < NSUM; ++c) s[c] += q[NSUM * i + c];
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < NSUM; ++c) {
-        s[c] = wave_sum(s[c]);
-        if (lane == 0) red[c][wave] = s[c];
-    }
-    __syncthreads();
-    if (threadIdx.x < NSUM) keep[KEEP_STRIDE * r + threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
-}
-
 // one thread: the loss and, per resolution, the factors of dL/dm_p = -mask (c0 d + c1 dl / m_p) (norm 2; the norm's
 // gradient is 0 where the norm is, as torch's is) or -mask (c0 sign d + c1 sign dl / m_p) (norm 1)
 template <typename T>
@@ -352,7 +276,7 @@ __device__ inline void frame_grad(const T* __restrict__ yp, long sp, const T* __
                                   const double* __restrict__ coef, cx<C>* A, cx<C>* Y, T* __restrict__ out, int tid) {
     constexpr int NC = Shape<P>::NC, NT = Shape<P>::NT, NM = Shape<P>::NM, NB = Shape<P>::NB;
     const double c0 = coef[KEEP_C0], c1 = coef[KEEP_C1];
-    // one body for both signals (see the note at `both_signals`): the target, then the prediction, whose bins stay in Y.
+    // one body for both signals (see the note at `both_signals`, criterion.h): the target, then the prediction, whose bins stay in Y.
     // The |X|^2 of a signal lie in A, free between the split and the next walk; dL/dm_p goes behind them.
     double mt[NB], mp[NB];
     double* Sp = reinterpret_cast<double*>(A);
@@ -364,7 +288,7 @@ __device__ inline void frame_grad(const T* __restrict__ yp, long sp, const T* __
         for (int k = tid; k <= NC; k += NT) Sp[k] = power(Y[k]);
         __syncthreads();
 #pragma unroll
-        for (int i = 0; i < NB; ++i) m[i] = tid + NT * i < NM ? project<P>(Sp, mel, tid + NT * i) : 0.0;
+        for (int i = 0; i < NB; ++i) m[i] = tid + NT * i < NM ? framed::mel_project<NC, NM>(Sp, mel, tid + NT * i) : 0.0;
         __syncthreads();
     });
 #pragma unroll
@@ -435,23 +359,6 @@ melmss_frames_bwd_kernel(const T* __restrict__ yp, Strides sp, const T* __restri
     }
 }
 
-// ---------------------------------------------------------------- overlap-add: a gather per sample, in a fixed order
-template <typename T>
-__global__ void __launch_bounds__(256) melmss_ola_kernel(const T* __restrict__ gframes, Plan p, const T* __restrict__ gloss,
-                                                        T* __restrict__ gy) {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= p.rows * p.T) return;
-    const long row = e / p.T, t = e - row * p.T;
-    double acc = 0.0;
-    for (int r = 0; r < p.R; ++r) {
-        const Res& q = p.r[r];
-        const T* g = gframes + q.g0 + row * q.F * q.win;
-        framed::gather_sample(g, t, p.T, q.nfft / 2, q, q.F - 1, acc);
-    }
-    const long b = row / p.N, c = row - b * p.N;
-    gy[(b * p.T + t) * p.N + c] = (T)((double)gloss[0] * acc);
-}
-
 }  // namespace melmss
 }  // namespace fl
 
@@ -517,8 +424,9 @@ FL_ENTRY_F32_F64(fl_melmss_fwd, (const void* yp, long spb, long spt, long spc, c
                            (const double*)melw, o, (double*)partial);
         FL_CHECK_LAUNCH("melmss_frames (long)");
     }
-    hipLaunchKernelGGL(melmss_combine_kernel, dim3((unsigned)p.R), dim3(256), 0, (hipStream_t)stream, (const double*)partial, p,
-                       (double*)keep);
+    const framed::Spans sums = framed::spans_of(p, [](const Res& q) { return q.fr0; }, [&](const Res& q) { return p.rows * q.F; });
+    hipLaunchKernelGGL((framed::combine_kernel<NSUM, KEEP_STRIDE>), dim3((unsigned)p.R), dim3(256), 0, (hipStream_t)stream,
+                       (const double*)partial, sums, (double*)keep);
     FL_CHECK_LAUNCH("melmss_combine");
     hipLaunchKernelGGL((melmss_final_kernel<T>), dim3(1), dim3(64), 0, (hipStream_t)stream, p, o, (double*)keep, (T*)loss);
     FL_CHECK_LAUNCH("melmss_final");
@@ -547,7 +455,7 @@ FL_ENTRY_F32_F64(fl_melmss_bwd, (const void* yp, long spb, long spt, long spc, c
         FL_CHECK_LAUNCH("melmss_frames_bwd (long)");
     }
     const long blocks = (p.rows * p.T + 255) / 256;
-    hipLaunchKernelGGL((melmss_ola_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const T*)gframes, p,
+    hipLaunchKernelGGL((framed::ola_kernel<T, Plan>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const T*)gframes, p,
                        (const T*)gloss, (T*)gy);
     FL_CHECK_LAUNCH("melmss_ola");
     return FL_OK;

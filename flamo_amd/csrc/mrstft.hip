@@ -14,11 +14,11 @@
 // Frames.  One wavefront per frame on the framed real transform of framed.h (the packed Stockham walk, its LDS padding and
 // register budget, the split into bins and its adjoint are described there), P = n_fft / 128 = 2, 4, 8, 16 complex values per
 // lane.  The spectrograms never reach memory: a frame leaves four doubles (sum (M_t - M_p)^2, sum M_t^2,
-// sum |log M_p - log M_t|, sum |M_p - M_t|), the combine adds them per resolution in a fixed order (no atomics: two runs give
-// the same bits), the final kernel forms the loss and the three factors of dL/dM_p the backward pass needs.  The backward
-// frame kernel recomputes both transforms, forms dL/dX = dL/dM_p X / M_p (zero where |X|^2 <= eps), runs the adjoint of the
-// split and the inverse walk, and writes the win samples under the window; the overlap-add gathers per sample, resolution by
-// resolution and frame by frame, with the reflected margins folded back onto the interior samples they mirror.
+// sum |log M_p - log M_t|, sum |M_p - M_t|), the combine of criterion.h adds them per resolution in a fixed order (no atomics:
+// two runs give the same bits), the final kernel forms the loss and the three factors of dL/dM_p the backward pass needs.  The
+// backward frame kernel recomputes both transforms, forms dL/dX = dL/dM_p X / M_p (zero where |X|^2 <= eps), runs the adjoint
+// of the split and the inverse walk, and writes the win samples under the window; the overlap-add of criterion.h gathers per
+// sample, resolution by resolution and frame by frame, with the reflected margins folded back onto the samples they mirror.
 //
 // Precision.  The signals, the frame gradients and the gradient have the signals' type; everything between is a double in
 // float32 too (see `C` below), so the two precisions run the same kernels and differ in their loads and stores.
@@ -28,7 +28,7 @@
 // doubles, 16 KB): 25 KB forward and 33 KB backward per wavefront, six and four wavefronts per CU of its 160 KB.  The
 // compiler reports 170 VGPRs for the forward and 200 for the backward kernel, no scratch: at four to six wavefronts per CU it
 // is LDS, not registers, that bounds the occupancy.
-#include "framed.h"
+#include "criterion.h"
 #include "../../include/flamo_hip_mrstft.h"
 
 namespace fl {
@@ -41,8 +41,12 @@ using C = double;
 
 constexpr int MAXR = 8, NFFT_MIN = 256, NFFT_MAX = 2048, NTW = 2048;
 constexpr int NC_MAX = NFFT_MAX / 2, ALDS = NC_MAX + 64, NB_MAX = NC_MAX + 1;
-constexpr long T_MAX = 1L << 30, BLOCKS_MAX = (1L << 31) - 1, SAMPLES_MAX = 1L << 38;
+constexpr long BLOCKS_MAX = (1L << 31) - 1, SAMPLES_MAX = 1L << 38;
 constexpr int KEEP_STRIDE = 8, KEEP_LOSS = KEEP_STRIDE * MAXR, KEEP_DOUBLES = KEEP_LOSS + 1;
+
+using framed::Strides;
+using framed::power;
+using framed::row_offset;
 
 struct Res : framed::Frame {
     int nfft;
@@ -56,13 +60,9 @@ struct Plan {
     long B, T, N, rows, blocks, gelems;
     Res r[MAXR];
 };
-struct Strides {
-    long b, t, c;
-};
 
 static bool make_plan(long B, long T, long N, int R, const int* res, Plan& p) {
-    if (!res || R < 1 || R > MAXR || B < 1 || N < 1 || T < 1 || T > T_MAX) return false;
-    if (B > SAMPLES_MAX / T || B * T > SAMPLES_MAX / N) return false;
+    if (!res || R < 1 || R > MAXR || !framed::signal_sizes(B, T, N, SAMPLES_MAX)) return false;
     p.R = R; p.B = B; p.T = T; p.N = N; p.rows = B * N;
     long blocks = 0, g = 0, w = 0;
     for (int r = 0; r < R; ++r) {
@@ -70,9 +70,9 @@ static bool make_plan(long B, long T, long N, int R, const int* res, Plan& p) {
         if (nfft < NFFT_MIN || nfft > NFFT_MAX || (nfft & (nfft - 1)) || hop < 1 || win < 1 || win > nfft || T <= nfft / 2) return false;
         Res& q = p.r[r];
         q.nfft = nfft; q.hop = hop; q.win = win; q.lpad = (nfft - win) / 2;
-        q.F = 1 + T / hop;
+        q.F = framed::frames_per_row(T, hop, p.rows, BLOCKS_MAX);
+        if (q.F < 0) return false;
         q.blk0 = blocks; q.g0 = g; q.w0 = w;
-        if (q.F > BLOCKS_MAX / p.rows) return false;
         blocks += p.rows * q.F;
         if (blocks > BLOCKS_MAX) return false;
         g += p.rows * q.F * win;
@@ -82,8 +82,6 @@ static bool make_plan(long B, long T, long N, int R, const int* res, Plan& p) {
     return true;
 }
 
-__device__ inline double power(cx<C> x) { return x.x * x.x + x.y * x.y; }
-
 // (resolution, row, frame) of a workgroup
 __device__ inline void locate(const Plan& p, long blk, int& r, long& row, long& f) {
     r = p.R - 1;
@@ -91,11 +89,6 @@ __device__ inline void locate(const Plan& p, long blk, int& r, long& row, long& 
     const long local = blk - p.r[r].blk0;
     row = local / p.r[r].F;
     f = local - row * p.r[r].F;
-}
-
-__device__ inline long row_offset(const Plan& p, long row, Strides s) {
-    const long b = row / p.N, c = row - b * p.N;
-    return b * s.b + c * s.c;
 }
 
 // ---------------------------------------------------------------- forward: the four sums of a frame
@@ -150,27 +143,6 @@ __global__ void __launch_bounds__(64) mrstft_frames_kernel(const T* __restrict__
         case 1024: frame_sums<T, 8>(a, sp.t, b, st.t, p.T, f, q, w, tw, eps, A, Sp, out, lane); break;
         default: frame_sums<T, 16>(a, sp.t, b, st.t, p.T, f, q, w, tw, eps, A, Sp, out, lane); break;
     }
-}
-
-// ---------------------------------------------------------------- combine: one workgroup per resolution, a fixed order
-__global__ void __launch_bounds__(256) mrstft_combine_kernel(const double* __restrict__ partial, Plan p, double* __restrict__ keep) {
-    __shared__ double red[4][4];
-    const int r = blockIdx.x;
-    const long n = p.rows * p.r[r].F;
-    const double* q = partial + 4 * p.r[r].blk0;
-    double s[4] = {0.0, 0.0, 0.0, 0.0};
-    for (long i = threadIdx.x; i < n; i += 256) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) s[c] += q[4 * i + c];
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        s[c] = wave_sum(s[c]);
-        if (lane == 0) red[c][wave] = s[c];
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) keep[KEEP_STRIDE * r + threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
 }
 
 // one thread: the loss and, per resolution, the factors of dL/dM_p = c0 (M_p - M_t) + c1 sign / M_p + c2 sign
@@ -252,24 +224,6 @@ __global__ void __launch_bounds__(64) mrstft_frames_bwd_kernel(const T* __restri
     }
 }
 
-// ---------------------------------------------------------------- overlap-add: a gather per sample, in a fixed order
-template <typename T>
-__global__ void __launch_bounds__(256) mrstft_ola_kernel(const T* __restrict__ gframes, Plan p, const T* __restrict__ gloss,
-                                                        T* __restrict__ gy) {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= p.rows * p.T) return;
-    const long row = e / p.T, t = e - row * p.T;
-    double acc = 0.0;
-    for (int r = 0; r < p.R; ++r) {
-        const Res& q = p.r[r];
-        const int half = q.nfft / 2;
-        const T* g = gframes + q.g0 + row * q.F * q.win;
-        framed::gather_sample(g, t, p.T, half, q, q.F - 1, acc);
-    }
-    const long b = row / p.N, c = row - b * p.N;
-    gy[(b * p.T + t) * p.N + c] = (T)((double)gloss[0] * acc);
-}
-
 }  // namespace mrstft
 }  // namespace fl
 
@@ -305,8 +259,9 @@ FL_ENTRY_F32_F64(fl_mrstft_fwd, (const void* yp, long spb, long spt, long spc, c
                        Strides{spb, spt, spc}, (const T*)yt, Strides{stb, stt, stc}, p, (const C*)wtab, (const cx<C>*)tw, eps,
                        (double*)partial);
     FL_CHECK_LAUNCH("mrstft_frames");
-    hipLaunchKernelGGL(mrstft_combine_kernel, dim3((unsigned)p.R), dim3(256), 0, (hipStream_t)stream, (const double*)partial, p,
-                       (double*)keep);
+    const framed::Spans sums = framed::spans_of(p, [](const Res& q) { return q.blk0; }, [&](const Res& q) { return p.rows * q.F; });
+    hipLaunchKernelGGL((framed::combine_kernel<4, KEEP_STRIDE>), dim3((unsigned)p.R), dim3(256), 0, (hipStream_t)stream,
+                       (const double*)partial, sums, (double*)keep);
     FL_CHECK_LAUNCH("mrstft_combine");
     hipLaunchKernelGGL((mrstft_final_kernel<T>), dim3(1), dim3(64), 0, (hipStream_t)stream, p, w_sc, w_log, w_lin, (double*)keep,
                        (T*)loss);
@@ -327,7 +282,7 @@ FL_ENTRY_F32_F64(fl_mrstft_bwd, (const void* yp, long spb, long spt, long spc, c
                        (const double*)keep, (T*)gframes);
     FL_CHECK_LAUNCH("mrstft_frames_bwd");
     const long blocks = (p.rows * p.T + 255) / 256;
-    hipLaunchKernelGGL((mrstft_ola_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const T*)gframes, p,
+    hipLaunchKernelGGL((framed::ola_kernel<T, Plan>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const T*)gframes, p,
                        (const T*)gloss, (T*)gy);
     FL_CHECK_LAUNCH("mrstft_ola");
     return FL_OK;

@@ -20,22 +20,22 @@
 //
 // Forward tiles.  A workgroup of four wavefronts takes 16 frames x 256 bins; the frames' windowed samples are staged 64 at a
 // time in LDS (two buffers: the next chunk is loaded while this one is multiplied, one barrier per chunk) straight from the
-// signal through its strides and the reflection.  Prediction and target run through ONE loop body (`both_signals`): equal
-// signals give equal M to the bit, and an exact 0 for the loss and every sign.  With `planes` the prediction's X and the
-// target's M go to `keep` -- recomputing an O(n^2) transform in the backward pass would triple its work.  A workgroup leaves
-// six sums; combine and final as in melmss.hip.
+// signal through its strides and the reflection.  Prediction and target run through ONE loop body (`both_signals` of
+// criterion.h): equal signals give equal M to the bit, and an exact 0 for the loss and every sign.  With `planes` the
+// prediction's X and the target's M go to `keep` -- recomputing an O(n^2) transform in the backward pass would triple its
+// work.  A workgroup leaves six sums; the combine is criterion.h's, the final kernel as in melmss.hip.
 //
 // Adjoint tiles.  A workgroup takes 16 frames x 512 samples of the frame; G = dL/dM_p X_p / M_p (0 where M_p is 0) is formed
 // from the kept planes 64 bins at a time in LDS, and gframe[f, j] = w_j sum_k (Re G cos(theta_k j) - Im G sin(theta_k j)) runs
 // on the same instruction with the bins as the contracted index: a lane owns one sample per tile and the bin offset lane >> 4,
 // advances by four bins with exp(+i (theta_4 - theta_0) j) and starts again every 64 bins from exp(+i theta_{64 m} j).  The
-// overlap-add is framed::gather_sample per sample.
+// overlap-add is criterion.h's, framed::gather_sample per sample.
 //
 // Precision.  As in mrstft.hip, edr.hip and melmss.hip: the signals, the frame gradients and the gradient have the signals'
 // type, everything between is a double in float32 too.
 //
 // Resources (the compiler's report for gfx950 is in DESIGN 4.6): LDS 17.5 KB forward, 35 KB backward; no scratch.
-#include "framed.h"
+#include "criterion.h"
 #include "../../include/flamo_hip_mss.h"
 
 #include <math.h>
@@ -52,9 +52,15 @@ constexpr int FWD_TILES = 4, FWD_BINS = 4 * 16 * FWD_TILES;           // bins of
 constexpr int BWD_TILES = 8, BWD_SAMPLES = 4 * 16 * BWD_TILES;        // samples of an adjoint workgroup
 // every launch stays under 2^32 threads (a grid of more has been refused by the runtime): the tile grids have at most 2^24 - 1
 // workgroups of 256, the overlap-add one thread per sample.  (Far beyond any memory: 2^24 tiles keep over 100 GB of planes.)
-constexpr long T_MAX = 1L << 30, FRAMES_MAX = (1L << 31) - 1, BLOCKS_MAX = (1L << 24) - 1, SAMPLES_MAX = (1L << 32) - 256;
+constexpr long FRAMES_MAX = (1L << 31) - 1, BLOCKS_MAX = (1L << 24) - 1, SAMPLES_MAX = (1L << 32) - 256;
 constexpr int NSUM = 6;      // sum mask d^2, sum mask |d|, the same two of the log difference, sum mask, sum M_t^2
 constexpr int KEEP_STRIDE = 8, KEEP_C0 = 6, KEEP_C1 = 7, KEEP_LOSS = KEEP_STRIDE * MAXR, KEEP_HEAD = KEEP_LOSS + 1;
+
+using framed::Strides;
+using framed::sign;
+using framed::row_offset;
+using framed::snr_mask;      // (of a magnitude here)
+using framed::both_signals;
 
 struct Res : framed::Frame {
     int nfft, K, NJ, NK;     // bins, chunks of 64 samples, chunks of 64 bins
@@ -70,9 +76,6 @@ struct Plan {
     int R;
     long B, T, N, rows, frames, gelems, blocks, bblocks, tabdoubles, planedoubles;
     Res r[MAXR];
-};
-struct Strides {
-    long b, t, c;
 };
 struct Opt {
     int lin_norm, log_norm, apply_mask, form;      // log_norm 0: no log term
@@ -102,16 +105,15 @@ static bool make_tables(int R, const int* res, Plan& p) {
 }
 
 static bool make_plan(long B, long T, long N, int R, const int* res, Plan& p) {
-    if (!make_tables(R, res, p) || B < 1 || N < 1 || T < 1 || T > T_MAX) return false;
-    if (B > SAMPLES_MAX / T || B * T > SAMPLES_MAX / N) return false;
+    if (!make_tables(R, res, p) || !framed::signal_sizes(B, T, N, SAMPLES_MAX)) return false;
     p.B = B; p.T = T; p.N = N; p.rows = B * N;
     long frames = 0, g = 0, planes = 0;
     for (int r = 0; r < R; ++r) {
         Res& q = p.r[r];
         if (T <= q.nfft / 2) return false;
-        q.F = 1 + T / q.hop;
+        q.F = framed::frames_per_row(T, q.hop, p.rows, FRAMES_MAX);
+        if (q.F < 0) return false;
         q.ft = (q.F + FT - 1) / FT;
-        if (q.F > FRAMES_MAX / p.rows) return false;
         q.g0 = g; q.p0 = planes;
         frames += p.rows * q.F;
         if (frames > FRAMES_MAX) return false;
@@ -154,38 +156,9 @@ __device__ inline void locate(const Plan& p, long blk, int& r, long& row, long& 
     ft = tile - row * q.ft;
 }
 
-__device__ inline long row_offset(const Plan& p, long row, Strides s) {
-    const long b = row / p.N, c = row - b * p.N;
-    return b * s.b + c * s.c;
-}
-
 // |X|, the same instructions wherever it is formed: the forward pass keeps M_t and the backward pass forms M_p again from the
 // kept X_p, and for equal signals the two must be equal to the bit
 __device__ inline double magnitude(double re, double im) { return sqrt(fma(re, re, im * im)); }
-
-// 1 where the target's magnitude stands `threshold` dB over the noise energy, else 0 (a NaN keeps its entry, as the comparison
-// SNR < threshold of the definition does)
-__device__ inline double snr_mask(double mt, const Opt& o) {
-    if (!o.apply_mask) return 1.0;
-    const double snr = 10.0 * log10(fmax(mt * mt, o.ne * 1.01) - o.ne) - 10.0 * log10(o.ne);
-    return snr < o.threshold ? 0.0 : 1.0;
-}
-
-__device__ inline double sign(double d) { return d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : 0.0); }
-
-// Runs body(0, .) and then body(1, .) as ONE loop body that is not unrolled, and hands back the NB values each left (see the
-// note of the same name in melmss.hip: two inlined copies of one source are not held to the same contractions).
-template <int NB, class Body>
-__device__ inline void both_signals(double (&first)[NB], double (&second)[NB], Body&& body) {
-#pragma clang loop unroll(disable)
-    for (int sig = 0; sig < 2; ++sig) {
-        if (sig) {
-#pragma unroll
-            for (int i = 0; i < NB; ++i) first[i] = second[i];
-        }
-        body(sig, second);
-    }
-}
 
 // ---------------------------------------------------------------- forward: 16 frames x 256 bins per workgroup
 template <typename T>
@@ -332,27 +305,6 @@ mss_tile_kernel(const T* __restrict__ yp, Strides sp, const T* __restrict__ yt, 
     }
     __syncthreads();
     if (tid < NSUM) partial[NSUM * (long)blockIdx.x + tid] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
-}
-
-// ---------------------------------------------------------------- combine: one workgroup per resolution, a fixed order
-__global__ void __launch_bounds__(256) mss_combine_kernel(const double* __restrict__ partial, Plan p, double* __restrict__ keep) {
-    __shared__ double red[NSUM][4];
-    const int r = blockIdx.x;
-    const long n = p.r[r].nblk;
-    const double* q = partial + NSUM * p.r[r].blk0;
-    double s[NSUM] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (long i = threadIdx.x; i < n; i += 256) {
-#pragma unroll
-        for (int c = 0; c < NSUM; ++c) s[c] += q[NSUM * i + c];
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < NSUM; ++c) {
-        s[c] = wave_sum(s[c]);
-        if (lane == 0) red[c][wave] = s[c];
-    }
-    __syncthreads();
-    if (threadIdx.x < NSUM) keep[KEEP_STRIDE * r + threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
 }
 
 // one thread: the loss and, per resolution, the factors of dL/dM_p = -mask (c0 gd + c1 gl / M_p), gd = d under a 2-norm and
@@ -510,22 +462,6 @@ mss_adjoint_kernel(Plan p, const double* __restrict__ tab, Opt o, const double* 
     }
 }
 
-// ---------------------------------------------------------------- overlap-add: a gather per sample, in a fixed order
-template <typename T>
-__global__ void __launch_bounds__(256) mss_ola_kernel(const T* __restrict__ gframes, Plan p, const T* __restrict__ gloss, T* __restrict__ gy) {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= p.rows * p.T) return;
-    const long row = e / p.T, t = e - row * p.T;
-    double acc = 0.0;
-    for (int r = 0; r < p.R; ++r) {
-        const Res& q = p.r[r];
-        const T* g = gframes + q.g0 + row * q.F * q.win;
-        framed::gather_sample(g, t, p.T, q.nfft / 2, q, q.F - 1, acc);
-    }
-    const long b = row / p.N, c = row - b * p.N;
-    gy[(b * p.T + t) * p.N + c] = (T)((double)gloss[0] * acc);
-}
-
 }  // namespace mss
 }  // namespace fl
 
@@ -583,8 +519,9 @@ FL_ENTRY_F32_F64(fl_mss_fwd, (const void* yp, long spb, long spt, long spc, cons
     hipLaunchKernelGGL((mss_tile_kernel<T>), dim3((unsigned)p.blocks), dim3(NT), 0, (hipStream_t)stream, (const T*)yp, sp, (const T*)yt,
                        st, p, (const double*)tab, o, planes ? 1 : 0, (double*)partial, (double*)keep);
     FL_CHECK_LAUNCH("mss_tile");
-    hipLaunchKernelGGL(mss_combine_kernel, dim3((unsigned)p.R), dim3(256), 0, (hipStream_t)stream, (const double*)partial, p,
-                       (double*)keep);
+    const framed::Spans sums = framed::spans_of(p, [](const Res& q) { return q.blk0; }, [](const Res& q) { return q.nblk; });
+    hipLaunchKernelGGL((framed::combine_kernel<NSUM, KEEP_STRIDE>), dim3((unsigned)p.R), dim3(256), 0, (hipStream_t)stream,
+                       (const double*)partial, sums, (double*)keep);
     FL_CHECK_LAUNCH("mss_combine");
     hipLaunchKernelGGL((mss_final_kernel<T>), dim3(1), dim3(64), 0, (hipStream_t)stream, p, o, (double*)keep, (T*)loss);
     FL_CHECK_LAUNCH("mss_final");
@@ -602,7 +539,7 @@ FL_ENTRY_F32_F64(fl_mss_bwd, (long B, long Tn, long N, int R, int* res, const vo
                        (const double*)keep, (T*)gframes);
     FL_CHECK_LAUNCH("mss_adjoint");
     const long blocks = (p.rows * p.T + 255) / 256;
-    hipLaunchKernelGGL((mss_ola_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const T*)gframes, p,
+    hipLaunchKernelGGL((framed::ola_kernel<T, Plan>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const T*)gframes, p,
                        (const T*)gloss, (T*)gy);
     FL_CHECK_LAUNCH("mss_ola");
     return FL_OK;

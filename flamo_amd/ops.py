@@ -2892,7 +2892,7 @@ def _filterbank_consts(bank, dev: torch.device):
     of the bank) and kept on the bank, whose setters drop them.  Never uploaded during a graph capture: a copy from pageable
     host memory cannot be captured, so the bank has to have run on the device before."""
     state, K, _, rec = bank.band_constants()
-    key = dev.index if dev.index is not None else torch.cuda.current_device()
+    key = _dev_index(dev)
     ent = bank._device_consts.get(key)
     if ent is None or ent[0] != state:
         if torch.cuda.is_current_stream_capturing():
@@ -3044,7 +3044,7 @@ _avgpow_windows = {}
 def _avgpow_consts(real: torch.dtype, dev: torch.device):
     """(w, h, twiddles) on the device, cached per (device, precision): w = torch.hann_window(1024), which the reference builds
     without a dtype -- float32 VALUES also under a float64 signal -- and h = torch.hann_window(64) in the signal's precision"""
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), real)
+    key = (_dev_index(dev), real)
     ent = _avgpow_windows.get(key)
     if ent is None:
         w = torch.hann_window(AVGPOW_NFFT).to(device=dev, dtype=real)
@@ -3133,6 +3133,87 @@ def average_power(y_pred: torch.Tensor, y_true: torch.Tensor, stride: Tuple[int,
     return _AveragePower.apply(y_pred, t, si, sj)
 
 
+# ---- one layer over the fl_mrstft_*, fl_edr_*, fl_melmss_* and fl_mss_* entries, each called from ONE place (the forward and the
+# ---- backward of _MRSTFT, _EDR, _MelMSS and _MSS); what the four criteria ask alike is stated once: the signals (_check_signals),
+# ---- a shape or a frame as integers (_int_dims), the resolutions of the multi-scale pair and their norm (_resolution_frames,
+# ---- _norm_code), the mask's options (_mask_options), a host int array (_c_ints), the device of a cache key (_dev_index, also
+# ---- the filter bank's and the average power's) and the buffers of a backward pass (_grad_buffers)
+def _dev_index(dev: torch.device) -> int:
+    """the device's part of a cache key: its index, the current device's when it has none"""
+    return dev.index if dev.index is not None else torch.cuda.current_device()
+
+
+def _check_signals(name, y_pred, y_true, torch_lines):
+    """what a criterion asks of (prediction, target): non-empty real (B, T, N) signals of one shape and precision, the target
+    without a gradient -- ``torch_lines`` names whose torch lines take one that has"""
+    if y_pred.dim() != 3 or y_pred.dtype not in (torch.float32, torch.float64) or y_pred.numel() == 0:
+        raise ValueError(f"{name}: a non-empty real float32 / float64 (B, T, N) signal, got {tuple(y_pred.shape)} {y_pred.dtype}")
+    if tuple(y_true.shape) != tuple(y_pred.shape) or y_true.dtype != y_pred.dtype:
+        raise ValueError(f"{name}: prediction {tuple(y_pred.shape)} {y_pred.dtype} and target {tuple(y_true.shape)} "
+                         f"{y_true.dtype} differ")
+    if y_true.requires_grad:
+        raise ValueError(f"{name}: the target takes no gradient here (detach it, or use {torch_lines}'s torch lines)")
+
+
+def _int_dims(values, bound=1 << 62):
+    """three integers -- a (B, T, N) shape, a frame (n_fft, hop, win) -- as an int triple, each under ``bound`` in size, or None
+    when they are not"""
+    try:
+        dims = tuple(int(v) for v in values)
+        same = all(a == b for a, b in zip(dims, tuple(values)))
+    except (TypeError, ValueError):
+        return None
+    return dims if same and len(dims) == 3 and max(map(abs, dims)) < bound else None
+
+
+def _c_ints(values):
+    """the integers as the host int array an entry's ``int*`` takes"""
+    flat = list(values)
+    return (ctypes.c_int * len(flat))(*flat)
+
+
+def _resolution_frames(nfft, overlap):
+    """((n_fft, hop), ...) with hop = int(n_fft (1 - overlap)) as a tuple of int pairs, or None when ``nfft`` is not a
+    sequence of integers or ``overlap`` not a number"""
+    try:
+        ns = tuple(int(n) for n in nfft)
+        same = len(ns) == len(tuple(nfft)) and all(a == b for a, b in zip(ns, nfft))
+        hops = tuple(int(n * (1 - overlap)) for n in ns)
+    except (TypeError, ValueError, OverflowError):
+        return None
+    if not same or any(abs(v) >= 1 << 31 for v in ns + hops):
+        return None
+    return tuple(zip(ns, hops))
+
+
+def _norm_code(p):
+    """``p`` ("fro", 2, 1) as the kernels' norm (2, 2, 1), or None"""
+    try:
+        return MELMSS_NORMS.get(p)
+    except TypeError:
+        return None
+
+
+def _mask_options(name, alpha, threshold, apply_mask, noise_energy, finite):
+    """(alpha, threshold, noise energy) as floats; with ``apply_mask`` the noise energy has to be a number > 0, and with
+    ``finite`` (mss_loss asks it, mel_mss_loss does not) a finite one.  Without the mask it is 1."""
+    try:
+        alpha, threshold = float(alpha), float(threshold)
+        ne = 1.0 if not apply_mask else float(noise_energy)
+    except (TypeError, ValueError):
+        ne = float("nan")
+    if not (ne > 0.0 and (math.isfinite(ne) or not finite)):
+        raise ValueError(f"{name}: apply_mask needs a {'finite ' if finite else ''}noise_energy > 0 (a number: the class derives "
+                         f"it from the target when it is None), got {noise_energy!r}")
+    return alpha, threshold, ne
+
+
+def _grad_buffers(gframe_elems, shape, gloss, real, dev):
+    """(the frames' gradients, the gradient of the (B, T, N) prediction, the loss's cotangent as the kernels read it) of a
+    backward pass"""
+    return torch.empty(gframe_elems, dtype=real, device=dev), torch.empty(shape, dtype=real, device=dev), _gloss_as(gloss, real)
+
+
 MRSTFT_MAX_RES, MRSTFT_NFFTS, MRSTFT_MAX_T = 8, (256, 512, 1024, 2048), 1 << 30      # what csrc/mrstft.hip takes
 MRSTFT_NTW = 2048                                                                  # its one twiddle table
 _mrstft_tables = {}
@@ -3171,12 +3252,11 @@ def _mrstft_consts(res, dev: torch.device):
     """(windows, twiddles, the resolutions as a host int array) cached per (resolutions, device): the periodic Hann windows of
     the resolutions, one behind the other, made on the host -- float64 like the twiddles under either precision of the
     signals, since the kernels transform in double"""
-    key = (res, dev.index if dev.index is not None else torch.cuda.current_device())
+    key = (res, _dev_index(dev))
     ent = _mrstft_tables.get(key)
     if ent is None:
         w = torch.cat([torch.hann_window(win, dtype=torch.float64) for _, _, win in res]).to(dev)
-        flat = [v for r in res for v in r]
-        ent = _mrstft_tables[key] = (w, (ctypes.c_int * len(flat))(*flat))
+        ent = _mrstft_tables[key] = (w, _c_ints(v for r in res for v in r))
     return ent[0], twiddles(MRSTFT_NTW, torch.float64, dev), ent[1]
 
 
@@ -3212,9 +3292,7 @@ class _MRSTFT(torch.autograd.Function):
         B, T, N = y.shape
         w, tw, cres = _mrstft_consts(res, y.device)
         R = len(res)
-        gframes = torch.empty(L.fl_mrstft_gframe_elems(B, T, N, R, cres), dtype=y.dtype, device=y.device)
-        gy = torch.empty((B, T, N), dtype=y.dtype, device=y.device)
-        g = _gloss_as(gloss, y.dtype)
+        gframes, gy, g = _grad_buffers(L.fl_mrstft_gframe_elems(B, T, N, R, cres), (B, T, N), gloss, y.dtype, y.device)
         with kernel_timer.span("mrstft_bwd"):
             _lib.check(_fn("fl_mrstft_bwd", y.dtype)(y.data_ptr(), *y.stride(), t.data_ptr(), *t.stride(), B, T, N, R, cres,
                                                      w.data_ptr(), tw.data_ptr(), eps, keep.data_ptr(), g.data_ptr(),
@@ -3232,13 +3310,7 @@ def mrstft_loss(y_pred: torch.Tensor, y_true: torch.Tensor, resolutions=((1024, 
     whatever the number of resolutions; the signals are read through their strides, nothing is copied, nothing is read back.
     The target takes no gradient.  Sizes: ``mrstft_supported``."""
     _require_gpu(y_pred, y_true)
-    if y_pred.dim() != 3 or y_pred.dtype not in (torch.float32, torch.float64) or y_pred.numel() == 0:
-        raise ValueError(f"mrstft_loss: a non-empty real float32 / float64 (B, T, N) signal, got {tuple(y_pred.shape)} {y_pred.dtype}")
-    if tuple(y_true.shape) != tuple(y_pred.shape) or y_true.dtype != y_pred.dtype:
-        raise ValueError(f"mrstft_loss: prediction {tuple(y_pred.shape)} {y_pred.dtype} and target {tuple(y_true.shape)} "
-                         f"{y_true.dtype} differ")
-    if y_true.requires_grad:
-        raise ValueError("mrstft_loss: the target takes no gradient here (detach it, or use MultiResoSTFT's torch lines)")
+    _check_signals("mrstft_loss", y_pred, y_true, "MultiResoSTFT")
     res = _mrstft_resolutions(resolutions)
     if res is None or not mrstft_supported(tuple(y_pred.shape), res, eps):
         raise ValueError(f"mrstft_loss: resolutions {resolutions!r} on T = {y_pred.shape[1]}: 1 to {MRSTFT_MAX_RES} triples "
@@ -3308,12 +3380,8 @@ def _edr_mel_tables(W: np.ndarray):
 def edr_supported(shape, nfft, hop, win) -> bool:
     """whether ``edr_loss`` takes (B, T, N) signals under these frames: nfft a power of two from 256 to 2048,
     1 <= win <= nfft, hop >= 1, nfft / 2 < T <= 2^30, fewer than 2^31 frames and at most 2^38 samples in all"""
-    try:
-        dims, frame = tuple(int(s) for s in shape), tuple(int(v) for v in (nfft, hop, win))
-        same = all(a == b for a, b in zip(dims + frame, tuple(shape) + (nfft, hop, win)))
-    except (TypeError, ValueError):
-        return False
-    if not same or len(dims) != 3 or max(map(abs, dims)) >= 1 << 62 or max(map(abs, frame)) >= 1 << 31:
+    dims, frame = _int_dims(shape), _int_dims((nfft, hop, win), 1 << 31)
+    if dims is None or frame is None:
         return False
     return _lib.lib().fl_edr_frames(*dims, *frame) >= 0      # the library's own support query: one statement of the sizes
 
@@ -3321,7 +3389,7 @@ def edr_supported(shape, nfft, hop, win) -> bool:
 def _edr_consts(sample_rate, nfft, win, dev: torch.device):
     """(window, twiddles, melidx, melw, nnz) cached per (sample_rate, nfft, win, device): the periodic Hann window and the mel
     tables, made on the host in float64 under either precision of the signals"""
-    key = (sample_rate, nfft, win, dev.index if dev.index is not None else torch.cuda.current_device())
+    key = (sample_rate, nfft, win, _dev_index(dev))
     ent = _edr_tables.get(key)
     if ent is None:
         melidx, melw, nnz = _edr_mel_tables(mel_basis(sample_rate, nfft, EDR_BANDS, EDR_FMIN, sample_rate // 2).numpy())
@@ -3367,9 +3435,7 @@ class _EDR(torch.autograd.Function):
         B, T, N = y.shape
         w, tw, melidx, melw, nnz = _edr_consts(sample_rate, nfft, win, y.device)
         gmel = torch.empty_like(kept)
-        gframes = torch.empty(L.fl_edr_gframe_elems(B, T, N, nfft, hop, win), dtype=y.dtype, device=y.device)
-        gy = torch.empty((B, T, N), dtype=y.dtype, device=y.device)
-        g = _gloss_as(gloss, y.dtype)
+        gframes, gy, g = _grad_buffers(L.fl_edr_gframe_elems(B, T, N, nfft, hop, win), (B, T, N), gloss, y.dtype, y.device)
         with kernel_timer.span("edr_bwd"):
             _lib.check(_fn("fl_edr_bwd", y.dtype)(y.data_ptr(), *y.stride(), B, T, N, nfft, hop, win, w.data_ptr(), tw.data_ptr(),
                                                   melidx.data_ptr(), melw.data_ptr(), nnz, mel.data_ptr(), kept.data_ptr(),
@@ -3388,13 +3454,7 @@ def edr_loss(y_pred: torch.Tensor, y_true: torch.Tensor, nfft: int = 1024, hop: 
     read through their strides, nothing is copied, nothing is read back.  The target takes no gradient.  Sizes:
     ``edr_supported``."""
     _require_gpu(y_pred, y_true)
-    if y_pred.dim() != 3 or y_pred.dtype not in (torch.float32, torch.float64) or y_pred.numel() == 0:
-        raise ValueError(f"edr_loss: a non-empty real float32 / float64 (B, T, N) signal, got {tuple(y_pred.shape)} {y_pred.dtype}")
-    if tuple(y_true.shape) != tuple(y_pred.shape) or y_true.dtype != y_pred.dtype:
-        raise ValueError(f"edr_loss: prediction {tuple(y_pred.shape)} {y_pred.dtype} and target {tuple(y_true.shape)} "
-                         f"{y_true.dtype} differ")
-    if y_true.requires_grad:
-        raise ValueError("edr_loss: the target takes no gradient here (detach it, or use optimize.edr_loss's torch lines)")
+    _check_signals("edr_loss", y_pred, y_true, "optimize.edr_loss")
     if not edr_supported(tuple(y_pred.shape), nfft, hop, win):
         raise ValueError(f"edr_loss: frames (nfft, hop, win) = {(nfft, hop, win)!r} on T = {y_pred.shape[1]}: nfft a power of "
                          f"two from 256 to 2048, 1 <= win <= nfft, hop >= 1, nfft / 2 < T <= 2^30 and fewer than 2^31 frames in all")
@@ -3407,27 +3467,6 @@ MELMSS_MAX_RES, MELMSS_NFFTS, MELMSS_NTW = 8, (128, 256, 512, 1024, 2048, 4096),
 MELMSS_NORMS = {"fro": 2, 2: 2, 1: 1}                                                      # ``p`` -> the kernels' norm
 _melmss_host_tables = {}
 _melmss_tables = {}
-
-
-def _melmss_frames(nfft, overlap):
-    """((n_fft, hop), ...) with hop = int(n_fft (1 - overlap)) as a tuple of int pairs, or None when ``nfft`` is not a
-    sequence of integers or ``overlap`` not a number"""
-    try:
-        ns = tuple(int(n) for n in nfft)
-        same = len(ns) == len(tuple(nfft)) and all(a == b for a, b in zip(ns, nfft))
-        hops = tuple(int(n * (1 - overlap)) for n in ns)
-    except (TypeError, ValueError, OverflowError):
-        return None
-    if not same or any(abs(v) >= 1 << 31 for v in ns + hops):
-        return None
-    return tuple(zip(ns, hops))
-
-
-def _melmss_norm(p):
-    try:
-        return MELMSS_NORMS.get(p)
-    except TypeError:
-        return None
 
 
 def _melmss_host(sample_rate, nffts):
@@ -3445,21 +3484,13 @@ def mel_mss_supported(shape, nfft=MELMSS_NFFTS, overlap=0.75, sample_rate=48000,
     """whether ``mel_mss_loss`` takes (B, T, N) signals under these resolutions: 1 to 8 of them, n_fft a power of two from 128
     to 4096, hop = int(n_fft (1 - overlap)) >= 1, n_fft / 2 < T <= 2^30, fewer than 2^31 frames and at most 2^38 samples in
     all, ``p`` in "fro", 2, 1, and a sample rate whose mel bases keep every bin in at most two consecutive bands"""
-    frames = _melmss_frames(nfft, overlap)
-    try:
-        dims = tuple(int(s) for s in shape)
-        same = all(a == b for a, b in zip(dims, tuple(shape)))
-    except (TypeError, ValueError):
-        return False
-    if frames is None or not same or len(dims) != 3 or max(map(abs, dims)) >= 1 << 62 or not 1 <= len(frames) <= MELMSS_MAX_RES:
-        return False
-    if _melmss_norm(p) is None:
+    frames, dims = _resolution_frames(nfft, overlap), _int_dims(shape)
+    if frames is None or dims is None or not 1 <= len(frames) <= MELMSS_MAX_RES or _norm_code(p) is None:
         return False
     if not (isinstance(sample_rate, (int, float)) and math.isfinite(sample_rate) and sample_rate // 2 > 0):
         return False
-    flat = [v for n, hop in frames for v in (n, hop, 0)]
     # the library's own support query: one statement of the sizes
-    if _lib.lib().fl_melmss_frames(*dims, len(frames), (ctypes.c_int * len(flat))(*flat)) < 0:
+    if _lib.lib().fl_melmss_frames(*dims, len(frames), _c_ints(v for n, hop in frames for v in (n, hop, 0))) < 0:
         return False
     try:
         _melmss_host(sample_rate, tuple(n for n, _ in frames))
@@ -3472,12 +3503,11 @@ def _melmss_consts(frames, sample_rate, dev: torch.device):
     """(windows, twiddles, melidx, melw, the resolutions as a host int array of (n_fft, hop, nnz)) cached per (resolutions,
     sample_rate, device): the periodic Hann windows and the mel tables of the resolutions, one behind the other, made on the
     host in float64 under either precision of the signals"""
-    key = (frames, sample_rate, dev.index if dev.index is not None else torch.cuda.current_device())
+    key = (frames, sample_rate, _dev_index(dev))
     ent = _melmss_tables.get(key)
     if ent is None:
         host = _melmss_host(sample_rate, tuple(n for n, _ in frames))
-        flat = [v for (n, hop), (_, _, nnz) in zip(frames, host) for v in (n, hop, nnz)]
-        cres = (ctypes.c_int * len(flat))(*flat)
+        cres = _c_ints(v for (n, hop), (_, _, nnz) in zip(frames, host) for v in (n, hop, nnz))
         melidx = np.concatenate([h[0] for h in host])
         melw = np.concatenate([h[1] for h in host])
         L = _lib.lib()
@@ -3522,9 +3552,7 @@ class _MelMSS(torch.autograd.Function):
         w, tw, melidx, melw, cres = _melmss_consts(frames, sample_rate, y.device)
         R = len(frames)
         norm, log_term, _, apply_mask, threshold, ne = opts
-        gframes = torch.empty(L.fl_melmss_gframe_elems(B, T, N, R, cres), dtype=y.dtype, device=y.device)
-        gy = torch.empty((B, T, N), dtype=y.dtype, device=y.device)
-        g = _gloss_as(gloss, y.dtype)
+        gframes, gy, g = _grad_buffers(L.fl_melmss_gframe_elems(B, T, N, R, cres), (B, T, N), gloss, y.dtype, y.device)
         with kernel_timer.span("melmss_bwd"):
             _lib.check(_fn("fl_melmss_bwd", y.dtype)(y.data_ptr(), *y.stride(), t.data_ptr(), *t.stride(), B, T, N, R, cres,
                                                      w.data_ptr(), tw.data_ptr(), melidx.data_ptr(), melw.data_ptr(), norm,
@@ -3546,32 +3574,19 @@ def mel_mss_loss(y_pred: torch.Tensor, y_true: torch.Tensor, nfft=MELMSS_NFFTS, 
     are read through their strides, nothing is copied, nothing is read back.  The target takes no gradient.  Sizes:
     ``mel_mss_supported``."""
     _require_gpu(y_pred, y_true)
-    if y_pred.dim() != 3 or y_pred.dtype not in (torch.float32, torch.float64) or y_pred.numel() == 0:
-        raise ValueError(f"mel_mss_loss: a non-empty real float32 / float64 (B, T, N) signal, got {tuple(y_pred.shape)} {y_pred.dtype}")
-    if tuple(y_true.shape) != tuple(y_pred.shape) or y_true.dtype != y_pred.dtype:
-        raise ValueError(f"mel_mss_loss: prediction {tuple(y_pred.shape)} {y_pred.dtype} and target {tuple(y_true.shape)} "
-                         f"{y_true.dtype} differ")
-    if y_true.requires_grad:
-        raise ValueError("mel_mss_loss: the target takes no gradient here (detach it, or use optimize.mel_mss_loss's torch lines)")
-    norm = _melmss_norm(p)
+    _check_signals("mel_mss_loss", y_pred, y_true, "optimize.mel_mss_loss")
+    norm = _norm_code(p)
     if norm is None:
         raise ValueError(f"mel_mss_loss: p must be 'fro', 2 or 1, got {p!r}")
     if not (isinstance(sample_rate, (int, float)) and math.isfinite(sample_rate) and sample_rate // 2 > 0):
         raise ValueError(f"mel_mss_loss: sample_rate must be a number with sample_rate // 2 > 0, got {sample_rate!r}")
-    frames = _melmss_frames(nfft, overlap)
+    frames = _resolution_frames(nfft, overlap)
     if frames is None or not mel_mss_supported(tuple(y_pred.shape), nfft, overlap, sample_rate, p):
         raise ValueError(f"mel_mss_loss: resolutions nfft = {nfft!r}, overlap = {overlap!r} on T = {y_pred.shape[1]}: 1 to "
                          f"{MELMSS_MAX_RES} n_fft, each a power of two from 128 to 4096 with hop = int(n_fft (1 - overlap)) >= 1, "
                          f"n_fft / 2 < T <= 2^30, fewer than 2^31 frames in all, and mel bases with every bin in at most two "
                          f"consecutive bands")
-    try:
-        alpha, threshold = float(alpha), float(threshold)
-        ne = 1.0 if not apply_mask else float(noise_energy)
-    except (TypeError, ValueError):
-        ne = float("nan")
-    if not ne > 0.0:
-        raise ValueError(f"mel_mss_loss: apply_mask needs a noise_energy > 0 (a number: the class derives it from the target "
-                         f"when it is None), got {noise_energy!r}")
+    alpha, threshold, ne = _mask_options("mel_mss_loss", alpha, threshold, apply_mask, noise_energy, finite=False)
     opts = (norm, int(bool(log_term)), alpha, int(bool(apply_mask)), threshold, ne)
     return _MelMSS.apply(y_pred, y_true, frames, sample_rate, opts)
 
@@ -3620,10 +3635,6 @@ def mss_basis(sample_rate, nfft, device=None):
     return torch.cos(ang), torch.sin(ang)
 
 
-def _mss_frames(nfft, overlap):
-    return _melmss_frames(nfft, overlap)
-
-
 def _mss_host(sample_rate, n):
     """the tables of one resolution as include/flamo_hip_mss.h lays them out, a float64 vector, cached per (sample_rate,
     n_fft): the periodic Hann window, then as (re, im) pairs fseed[k, m] = exp(-i theta_k 64 m), fstep[k, c] = exp(-i theta_k
@@ -3651,10 +3662,6 @@ def _mss_host(sample_rate, n):
     return ent
 
 
-def _mss_norm(p):
-    return _melmss_norm(p)
-
-
 def _mss_form(form):
     try:
         return MSS_FORMS.get(form)
@@ -3667,29 +3674,22 @@ def mss_supported(shape, nfft=MSS_NFFTS, overlap=0.75, sample_rate=48000, p="fro
     4096 (no power of two is asked for), hop = int(n_fft (1 - overlap)) >= 1, n_fft / 2 < T <= 2^30, fewer than 2^31 frames,
     2^24 workgroups per launch and 2^32 samples in all, an integral sample rate >= 80, ``p`` in "fro", 2, 1 and ``form`` None, "yamamoto" or
     "magenta" """
-    frames = _mss_frames(nfft, overlap)
-    try:
-        dims = tuple(int(s) for s in shape)
-        same = all(a == b for a, b in zip(dims, tuple(shape)))
-    except (TypeError, ValueError):
+    frames, dims = _resolution_frames(nfft, overlap), _int_dims(shape)
+    if frames is None or dims is None or not 1 <= len(frames) <= MSS_MAX_RES:
         return False
-    if frames is None or not same or len(dims) != 3 or max(map(abs, dims)) >= 1 << 62 or not 1 <= len(frames) <= MSS_MAX_RES:
+    if _norm_code(p) is None or _mss_form(form) is None or _mss_rate(sample_rate) is None:
         return False
-    if _mss_norm(p) is None or _mss_form(form) is None or _mss_rate(sample_rate) is None:
-        return False
-    flat = [v for pair in frames for v in pair]
     # the library's own support query: one statement of the sizes
-    return _lib.lib().fl_mss_frames(*dims, len(frames), (ctypes.c_int * len(flat))(*flat)) >= 0
+    return _lib.lib().fl_mss_frames(*dims, len(frames), _c_ints(v for pair in frames for v in pair)) >= 0
 
 
 def _mss_consts(frames, sample_rate, dev: torch.device):
     """(the tables of the resolutions one behind the other on the device, the resolutions as a host int array of (n_fft,
     hop)), cached per (resolutions, sample_rate, device); made on the host in float64 under either precision of the signals"""
-    key = (frames, sample_rate, dev.index if dev.index is not None else torch.cuda.current_device())
+    key = (frames, sample_rate, _dev_index(dev))
     ent = _mss_tables.get(key)
     if ent is None:
-        flat = [v for pair in frames for v in pair]
-        cres = (ctypes.c_int * len(flat))(*flat)
+        cres = _c_ints(v for pair in frames for v in pair)
         tab = torch.cat([_mss_host(sample_rate, n) for n, _ in frames])
         assert tab.numel() == _lib.lib().fl_mss_table_doubles(len(frames), cres)
         ent = _mss_tables[key] = (tab.to(dev), cres)
@@ -3732,9 +3732,7 @@ class _MSS(torch.autograd.Function):
         tab, cres = _mss_consts(frames, sample_rate, dev)
         R = len(frames)
         norm, form, log_term, _, apply_mask, threshold, ne = opts
-        gframes = torch.empty(L.fl_mss_gframe_elems(B, T, N, R, cres), dtype=dtype, device=dev)
-        gy = torch.empty((B, T, N), dtype=dtype, device=dev)
-        g = _gloss_as(gloss, dtype)
+        gframes, gy, g = _grad_buffers(L.fl_mss_gframe_elems(B, T, N, R, cres), (B, T, N), gloss, dtype, dev)
         with kernel_timer.span("mss_bwd"):
             _lib.check(_fn("fl_mss_bwd", dtype)(B, T, N, R, cres, tab.data_ptr(), norm, form, log_term, apply_mask, threshold, ne,
                                                 keep.data_ptr(), g.data_ptr(), gframes.data_ptr(), gy.data_ptr(), _stream()),
@@ -3757,33 +3755,20 @@ def mss_loss(y_pred: torch.Tensor, y_true: torch.Tensor, nfft=MSS_NFFTS, overlap
     are read through their strides, nothing is copied, nothing is read back.  The target takes no gradient.  Sizes:
     ``mss_supported``."""
     _require_gpu(y_pred, y_true)
-    if y_pred.dim() != 3 or y_pred.dtype not in (torch.float32, torch.float64) or y_pred.numel() == 0:
-        raise ValueError(f"mss_loss: a non-empty real float32 / float64 (B, T, N) signal, got {tuple(y_pred.shape)} {y_pred.dtype}")
-    if tuple(y_true.shape) != tuple(y_pred.shape) or y_true.dtype != y_pred.dtype:
-        raise ValueError(f"mss_loss: prediction {tuple(y_pred.shape)} {y_pred.dtype} and target {tuple(y_true.shape)} "
-                         f"{y_true.dtype} differ")
-    if y_true.requires_grad:
-        raise ValueError("mss_loss: the target takes no gradient here (detach it, or use optimize.loss.mss_loss's torch lines)")
-    norm, kform = _mss_norm(p), _mss_form(form)
+    _check_signals("mss_loss", y_pred, y_true, "optimize.loss.mss_loss")
+    norm, kform = _norm_code(p), _mss_form(form)
     if norm is None:
         raise ValueError(f"mss_loss: p must be 'fro', 2 or 1, got {p!r}")
     if kform is None:
         raise ValueError(f"mss_loss: form must be None, 'yamamoto' or 'magenta', got {form!r}")
     if _mss_rate(sample_rate) is None:
         raise ValueError(f"mss_loss: sample_rate must be an integral number >= 80, got {sample_rate!r}")
-    frames = _mss_frames(nfft, overlap)
+    frames = _resolution_frames(nfft, overlap)
     if frames is None or not mss_supported(tuple(y_pred.shape), nfft, overlap, sample_rate, p, form):
         raise ValueError(f"mss_loss: resolutions nfft = {nfft!r}, overlap = {overlap!r} on T = {y_pred.shape[1]}: 1 to "
                          f"{MSS_MAX_RES} n_fft, each a multiple of 4 from 16 to 4096 with hop = int(n_fft (1 - overlap)) >= 1, "
                          f"n_fft / 2 < T <= 2^30 and fewer than 2^31 frames in all")
-    try:
-        alpha, threshold = float(alpha), float(threshold)
-        ne = 1.0 if not apply_mask else float(noise_energy)
-    except (TypeError, ValueError):
-        ne = float("nan")
-    if not (ne > 0.0 and math.isfinite(ne)):
-        raise ValueError(f"mss_loss: apply_mask needs a finite noise_energy > 0 (a number: the class derives it from the target "
-                         f"when it is None), got {noise_energy!r}")
+    alpha, threshold, ne = _mask_options("mss_loss", alpha, threshold, apply_mask, noise_energy, finite=True)
     opts = (norm, kform, int(bool(log_term)), alpha, int(bool(apply_mask)), threshold, ne)
     return _MSS.apply(y_pred, y_true, frames, _mss_rate(sample_rate), opts)
 

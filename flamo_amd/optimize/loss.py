@@ -19,6 +19,13 @@ from .. import ops
 from .utils import generate_partitions
 
 
+def _device_pair(y_pred, y_true):
+    """whether (prediction, target) are what the framed criteria's kernels read: device tensors of one real precision, the
+    target without a gradient (the sizes are the ops' ``*_supported`` queries)"""
+    return (torch.is_tensor(y_pred) and torch.is_tensor(y_true) and y_pred.is_cuda and y_true.is_cuda
+            and y_pred.dtype in (torch.float32, torch.float64) and y_true.dtype == y_pred.dtype and not y_true.requires_grad)
+
+
 class mse_loss(nn.Module):
     """Wrapper for the mean squared error loss: nn.MSELoss()(y_pred.sum(-1), y_true.squeeze(-1)), as
     flamo/optimize/loss.py:101-102.  Same constructor and attributes (nfft, device, mse_loss, name)."""
@@ -276,9 +283,7 @@ class MultiResoSTFT(nn.Module):
         return tuple(zip(self.fft_sizes, self.hop_sizes, self.win_lengths))
 
     def _on_kernels(self, y_pred, y_true):
-        return (torch.is_tensor(y_pred) and torch.is_tensor(y_true) and y_pred.is_cuda and y_true.is_cuda
-                and y_pred.dtype in (torch.float32, torch.float64) and y_true.dtype == y_pred.dtype
-                and not y_true.requires_grad
+        return (_device_pair(y_pred, y_true)
                 and ops.mrstft_supported(tuple(y_pred.shape), self.resolutions(), self.eps))
 
     def forward(self, y_pred, y_true):
@@ -369,9 +374,7 @@ class edr_loss(nn.Module):
         return torch.matmul(W, X.real ** 2 + X.imag ** 2)
 
     def _on_kernels(self, y_pred, y_true):
-        return (torch.is_tensor(y_pred) and torch.is_tensor(y_true) and y_pred.is_cuda and y_true.is_cuda
-                and y_pred.dtype in (torch.float32, torch.float64) and y_true.dtype == y_pred.dtype
-                and not y_true.requires_grad and self.sample_rate // 2 > ops.EDR_FMIN
+        return (_device_pair(y_pred, y_true) and self.sample_rate // 2 > ops.EDR_FMIN
                 and ops.edr_supported(tuple(y_pred.shape), self.nfft, self.hop_length(), self.win_length))
 
     def forward(self, y_pred, y_true):
@@ -472,9 +475,7 @@ class mel_mss_loss(nn.Module):
         return y.permute(0, 2, 1).reshape(B * N, T)
 
     def _on_kernels(self, y_pred, y_true):
-        return (torch.is_tensor(y_pred) and torch.is_tensor(y_true) and y_pred.is_cuda and y_true.is_cuda
-                and y_pred.dtype in (torch.float32, torch.float64) and y_true.dtype == y_pred.dtype
-                and not y_true.requires_grad
+        return (_device_pair(y_pred, y_true)
                 and ops.mel_mss_supported(tuple(y_pred.shape), self.nfft, self.overlap, self.sample_rate, self.p))
 
     def forward(self, y_pred, y_true):
@@ -613,9 +614,7 @@ class mss_loss(nn.Module):
         return y.permute(0, 2, 1).reshape(B * N, T)
 
     def _on_kernels(self, y_pred, y_true):
-        return (torch.is_tensor(y_pred) and torch.is_tensor(y_true) and y_pred.is_cuda and y_true.is_cuda
-                and y_pred.dtype in (torch.float32, torch.float64) and y_true.dtype == y_pred.dtype
-                and not y_true.requires_grad
+        return (_device_pair(y_pred, y_true)
                 and ops.mss_supported(tuple(y_pred.shape), self.nfft, self.overlap, self.sample_rate, self.p, self.form))
 
     def forward(self, y_pred, y_true):
