@@ -9,6 +9,7 @@
 //
 // One wavefront per matrix, the matrix (H), the accumulated unitary (Q) and the eigenvector scratch
 // in LDS.  Classical dense path, every loop with wavefront-uniform control flow:
+//   0. the matrix scaled by a power of two to a largest component in [0.5, 1) (exact; undone on the eigenvalues);
 //   1. Householder reduction to upper Hessenberg form, Q accumulated;
 //   2. explicitly shifted QR sweeps (Wilkinson shift, exceptional shifts at iterations 10 and 20,
 //      deflation on |h(k,k-1)| <= eps (|h(k-1,k-1)| + |h(k,k)|)) with Givens rotations applied to the
@@ -36,9 +37,30 @@ template <typename T> __device__ inline cx<T> csqrt_(cx<T> a) {
     }
     return cx<T>(re, im);
 }
+// the largest v of the 64 lanes, in every lane (NaN lanes are passed over)
+template <typename T> __device__ inline T wave_max(T v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+    return v;
+}
+// v: machine epsilon;  tiny: a squared column tail at or below it counts as zero (the matrix is scaled to a largest
+// component in [0.5, 1) first);  small: smallest normal number / v -- a squared modulus below it is not trusted
 template <typename T> struct Eps;
-template <> struct Eps<float> { static constexpr float v = 1.1920929e-07f; static constexpr float tiny = 1e-30f; };
-template <> struct Eps<double> { static constexpr double v = 2.220446049250313e-16; static constexpr double tiny = 1e-290; };
+template <> struct Eps<float> { static constexpr float v = 1.1920929e-07f; static constexpr float tiny = 1e-30f; static constexpr float small = 9.8607613e-32f; };
+template <> struct Eps<double> { static constexpr double v = 2.220446049250313e-16; static constexpr double tiny = 1e-290; static constexpr double small = 1.0020841800044864e-292; };
+// |a| and ph = a/|a| of an entry whose squared modulus may underflow, through the power of two of its larger component;
+// a = 0: 0 and (1, 0)
+template <typename T> __device__ inline T cmod_small(cx<T> a, cx<T>& ph) {
+    const T m = fmax(fabs(a.x), fabs(a.y));
+    ph = cx<T>(1, 0);
+    if (!(m > 0)) return m;
+    int e = 0;
+    frexp(m, &e);
+    const cx<T> s(ldexp(a.x, -e), ldexp(a.y, -e));
+    const T ms = sqrt(cabs2(s));
+    ph = cx<T>(s.x / ms, s.y / ms);
+    return ldexp(ms, e);
+}
 
 template <typename T>
 __global__ void __launch_bounds__(64) eig_kernel(const cx<T>* __restrict__ A, long a_pitch, int N, int M,
@@ -56,23 +78,51 @@ __global__ void __launch_bounds__(64) eig_kernel(const cx<T>* __restrict__ A, lo
     if (f >= M) return;
     const T eps = Eps<T>::v;
 
+    T amax = 0;
+    int bad = 0;
     for (int idx = lane; idx < N * N; idx += 64) {
         const int i = idx / N, j = idx - i * N;
-        H[i * NP + j] = A[(size_t)idx * a_pitch + f];
+        const cx<T> a = A[(size_t)idx * a_pitch + f];
+        H[i * NP + j] = a;
         Q[i * NP + j] = cx<T>(i == j ? (T)1 : (T)0, 0);
+        amax = fmax(amax, fmax(fabs(a.x), fabs(a.y)));
+        bad |= !(isfinite(a.x) && isfinite(a.y));
     }
+    // Scale by the power of two that brings the largest |Re|, |Im| into [0.5, 1) -- exact, and what keeps the squared
+    // magnitudes and the absolute thresholds below in range for any input; the eigenvalues are scaled back where they are
+    // stored, eigenvectors are scale-free.  An all-zero or non-finite matrix keeps scale 1; a non-finite entry is reported
+    // in info whatever the iteration makes of it.  amax, bad and se are wavefront-uniform.
+    amax = wave_max(amax);
+    bad = __any(bad);
+    int se = 0;
+    if (amax > 0 && isfinite(amax)) frexp(amax, &se);
+    __syncthreads();
+    if (se != 0)
+        for (int idx = lane; idx < N * N; idx += 64) {
+            const int i = idx / N, j = idx - i * N;
+            const cx<T> a = H[i * NP + j];
+            H[i * NP + j] = cx<T>(ldexp(a.x, -se), ldexp(a.y, -se));
+        }
     __syncthreads();
 
     // ---- 1. Hessenberg reduction: H <- P_k H P_k, Q <- Q P_k, P_k = I - beta v v^H
     for (int k = 0; k + 2 < N; ++k) {
         const bool in = lane > k && lane < N;
         const cx<T> xi = in ? H[lane * NP + k] : cx<T>(0, 0);
-        const T nrm2 = wave_sum(cabs2(xi));
+        // the part below the subdiagonal summed on its own: nrm2 - |x0|^2 cancels to zero once it is below sqrt(eps) |x0|,
+        // and the column would pass as reduced with entries of that size left in it
+        const T tail2 = wave_sum(lane > k + 1 ? cabs2(xi) : (T)0);
         const cx<T> x0 = H[(k + 1) * NP + k];
-        const T tail2 = nrm2 - cabs2(x0);
+        const T nrm2 = tail2 + cabs2(x0);
         if (!(tail2 > Eps<T>::tiny)) continue;           // column already in Hessenberg form (uniform)
-        const T nrm = sqrt(nrm2), a0 = cabsv(x0);
-        const cx<T> ph = (a0 > 0) ? cx<T>(x0.x / a0, x0.y / a0) : cx<T>(1, 0);
+        const T nrm = sqrt(nrm2);
+        cx<T> ph;                                        // x0/|x0|, (1, 0) for x0 = 0
+        if (cabs2(x0) >= Eps<T>::small) {
+            const T a0 = cabsv(x0);
+            ph = cx<T>(x0.x / a0, x0.y / a0);
+        } else {
+            cmod_small(x0, ph);
+        }
         const cx<T> alpha(-ph.x * nrm, -ph.y * nrm);     // x -> alpha e1
         const cx<T> v0 = x0 - alpha;
         const T beta = (T)2 / (tail2 + cabs2(v0));
@@ -136,7 +186,9 @@ __global__ void __launch_bounds__(64) eig_kernel(const cx<T>* __restrict__ A, lo
         const cx<T> a = H[(hi - 1) * NP + hi - 1], b = H[(hi - 1) * NP + hi], c = H[hi * NP + hi - 1], d = H[hi * NP + hi];
         cx<T> mu;
         if (iter == 10 || iter == 20) {
-            const T e = fabs(H[hi * NP + hi - 1].x) + ((hi >= 2) ? fabs(H[(hi - 1) * NP + hi - 2].x) : (T)0);
+            // |re| + |im|, not LAPACK's |re|: zlahqr makes the subdiagonal real first, here it is complex, and on a
+            // purely imaginary one (i x a cyclic shift) the real parts give the zero shift that stalled the iteration
+            const T e = cabs1(H[hi * NP + hi - 1]) + ((hi >= 2) ? cabs1(H[(hi - 1) * NP + hi - 2]) : (T)0);
             mu = cx<T>(d.x + e, d.y);
         } else {
             const cx<T> hd = (T)0.5 * (a - d);
@@ -150,19 +202,30 @@ __global__ void __launch_bounds__(64) eig_kernel(const cx<T>* __restrict__ A, lo
         // R = G_{hi-1} ... G_lo (H - mu I): rotation k acts on rows k, k+1, columns k .. N-1 (lane = column)
         for (int k = lo; k < hi; ++k) {
             const cx<T> x = H[k * NP + k], y = H[(k + 1) * NP + k];
-            const T ax = cabsv(x), r = sqrt(cabs2(x) + cabs2(y));
+            const T x2 = cabs2(x), y2 = cabs2(y);
+            T ax, r;
+            cx<T> px;                                            // x/|x|, (1, 0) for x = 0
+            if (x2 >= Eps<T>::small && y2 >= Eps<T>::small) {    // (uniform: every lane reads the same x, y)
+                ax = sqrt(x2);
+                r = sqrt(x2 + y2);
+                px = cx<T>(x.x / ax, x.y / ax);
+            } else {
+                // a squared modulus in the denormal range has lost its digits (or is zero): x/|x| then has no unit
+                // modulus and the "rotation" scales its rows -- a unitary matrix with a zero diagonal under a zero
+                // shift has x ~ 1e-22 beside y ~ 1.  Moduli through the entries' own powers of two instead.
+                ax = cmod_small(x, px);
+                cx<T> py;
+                const T ay = cmod_small(y, py), s = fmax(ax, ay);
+                const T u = ax / s, v = ay / s;
+                r = (s > 0) ? s * sqrt(u * u + v * v) : (T)0;
+            }
             T cs;
             cx<T> sn;
             if (!(r > 0)) {
                 cs = 1;
                 sn = cx<T>(0, 0);
-            } else if (!(ax > 0)) {
-                cs = 0;
-                const T ay = cabsv(y);
-                sn = cx<T>(y.x / ay, -y.y / ay);                 // conj(y)/|y|
             } else {
-                cs = ax / r;
-                const cx<T> px(x.x / ax, x.y / ax);              // x/|x|
+                cs = ax / r;                                     // x = 0: cs = 0, sn = conj(y)/|y|
                 sn = px * cx<T>(y.x / r, -y.y / r);              // (x/|x|) conj(y) / r
             }
             __syncthreads();
@@ -197,8 +260,12 @@ __global__ void __launch_bounds__(64) eig_kernel(const cx<T>* __restrict__ A, lo
         if (lane >= lo && lane <= hi) H[lane * NP + lane] = H[lane * NP + lane] + mu;
         __syncthreads();
     }
+    if (bad && !fail) fail = N;
     if (lane == 0 && info) info[f] = fail;
-    if (lane < N) lam[(size_t)lane * l_pitch + f] = H[lane * NP + lane];
+    if (lane < N) {
+        const cx<T> l = H[lane * NP + lane];
+        lam[(size_t)lane * l_pitch + f] = cx<T>(ldexp(l.x, se), ldexp(l.y, se));
+    }
     if (!V) return;
 
     // ---- 3. eigenvectors of T by back substitution (lane i: vector i), then V = Q Y
@@ -243,12 +310,14 @@ static int eig_impl(const void* A, long a_pitch, int N, int M, void* lam, long l
                     void* stream) {
     FL_REQUIRE(A && lam, "eig: null pointer");
     FL_REQUIRE(N >= 1 && N <= 64 && M >= 0 && a_pitch >= M && l_pitch >= M && (!V || v_pitch >= M), "eig: bad sizes (1 <= N <= 64, pitches >= M)");
-    if (M == 0) return FL_OK;
+    // the size is refused before the empty batch is accepted: with M = 0 the entry answers, on the host and without a
+    // launch, whether this N fits with / without eigenvectors (the tests take the largest differentiable N from it)
     const size_t lds = ((size_t)(V ? 3 : 2) * N * (N + 1) + N) * sizeof(cx<T>) + (size_t)N * sizeof(T);
     if (lds > 160 * 1024) {
         set_error("eig: N=%d does not fit in LDS at this precision", N);
         return FL_ERR_UNSUPPORTED;
     }
+    if (M == 0) return FL_OK;
     if (lds > 64 * 1024) {
         int rc = check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(&eig_kernel<T>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "eig LDS size");

@@ -24,7 +24,9 @@ def get_magnitude(x: torch.Tensor) -> torch.Tensor:
 def get_eigenvalues(x: torch.Tensor) -> torch.Tensor:
     """Eigenvalues over the last two (equal) dimensions (flamo/functional.py:24-39).  On the GPU: one
     wavefront per matrix (ops.eigvals, N <= 64); the order of the eigenvalues of a matrix is the order
-    on the diagonal of its Schur form, which is not torch.linalg.eigvals' order."""
+    on the diagonal of its Schur form, which is not torch.linalg.eigvals' order.  A matrix whose QR iteration
+    does not converge (or that holds a non-finite entry) raises nothing: ops.eigvals_info() is non-zero for
+    that bin and its values are whatever the iteration left."""
     assert x.shape[-1] == x.shape[-2]
     if x.shape[-1] == 1:
         return x

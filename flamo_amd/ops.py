@@ -3882,8 +3882,11 @@ _eig_state = {"info": None}
 
 def eigvals_info() -> Optional[torch.Tensor]:
     """int32 (bins,) convergence flags of the most recent ops.eigvals call (0 = converged; k > 0: the QR
-    iteration gave up with k eigenvalues of that matrix unconverged).  A device tensor: reading it
-    synchronises, which is why eigvals itself does not."""
+    iteration gave up with k eigenvalues of that matrix unconverged after its 60 N sweeps, or the matrix
+    held a non-finite entry: k = N then).  Where the flag of a bin is non-zero, the eigenvalues returned for
+    that bin are whatever the iteration left on the diagonal -- not eigenvalues, and not marked as such: a
+    caller that cannot rule the case out reads this flag.  A device tensor: reading it synchronises, which is
+    why eigvals itself does not."""
     return _eig_state["info"]
 
 
@@ -3926,6 +3929,9 @@ class _Eigvals(torch.autograd.Function):
 
 def eigvals(A: torch.Tensor) -> torch.Tensor:
     """Eigenvalues of the (..., N, N) complex matrices, N <= 64, one wavefront per matrix (Hessenberg + shifted
-    QR in LDS).  Order: position on the diagonal of the Schur form, not LAPACK's -- use order-independent
-    functions of the result.  Differentiable (g_A = V^-H diag(g) V^H) for simple eigenvalues."""
+    QR in LDS, on the matrix scaled by a power of two: any finite input, whatever its magnitude).  Order:
+    position on the diagonal of the Schur form, not LAPACK's -- use order-independent functions of the result.
+    Differentiable (g_A = V^-H diag(g) V^H) for simple eigenvalues; an input that requires grad keeps the
+    eigenvectors in LDS as well, which fits up to N = 64 in complex64 and N = 57 in complex128 (a larger one
+    raises).  Convergence is reported by eigvals_info(), never by the values."""
     return _Eigvals.apply(A)

@@ -780,9 +780,12 @@ int fl_matrix_exp_bwd_both_f64(const void* gE, const void* gEc, int N, int skew,
  *        NOT LAPACK's order; compare as sets)
  *   V:   NULL, or planar (N, N, v_pitch) right eigenvectors as columns, unit 2-norm (needed by the
  *        backward: g_A = V^-H diag(g_lambda) V^H, one fl_solve per bin)
- *   info: NULL, or int[M]: 0, or k > 0 if the QR iteration gave up with k eigenvalues unconverged.
- * One wavefront per matrix (Householder Hessenberg reduction, explicitly shifted QR with Wilkinson
- * shifts to Schur form, back substitution for the vectors), matrices in LDS. */
+ *   info: NULL, or int[M]: 0, or k > 0 if the QR iteration gave up with k eigenvalues unconverged (N for a matrix
+ *        with a non-finite entry); lam of such a bin is whatever the iteration left.
+ * One wavefront per matrix (scaling by a power of two, Householder Hessenberg reduction, explicitly shifted QR with
+ * Wilkinson shifts to Schur form, back substitution for the vectors), matrices in LDS: 160 KB hold N <= 64 without V
+ * at both precisions, with V N <= 64 (c64) / 57 (c128); a larger N is FL_ERR_UNSUPPORTED, for an empty batch too
+ * (a call with M = 0 answers on the host whether a size fits). */
 int fl_eig_c64(const void* A, long a_pitch, int N, int M, void* lam, long l_pitch, void* V, long v_pitch, void* info,
                void* stream);
 int fl_eig_c128(const void* A, long a_pitch, int N, int M, void* lam, long l_pitch, void* V, long v_pitch, void* info,

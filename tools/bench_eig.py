@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Per-bin eigenvalues: ops.eigvals on (F, N, N) complex matrices, forward and
 forward + backward of an |eig| loss, against torch.linalg.eigvals on the same device.
-    python tools/bench_eig.py [--n 32] [--bins 12000]"""
+    python tools/bench_eig.py [--n 32] [--bins 12000] [--skip-torch]
+--skip-torch leaves the torch.linalg.eigvals line out: four calls of about a minute each at the default size."""
 import argparse
 import json
 import os
@@ -29,6 +30,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=32)
     ap.add_argument("--bins", type=int, default=12000)
+    ap.add_argument("--skip-torch", action="store_true")
     args = ap.parse_args()
     from flamo_amd import ops
     dev = torch.device("cuda:0")
@@ -51,10 +53,11 @@ def main():
                 return torch.linalg.eigvals(A)
 
         r = {"fwd_ms": timeit(fwd), "fwd_bwd_ms": timeit(fwd_bwd)}
-        try:
-            r["torch_eigvals_fwd_ms"] = timeit(ref, n=2)
-        except Exception as e:   # noqa: BLE001
-            r["torch_eigvals_fwd_ms"] = f"failed: {type(e).__name__}"
+        if not args.skip_torch:
+            try:
+                r["torch_eigvals_fwd_ms"] = timeit(ref, n=2)
+            except Exception as e:   # noqa: BLE001
+                r["torch_eigvals_fwd_ms"] = f"failed: {type(e).__name__}"
         r["matrices_per_s_fwd"] = args.bins / (r["fwd_ms"] * 1e-3)
         out[name] = r
     print(json.dumps(out))
