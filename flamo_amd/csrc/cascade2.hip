@@ -59,15 +59,14 @@ struct LanesArgs {
     long g_pitch;
     const cx<T>* G;        // saved response, planes c
     long h_pitch;
-    const T* Wr;           // (PPR, NIW) constant factor (rc mode)
+    const T* Wr;           // (N_mid, NIW) constant factor (rc mode)
     T* psum;               // (S * C, nbx, 4) partial sums (G0 of B, G0 of A, G2 of B, G2 of A)
     T* pq;                 // (C, nbx) partial sums of Re(q)
-    T* partW;              // (PPR * NIW, nbx * pair groups) partial sums of the constant factor's gradient (rc mode)
-    // "outer" mode: dL/dG[m][n] = sum_b gY[b][m] conj(X[b][n]) formed from the two signals
-    const cx<T>* oG;
-    const cx<T>* oX;
-    long o_gb, o_gn, o_xb, o_xn;
-    int oB;
+    T* partW;              // (N_mid * NIW, nbx * pair groups) partial sums of the constant factor's gradient (rc mode)
+    // 52 bytes where a retired mode's operands lay.  The kernel sits at the 106-SGPR ceiling and keeps scalars in VGPR lanes:
+    // with the fields behind this one moved up, the compiler groups the argument loads differently and allocates and spills
+    // differently through the whole kernel -- a change of the hot loop's code, to be made with a measurement, not in passing
+    int retired[13];
     // geometry (lanes_plan)
     int npb, rows, seff, s_first, tb, tbp, ntiles, tph, half, L1, nlow, tiles_low, nbx;
     int lds1;              // bytes of ONE set of tile buffers (the kernel takes two)
@@ -80,8 +79,8 @@ struct LanesArgs {
 // (a transcendental occupies the SIMD for four passes: ONE reciprocal of |B~|^2 |A~|^2 serves both polynomials).
 // x = (1 -+ cos, sin); qa = (q.x, q.y), qb = (sin q.y, -sin q.x) as the lane-per-bin work left them: every scalar factor is a
 // half of an aligned register pair, i.e. an operand selector
-template <int NSUM, typename P2, typename T>
-__device__ __forceinline__ void lane_bin(P2 C0, P2 C1, P2 C2, P2 x, T uu, P2 qa, P2 qb, P2& t0, P2& t1, P2& t2) {
+template <typename P2, typename T>
+__device__ __forceinline__ void lane_bin(P2 C0, P2 C1, P2 C2, P2 x, P2 qa, P2 qb, P2& t0, P2& t2) {
     const P2 R = C1 * x.x + C0;
     const P2 I = C2 * x.y;
     P2 n = R * R;
@@ -94,16 +93,10 @@ __device__ __forceinline__ void lane_bin(P2 C0, P2 C1, P2 C2, P2 x, T uu, P2 qa,
     t0 = uI * qa.y + t0;
     t2 = uR * qb.x + t2;                                 // sin Im(q / P~)
     t2 = uI * qb.y + t2;
-    if constexpr (NSUM == 3) {
-        const P2 uq = qa * uu;
-        t1 = uR * uq.x + t1;                             // (1 - cos) Re(q / P~)
-        t1 = uI * uq.y + t1;
-    }
 }
 
-// NIW > 0: constant-factor mode (rows of PPR pairs share NIW cotangent planes); NIW == 0, !OUTER: plain (PPR = 1);
-// OUTER: rows of PPR pairs (m, n), cotangent formed from gY and X.
-template <typename RT, int NIW, int PPR, int NSUM, bool OUTER>
+// NIW > 0: constant-factor mode (rows of PPR = NIW pairs share NIW cotangent planes); NIW == 0: plain (PPR = 1)
+template <typename RT, int NIW>
 __global__ void __launch_bounds__(sizeof(RT) == 8 ? 384 : 768, sizeof(RT) == 8 ? 2 : 3) sos_bwd_lanes_kernel(const LanesArgs<RT> A) {
     typedef typename Vec<RT>::v2 P2;
     typedef typename Vec<RT>::v4 P4;
@@ -112,18 +105,18 @@ __global__ void __launch_bounds__(sizeof(RT) == 8 ? 384 : 768, sizeof(RT) == 8 ?
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int bx = blockIdx.x, cg = blockIdx.y;
     const int npb = A.npb, tbp = A.tbp, S = A.S, C = A.C;
+    constexpr bool RC = NIW > 0;
+    constexpr int PPR = NIW ? NIW : 1;      // pairs per row
     // two sets of tile buffers: the lane-per-bin work of tile t + 1 writes one while the lane-per-section work of tile t reads the other
     struct Bufs {
         P4* qs;             // [npb][tbp]  (q, sin * (-i q)), q = conj(gG) G; zero where nothing is due
         P2* xs;             // [tbp]       (1 -+ cos, sin)
-        RT* us;          // [tbp]       1 - cos      (NSUM == 3)
     };
     auto bufs_at = [&](int which) {
         Bufs B;
         char* p = smem + (size_t)which * A.lds1;
         B.qs = reinterpret_cast<P4*>(p);
         B.xs = reinterpret_cast<P2*>(B.qs + (size_t)npb * tbp);
-        B.us = reinterpret_cast<RT*>(B.xs + tbp);
         return B;
     };
 
@@ -146,7 +139,7 @@ __global__ void __launch_bounds__(sizeof(RT) == 8 ? 384 : 768, sizeof(RT) == 8 ?
     }
     const bool wave_on = wave * 64 < nl;
 
-    P2 acc0 = {(RT)0.0, (RT)0.0}, acc1 = {(RT)0.0, (RT)0.0}, acc2 = {(RT)0.0, (RT)0.0};
+    P2 acc0 = {(RT)0.0, (RT)0.0}, acc2 = {(RT)0.0, (RT)0.0};
     // ---- tiles: elements f0 .. f0 + n - 1, one expansion point, bin of element f0 + i = kbase + i * kstep
     struct Tile {
         int f0, n, kbase, kstep;
@@ -180,12 +173,11 @@ __global__ void __launch_bounds__(sizeof(RT) == 8 ? 384 : 768, sizeof(RT) == 8 ?
     // ---- the lane-per-bin work: item (element i of the tile, row r, group jg of JPT pairs of the row), operands requested one
     // tile ahead (they arrive under the lane-per-section work in between).  Plane bases are wavefront-uniform, the lane's part
     // is ONE 32-bit byte offset per tensor (saddr + voffset loads: a 64-bit address per plane would be 32 more registers)
-    constexpr bool RC = NIW > 0 && !OUTER;
     // pairs of the row per item (double: one -- two pairs' worth of constant-factor sums and cotangent rows in doubles do not fit the registers)
-    constexpr int JPT = RC ? ((NIW >= 16 || sizeof(RT) == 8) ? 1 : (PPR >= 2 ? 2 : PPR)) : (OUTER ? PPR : 1);
-    constexpr int JG = (RC || OUTER) ? PPR / JPT : 1;
-    constexpr int NG = OUTER ? 2 : (NIW > 0 ? NIW : 1);        // cotangent values per item
-    constexpr int TRIPS = (RC || OUTER) ? 1 : 4;               // items per thread and tile (plain mode: one per pair)
+    constexpr int JPT = RC ? ((NIW >= 16 || sizeof(RT) == 8) ? 1 : (PPR >= 2 ? 2 : PPR)) : 1;
+    constexpr int JG = RC ? PPR / JPT : 1;
+    constexpr int NG = NIW > 0 ? NIW : 1;                      // cotangent values per item
+    constexpr int TRIPS = RC ? 1 : 4;                          // items per thread and tile (plain mode: one per pair)
     struct Item {
         cT gv[NG];
         cT hv[JPT];
@@ -234,14 +226,7 @@ __global__ void __launch_bounds__(sizeof(RT) == 8 ? 384 : 768, sizeof(RT) == 8 ?
             const int f = T.f0 + ii, k = T.kbase + ii * T.kstep;
             pre[q].w1 = A.Wd[k];                                     // (k <= nfft / 2)
             const int row = cg * A.rows + r;                         // global row
-            if constexpr (OUTER) {
-#pragma unroll
-                for (int bb = 0; bb < 2; ++bb)
-                    pre[q].gv[bb] = bb < A.oB ? A.oG[(size_t)bb * A.o_gb + (size_t)row * A.o_gn + f] : cT((RT)0.0, (RT)0.0);
-                const unsigned hoff = (unsigned)(((size_t)(row * PPR) * A.h_pitch + f) * sizeof(cT));
-#pragma unroll
-                for (int j = 0; j < JPT; ++j) pre[q].hv[j] = at(A.G + (size_t)j * A.h_pitch, hoff);
-            } else if constexpr (RC) {
+            if constexpr (RC) {
                 const unsigned goff = (unsigned)(((size_t)(row * NIW) * A.g_pitch + f) * sizeof(cT));
                 const unsigned hoff = (unsigned)(((size_t)(row * PPR + it_j[q]) * A.h_pitch + f) * sizeof(cT));
                 if (A.pol & POL_LANES_GH_NT) {
@@ -279,10 +264,7 @@ __global__ void __launch_bounds__(sizeof(RT) == 8 ? 384 : 768, sizeof(RT) == 8 ?
             const bool valid = i < n;
             const Item& P = pre[q];
             const RT sn = (RT)(-P.w1.y);      // sin(omega)
-            if (r == 0 && j0 == 0) {
-                B.xs[i] = P2{(RT)(T.low ? 1.0 - P.w1.x : 1.0 + P.w1.x), sn};
-                if constexpr (NSUM == 3) B.us[i] = (RT)(1.0 - P.w1.x);
-            }
+            if (r == 0 && j0 == 0) B.xs[i] = P2{(RT)(T.low ? 1.0 - P.w1.x : 1.0 + P.w1.x), sn};
             if constexpr (RC) {
 #pragma unroll
                 for (int j = 0; j < JPT; ++j) {
@@ -297,20 +279,6 @@ __global__ void __launch_bounds__(sizeof(RT) == 8 ? 384 : 768, sizeof(RT) == 8 ?
                     qsum[q][j] += qz.x;
 #pragma unroll
                     for (int nn = 0; nn < NIW; ++nn) aw[j][nn] = P2{h.x, h.y} * P2{P.gv[nn].x, P.gv[nn].y} + aw[j][nn];
-                }
-            } else if constexpr (OUTER) {
-                // row = output channel m, the PPR pairs of the row are its input channels n: dL/dG[m][n] = sum_b gY[b][m] conj(X[b][n])
-                const int f = T.f0 + (valid ? i : n - 1);
-#pragma unroll 4
-                for (int j = 0; j < PPR; ++j) {
-                    cT gi((RT)0.0, (RT)0.0);
-                    for (int bb = 0; bb < A.oB && bb < 2; ++bb) fma_cxc(gi, P.gv[bb], A.oX[(size_t)bb * A.o_xb + (size_t)j * A.o_xn + f]);
-                    const cT h = P.hv[j];
-                    const bool live = valid && !(h.x == eps_of<RT>() && h.y == (RT)0.0);
-                    const cT qv(gi.x * h.x + gi.y * h.y, gi.x * h.y - gi.y * h.x);
-                    const cT qz = live ? qv : cT((RT)0.0, (RT)0.0);
-                    B.qs[(size_t)(r * PPR + j) * tbp + i] = P4{qz.x, qz.y, sn * qz.y, -(sn * qz.x)};
-                    qsum[q][j] += qz.x;
                 }
             } else {
                 const cT gi = P.gv[0], h = P.hv[0];
@@ -356,7 +324,7 @@ __global__ void __launch_bounds__(sizeof(RT) == 8 ? 384 : 768, sizeof(RT) == 8 ?
         auto section_work = [&]() {
             if (!(wave_on && !(A.skip & 2))) return;
             const P2 C0 = low ? C0lo : C0hi, C1 = low ? C1lo : -C1lo;
-            P2 t0 = {(RT)0.0, (RT)0.0}, t1 = {(RT)0.0, (RT)0.0}, t2 = {(RT)0.0, (RT)0.0};
+            P2 t0 = {(RT)0.0, (RT)0.0}, t2 = {(RT)0.0, (RT)0.0};
             const P4* qrow = B.qs + (size_t)pl * tbp;
 #pragma unroll 2
             for (int i = 0; i < np; i += 2) {
@@ -368,21 +336,14 @@ __global__ void __launch_bounds__(sizeof(RT) == 8 ? 384 : 768, sizeof(RT) == 8 ?
                     x4 = P4{xa.x, xa.y, xb.x, xb.y};
                 }
                 const P4 qA = qrow[i], qB = qrow[i + 1];
-                RT u0 = (RT)0.0, u1 = (RT)0.0;
-                if constexpr (NSUM == 3) {
-                    const P2 u2 = *reinterpret_cast<const P2*>(B.us + i);
-                    u0 = u2.x;
-                    u1 = u2.y;
-                }
-                lane_bin<NSUM, P2, RT>(C0, C1, C2, P2{x4.x, x4.y}, u0, P2{qA.x, qA.y}, P2{qA.z, qA.w}, t0, t1, t2);
-                lane_bin<NSUM, P2, RT>(C0, C1, C2, P2{x4.z, x4.w}, u1, P2{qB.x, qB.y}, P2{qB.z, qB.w}, t0, t1, t2);
+                lane_bin<P2, RT>(C0, C1, C2, P2{x4.x, x4.y}, P2{qA.x, qA.y}, P2{qA.z, qA.w}, t0, t2);
+                lane_bin<P2, RT>(C0, C1, C2, P2{x4.z, x4.w}, P2{qB.x, qB.y}, P2{qB.z, qB.w}, t0, t2);
             }
             // (no range test: an equaliser section has no zero on the sampling circle for finite positive gains -- B(1) = sqrt(g) (2 - 2 cos wc),
             // B(-1) = sqrt(g) (2 + 2 cos wc), the imaginary part g t sin(omega) -- and for a gain of exactly 0 the reference's own
             // gradient is not finite either (d sqrt(g) / dg); a vanishing norm shows as a non-finite gradient, as there)
             acc0 += t0;
             acc2 += t2;
-            if constexpr (NSUM == 3) acc1 += t1;
         };
         const bool sections_first = !(A.skip & 4) && ((wave >> 2) & 1);
         if (sections_first) section_work();
@@ -414,9 +375,7 @@ __global__ void __launch_bounds__(sizeof(RT) == 8 ? 384 : 768, sizeof(RT) == 8 ?
 
     // ---- partial sums of this block: [section * C + pair][block][4 sums] -- one 16-byte store per lane, and the reduction
     // reads an entry's partials as one run
-    (void)acc1;
     if (l_on) {
-        static_assert(NSUM == 2, "the partials are one 16-byte record per (entry, block)");
         reinterpret_cast<P4*>(A.psum)[((size_t)sl * C + c) * A.nbx + bx] = P4{acc0.x, acc0.y, acc2.x, acc2.y};
     }
     {   // sum Re(q) per pair: the items' sums through LDS (the tile buffers are done with), one thread per pair adds its tb items
@@ -590,12 +549,11 @@ __global__ void __launch_bounds__(256) sos_response_rc_ba_kernel(RcBaArgs A) {
 
 static void pin_kernel_order() {      // the code object's kernel order, kept as it has always been (see response.hip)
     (void)&sos_response_rc_ba_kernel<2>, (void)&sos_response_rc_ba_kernel<4>, (void)&sos_response_rc_ba_kernel<8>,
-        (void)&sos_response_rc_ba_kernel<16>, (void)&sos_bwd_lanes_kernel<float, 0, 1, 2, false>,
-        (void)&sos_bwd_lanes_kernel<float, 8, 8, 2, false>, (void)&sos_bwd_lanes_kernel<float, 4, 4, 2, false>,
-        (void)&sos_bwd_lanes_kernel<float, 2, 2, 2, false>, (void)&sos_bwd_lanes_kernel<float, 16, 16, 2, false>,
-        (void)&sos_bwd_lanes_kernel<double, 0, 1, 2, false>, (void)&sos_bwd_lanes_kernel<double, 8, 8, 2, false>,
-        (void)&sos_bwd_lanes_kernel<double, 4, 4, 2, false>, (void)&sos_bwd_lanes_kernel<double, 2, 2, 2, false>,
-        (void)&sos_bwd_lanes_kernel<double, 16, 16, 2, false>, (void)&geq_bwd_lanes_kernel<float>, (void)&geq_bwd_lanes_kernel<double>;
+        (void)&sos_response_rc_ba_kernel<16>, (void)&sos_bwd_lanes_kernel<float, 0>,
+        (void)&sos_bwd_lanes_kernel<float, 8>, (void)&sos_bwd_lanes_kernel<float, 4>, (void)&sos_bwd_lanes_kernel<float, 2>,
+        (void)&sos_bwd_lanes_kernel<float, 16>, (void)&sos_bwd_lanes_kernel<double, 0>, (void)&sos_bwd_lanes_kernel<double, 8>,
+        (void)&sos_bwd_lanes_kernel<double, 4>, (void)&sos_bwd_lanes_kernel<double, 2>, (void)&sos_bwd_lanes_kernel<double, 16>,
+        (void)&geq_bwd_lanes_kernel<float>, (void)&geq_bwd_lanes_kernel<double>;
 }
 
 // host side of the kernel above (called by response.hip: rc_impl); returns FL_ERR_UNSUPPORTED (no error text) when the shape is
@@ -651,16 +609,14 @@ static int lanes_ensure_lds(const void* kern, size_t lds, bool* done /* [kMaxDev
     return lds <= 64 * 1024 ? FL_OK : ensure_dynamic_lds(kern, lds, true, done, "lanes cascade backward");
 }
 
-// mode: 0 plain (ppr = 1), 1 constant factor (ppr = N_mid, niw columns), 2 outer (ppr = N_in)
+// mode: 0 plain (ppr = 1), 1 constant factor (ppr = N_mid, niw columns)
 // esz: bytes of the kernels' real type (4: float, 8: double -- half the lanes per workgroup, twice the LDS per value)
 static LanesPlan lanes_plan(int m_local, int C, int S, int nfft, int bin0, int ppr, int niw, int mode, int esz = 4) {
     LanesPlan P{};
-    static const int env_maxt = [] { const char* e = getenv("FLAMO_LANES_MAXT"); return e ? atoi(e) : 0; }();      // tuning: lanes per workgroup
-    const int max_threads = esz == 8 ? 384 : (env_maxt >= 64 && env_maxt <= 768 ? env_maxt : 768), sc = esz / 4;
-    if (!g_lanes || S < 4 || S > 64 || C < 1 || m_local < 1 || ppr < 1 || C % ppr) return P;
+    const int max_threads = esz == 8 ? 384 : 768, sc = esz / 4;
+    if ((mode != 0 && mode != 1) || !g_lanes || S < 4 || S > 64 || C < 1 || m_local < 1 || ppr < 1 || C % ppr) return P;
     if (mode == 1 && !((niw == 8 && ppr == 8) || (niw == 4 && ppr == 4) || (niw == 2 && ppr == 2) || (niw == 16 && ppr == 16))) return P;
-    if (mode == 2 && !(ppr == 8 || ppr == 16 || ppr == 32)) return P;
-    if (esz == 8 && (mode == 2 || (mode == 1 && niw >= 16))) return P;      // (double: sixteen cotangent rows per item spill)
+    if (esz == 8 && mode == 1 && niw >= 16) return P;      // (double: sixteen cotangent rows per item spill)
     if (bin0 < 0 && ((-bin0) % 2 || (nfft / 2) % (-bin0) || m_local != nfft / 2 + 1)) return P;
     P.seff = S - 1;
     P.s_first = 1;
@@ -725,6 +681,8 @@ static LanesPlan lanes_plan(int m_local, int C, int S, int nfft, int bin0, int p
     P.nbx = P.ntiles < nbx_target ? P.ntiles : nbx_target;
     const int npad = (P.tb + 1) & ~1;
     P.tbp = npad + 1;      // pitch = 16 bytes x odd: the lanes' rows fall on different banks
+    // qs, xs, and the (tbp + 3 & ~3) * 4 bytes of a retired third buffer (1 - cos, for a third running sum): nothing reads
+    // them, but the LDS request decides how the workgroups share a CU, so it stays what the kernel was measured with
     P.lds1 = ((size_t)P.npb * P.tbp * 16 + (size_t)(P.tbp + 1) * 8 + (size_t)((P.tbp + 3) & ~3) * 4) * sc;
     P.lds1 = (P.lds1 + 31) & ~(size_t)31;
     {
@@ -807,7 +765,7 @@ FL_ENTRY_C64_C128(fl_geq_response_bwd_lanes, (int mode, const void* gH, long g_p
     dispatch<0, 8, 4, 2, 16>(mode == 0 ? 0 : Ni, [&](auto NIW) {      // (mode 1: the plan took one of these four)
         constexpr int niw = decltype(NIW)::value;
         static bool done[kMaxDevices] = {};
-        auto kern = sos_bwd_lanes_kernel<T, niw, niw ? niw : 1, 2, false>;
+        auto kern = sos_bwd_lanes_kernel<T, niw>;
         rc = lanes_ensure_lds(reinterpret_cast<const void*>(kern), lds, done);
         if (rc == FL_OK) hipLaunchKernelGGL(kern, grid, block, lds, (hipStream_t)stream, A);
     });

@@ -116,7 +116,7 @@ __global__ void __launch_bounds__(256) sos_response_rc_kernel(const double* __re
 // gains (eq.py:57-111, the arithmetic of geq_sections_kernel) instead of being read -- every workgroup needs the 12 sections
 // of its N_mid cascades, one per thread -- and the first bin block of each output channel writes them out for the backward
 // pass: the design launch in front of this one (5 us and a dispatch gap in the config-2 step) is gone.
-template <int NIW, int UNR = 1>
+template <int NIW>
 __global__ void __launch_bounds__(256) sos_response_rc_fast_kernel(const double* __restrict__ b, const double* __restrict__ a, int S,
                                                                   int C, int Nmid, const float* __restrict__ Wr, double g,
                                                                   const cx<double>* __restrict__ Wd, int nfft, int bin0,
@@ -186,7 +186,8 @@ __global__ void __launch_bounds__(256) sos_response_rc_fast_kernel(const double*
             e[1] = two ? e[0] + L2 : e[0];
         }
     }
-    constexpr int UNR_REST = UNR > 1 ? UNR - 1 : 1;      // pairs per trip behind the first one (which starts the products)
+    constexpr int kPairsPerTrip = 6;                     // section pairs per loop trip
+    constexpr int kPairsRest = kPairsPerTrip - 1;        // ... behind the first one (which starts the products)
     bool low[2];
     float xr[2], xi[2];
 #pragma unroll
@@ -226,8 +227,8 @@ __global__ void __launch_bounds__(256) sos_response_rc_fast_kernel(const double*
                     par[q] = a0 + a1 * xr[q]; pai[q] = a2 * xi[q];
                 }
             }
-            // (UNR section pairs per trip with the first: their table reads are issued together -- one LDS latency per trip, not per pair)
-#pragma unroll UNR_REST
+            // (their table reads are issued together -- one LDS latency per trip, not per pair)
+#pragma unroll kPairsRest
             for (int s = 2; s < SP; s += 2) {
                 const f2 b0 = *reinterpret_cast<const f2*>(cb + s), b1 = *reinterpret_cast<const f2*>(cb + SP + s),
                          b2 = *reinterpret_cast<const f2*>(cb + 2 * SP + s);
@@ -1041,27 +1042,22 @@ static void pin_kernel_order() {
         (void)&sos_response_bwd_mixed_kernel<8, 2>, (void)&sos_response_bwd_mixed_kernel<8, 4>, (void)&sos_response_bwd_mixed_kernel<8, 8>,
         (void)&sos_response_bwd_mixed_kernel<8, 16>, (void)&sos_response_bwd_mixed_kernel<12, 0>, (void)&sos_response_bwd_mixed_kernel<12, 2>,
         (void)&sos_response_bwd_mixed_kernel<12, 4>, (void)&sos_response_bwd_mixed_kernel<12, 8>, (void)&sos_response_bwd_mixed_kernel<12, 16>,
-        (void)&sos_response_bwd_kernel<float, 12>, (void)&sos_response_bwd_kernel<float, 6>, (void)&sos_response_bwd_kernel<float, 3>,
-        (void)&sos_response_bwd_kernel<float, 4>, (void)&sos_response_rc_fast_kernel<2, 2>, (void)&sos_response_rc_fast_kernel<2, 3>,
-        (void)&sos_response_rc_fast_kernel<2, 6>, (void)&sos_response_rc_fast_kernel<2, 1>, (void)&sos_response_rc_kernel<2, float>,
-        (void)&sos_response_rc_fast_kernel<4, 2>, (void)&sos_response_rc_fast_kernel<4, 3>, (void)&sos_response_rc_fast_kernel<4, 6>,
-        (void)&sos_response_rc_fast_kernel<4, 1>, (void)&sos_response_rc_kernel<4, float>, (void)&sos_response_rc_fast_kernel<8, 2>,
-        (void)&sos_response_rc_fast_kernel<8, 3>, (void)&sos_response_rc_fast_kernel<8, 6>, (void)&sos_response_rc_fast_kernel<8, 1>,
-        (void)&sos_response_rc_kernel<8, float>, (void)&sos_response_rc_fast_kernel<16, 2>, (void)&sos_response_rc_fast_kernel<16, 3>,
-        (void)&sos_response_rc_fast_kernel<16, 6>, (void)&sos_response_rc_fast_kernel<16, 1>, (void)&sos_response_rc_kernel<16, float>,
+        (void)&sos_response_bwd_kernel<float, 6>, (void)&sos_response_bwd_kernel<float, 4>, (void)&sos_response_rc_fast_kernel<2>,
+        (void)&sos_response_rc_kernel<2, float>, (void)&sos_response_rc_fast_kernel<4>, (void)&sos_response_rc_kernel<4, float>,
+        (void)&sos_response_rc_fast_kernel<8>, (void)&sos_response_rc_kernel<8, float>, (void)&sos_response_rc_fast_kernel<16>,
+        (void)&sos_response_rc_kernel<16, float>,
         (void)&sos_response_rc_kernel<2, double>, (void)&sos_response_rc_kernel<4, double>, (void)&sos_response_rc_kernel<8, double>,
         (void)&sos_response_rc_kernel<16, double>, (void)&sos_response_apply_fast_kernel<1>, (void)&sos_response_apply_fast_kernel<2>,
         (void)&sos_response_bwd_kernel<double, 6, 2>, (void)&sos_response_bwd_kernel<double, 6, 4>, (void)&sos_response_bwd_kernel<double, 6, 8>,
-        (void)&sos_response_bwd_kernel<double, 6, 16>, (void)&sos_response_bwd_kernel<double, 12>, (void)&sos_response_bwd_kernel<double, 6>,
-        (void)&sos_response_bwd_kernel<double, 3>, (void)&sos_response_bwd_kernel<double, 4>;
+        (void)&sos_response_bwd_kernel<double, 6, 16>, (void)&sos_response_bwd_kernel<double, 6>, (void)&sos_response_bwd_kernel<double, 4>;
 }
 
 // ================================================================ host side
 // Launch helpers (namespace fl) over the kernels above, then the exported entries in one section at the end of the file.  Where a
-// run-time integer selects a template instantiation -- section chunk, columns of the constant factor, section pairs per trip,
-// signal columns -- it goes through fl::dispatch (common.h).
+// run-time integer selects a template instantiation -- section chunk, columns of the constant factor, signal columns -- it goes
+// through fl::dispatch (common.h).
 static int g_sos_chunk = 0;
-static int g_rc_fast = 6;   // cascade-times-matrix forward: float evaluation in the 1 -+ w basis, section pairs per loop trip (1 | 2 | 3 | 6; 0: the double kernel)
+static int g_rc_fast = 1;   // cascade forward: float evaluation in the 1 -+ w basis where the caller allows it (0: the double kernels)
 static int g_sos_blocks = 0;
 
 // Bin blocks per channel pair of the backward kernels: the whole grid (blocks x C channel pairs x section chunks) is ONE
@@ -1074,8 +1070,7 @@ static int sos_chunk_of(int S, bool mixed) {
         const int want = g_sos_chunk > 0 ? g_sos_chunk : 12;
         return (S <= 4 || want <= 4) ? 4 : (S <= 6 || want <= 6) ? 6 : (S <= 8 || want <= 8) ? 8 : 12;
     }
-    const int sch = (g_sos_chunk == 3 || g_sos_chunk == 4 || g_sos_chunk == 6 || g_sos_chunk == 12) ? g_sos_chunk : 6;
-    return S > 4 ? sch : 4;
+    return (S <= 4 || g_sos_chunk == 4) ? 4 : 6;
 }
 
 static int sos_blocks(int m_local, int C, int S, bool mixed) {
@@ -1143,14 +1138,10 @@ static int rc_impl(const void* b, const void* a, int S, int No, int Nmid, int Ni
             if (rc2 != FL_ERR_UNSUPPORTED) return rc2;      // (shapes the second generation does not take fall through)
             const size_t lds_fast = ((size_t)Nmid * 12 * ((S + 1) & ~1) + (size_t)Nmid * Ni) * sizeof(float);
             const dim3 grid_fast(cdiv_i(rc_npairs(nfft, bin0, m_local), 256), No);
-            const int unr = (g_rc_fast == 2 || g_rc_fast == 3 || g_rc_fast == 6) ? g_rc_fast : 1;
             if (dispatch<2, 4, 8, 16>(Ni, [&](auto NIW) {
-                    dispatch<2, 3, 6, 1>(unr, [&](auto UNR) {
-                        hipLaunchKernelGGL((sos_response_rc_fast_kernel<decltype(NIW)::value, decltype(UNR)::value>), grid_fast, dim3(256),
-                                           lds_fast, (hipStream_t)stream, (const double*)b, (const double*)a, S, No * Nmid, Nmid,
-                                           (const float*)Wr, gamma, (const cx<double>*)Wd, nfft, bin0, m_local, (cx<float>*)G, g_pitch,
-                                           (cx<float>*)H, h_pitch, gd);
-                    });
+                    hipLaunchKernelGGL((sos_response_rc_fast_kernel<decltype(NIW)::value>), grid_fast, dim3(256), lds_fast,
+                                       (hipStream_t)stream, (const double*)b, (const double*)a, S, No * Nmid, Nmid, (const float*)Wr, gamma,
+                                       (const cx<double>*)Wd, nfft, bin0, m_local, (cx<float>*)G, g_pitch, (cx<float>*)H, h_pitch, gd);
                 })) {
                 FL_CHECK_LAUNCH("sos_response_rc_fast");
                 return FL_OK;
@@ -1252,7 +1243,7 @@ static int sos_bwd_rc_f64_launch(const SosBwd& A, SosRCd rcd, int rc_ni) {
 // plain, either type: the cascade evaluated in double (again, or from the saved response)
 template <typename T>
 static int sos_bwd_plain_launch(const SosBwd& A) {
-    dispatch<12, 6, 3, 4>(sos_chunk_of(A.S, false), [&](auto SC) {
+    dispatch<6, 4>(sos_chunk_of(A.S, false), [&](auto SC) {
         const dim3 grid(sos_blocks(A.m_local, A.C, A.S, false), A.C, cdiv_i(A.S, decltype(SC)::value));
         hipLaunchKernelGGL((sos_response_bwd_kernel<T, decltype(SC)::value>), grid, dim3(256), (size_t)6 * A.S * sizeof(double), (hipStream_t)A.stream,
                            (const cx<T>*)A.gH, A.g_pitch, (const cx<T>*)A.H, A.h_pitch, (const double*)A.b, (const double*)A.a, A.S, A.C, A.gamma,
@@ -1310,17 +1301,23 @@ extern "C" int fl_geq_response_c64(const void* gain, int in_kind, int nb, const 
     return sos_impl<float>(b, a, nb, C, gamma, Wd, nfft, bin0, m_local, H, h_pitch, stream, float_eval != 0, gd);
 }
 extern "C" int fl_sos_bwd_blocks(int m_local, int C, int S, int mixed) { return sos_blocks(m_local, C, S, mixed != 0); }
-// (test hooks: both return the previous setting; a negative argument only asks for it)
+// (test hooks: both return the previous setting; a negative argument only asks for it, any other unknown code is FL_ERR_BAD_ARG
+// and changes nothing)
 extern "C" int fl_debug_set_sos_chunk(int sections_per_thread) {
     const int prev = g_sos_blocks * 100 + g_sos_chunk;
     if (sections_per_thread < 0) return prev;
+    const int chunk = sections_per_thread % 100;      // 0 = default; the mixed kernel takes all four, the plain ones 4 (else 6)
+    FL_REQUIRE(chunk == 0 || chunk == 4 || chunk == 6 || chunk == 8 || chunk == 12,
+               "debug_set_sos_chunk: %d sections per thread is not 0, 4, 6, 8 or 12", chunk);
     g_sos_blocks = sections_per_thread / 100;      // hundreds digit(s): blocks per channel (0 = default)
-    g_sos_chunk = sections_per_thread % 100;
+    g_sos_chunk = chunk;
     return prev;
 }
 extern "C" int fl_debug_set_rc_fast(int on) {
     const int prev = g_rc_fast;
-    if (on >= 0) g_rc_fast = on;
+    if (on < 0) return prev;
+    FL_REQUIRE(on <= 1, "debug_set_rc_fast: %d is not 0 (double evaluation) or 1 (float)", on);
+    g_rc_fast = on;
     return prev;
 }
 FL_ENTRY_C64_C128(fl_sos_response_bwd, (const void* gH, long g_pitch, const void* H, long h_pitch, const void* b, const void* a, int S,

@@ -399,11 +399,14 @@ int fl_geq_response_c64(const void* gain, int in_kind, int nb, const void* const
  * {1, d, d^2}, d = 1 - g w, converted back in double); H == NULL, and _c128 always, evaluates
  * everything in double. */
 int fl_sos_bwd_blocks(int m_local, int C, int S, int mixed);
-/* tuning hook: sections whose sums one thread keeps in registers (0 = default); + 100 * blocks per channel.  Returns the
- * previous setting in the same encoding; a negative argument changes nothing. */
+/* tuning hook: sections whose sums one thread keeps in registers, 0 (default), 4, 6, 8 or 12: the mixed-precision kernels take
+ * each of them (default 12), the all-double ones 4 and otherwise their default 6 (4 where S <= 4); + 100 * blocks per channel
+ * (0 = default).  Returns the previous setting in the same encoding; a negative argument changes nothing.  Any other value is
+ * FL_ERR_BAD_ARG and changes nothing. */
 int fl_debug_set_sos_chunk(int sections_per_thread);
-/* test hook: 0 = the float evaluations (fl_sos_response_f32eval_c64, fl_sos_response_rc_c64 with float_eval) fall back to double.
- * Returns the previous setting; a negative argument changes nothing. */
+/* test hook: 1 (default) = the float evaluations (fl_sos_response_f32eval_c64, fl_sos_response_rc_c64 with float_eval) run in
+ * float, 0 = they fall back to double.  Returns the previous setting; a negative argument changes nothing.  Any other value is
+ * FL_ERR_BAD_ARG and changes nothing. */
 int fl_debug_set_rc_fast(int on);
 int fl_sos_response_bwd_c64(const void* gH, long g_pitch, const void* H, long h_pitch, const void* b, const void* a, int S,
                             int C, double gamma, const void* Wd, int nfft, int bin0, int m_local, void* part, void* stream);

@@ -161,6 +161,40 @@ def test_mimo_variant_hook_accepts_only_the_remaining_codes():
     assert L.fl_mimo_gradw_blocks(256 * 100) == 100
 
 
+def test_cascade_hooks_accept_only_the_remaining_codes():
+    """fl_debug_set_rc_fast: 0 / 1 (the section pairs per trip 2, 3 and 6 of the removed forward kernels are errors);
+    fl_debug_set_sos_chunk: 0 / 4 / 6 / 8 / 12 sections per thread plus 100 x blocks per channel (3, of the removed backward
+    kernels, and unknown counts are errors).  An error carries a message and leaves the setting as it was; -1 reads it."""
+    from flamo_amd import _lib
+    L = _lib.lib()
+    fast0, chunk0 = L.fl_debug_set_rc_fast(-1), L.fl_debug_set_sos_chunk(-1)
+    assert (fast0, chunk0) == (1, 0)                                     # the shipped defaults
+    try:
+        prev = fast0
+        for ok in (0, 1):
+            assert L.fl_debug_set_rc_fast(ok) == prev, ok                # the previous setting
+            assert L.fl_debug_set_rc_fast(-1) == ok, ok
+            prev = ok
+        assert L.fl_debug_set_rc_fast(0) == 1
+        for bad in (2, 3, 6):
+            assert L.fl_debug_set_rc_fast(bad) == -1, bad
+            assert f"{bad} is not".encode() in L.fl_last_error(), bad    # this call's own message, not an earlier one
+            assert L.fl_debug_set_rc_fast(-1) == 0, bad                  # a refused call changes no state
+        prev = chunk0
+        for ok in (0, 4, 6, 8, 12, 304, 1206):
+            assert L.fl_debug_set_sos_chunk(ok) == prev, ok
+            assert L.fl_debug_set_sos_chunk(-1) == ok, ok
+            prev = ok
+        for bad in (3, 5, 1203):
+            assert L.fl_debug_set_sos_chunk(bad) == -1, bad
+            assert f"{bad % 100} sections".encode() in L.fl_last_error(), bad
+            assert L.fl_debug_set_sos_chunk(-1) == 1206, bad
+    finally:
+        L.fl_debug_set_rc_fast(fast0)
+        L.fl_debug_set_sos_chunk(chunk0)
+    assert (L.fl_debug_set_rc_fast(-1), L.fl_debug_set_sos_chunk(-1)) == (fast0, chunk0)
+
+
 def test_spec_hook_accepts_only_the_remaining_codes():
     """fl_debug_set_spec: tile width 0 / 16 / 32, load group 0 / 1 / 2 / 4, plus 1000 for the fake-response switch; the codes of
     the removed row-kernel variants (batch groups, three-sweep product, response-row prefetch) and an unknown tile width are

@@ -482,11 +482,11 @@ def test_cascade_times_matrix_float_evaluation(gpu, db):
     spec = geq._cascade_spec(geq.param)
     Hs = []
     for fast in (1, 0):
-        _lib.lib().fl_debug_set_rc_fast(fast)
+        prev = _lib.lib().fl_debug_set_rc_fast(fast)
         try:
             Hs.append(ops.geq_cascade_rc(spec[1], spec[2], W, geq._gamma_f, nfft))
         finally:
-            _lib.lib().fl_debug_set_rc_fast(1)
+            _lib.lib().fl_debug_set_rc_fast(prev)
     cc("Hs_0", Hs[0], Hs[1], 1e-6, max_tol=float("inf"))
     gamma = O.gamma_of(db, nfft, torch.float64)
     Href = O.geq_response(geq.param.detach().cpu().double(), nfft, gamma) @ W.cpu().double().to(torch.complex128)
@@ -518,7 +518,7 @@ def test_cascade_float_evaluation_plain_response(gpu, kind):
         mod = dsp.Biquad(size=(N, N), n_sections=2, filter_type=kind.split("_")[1], **kw)
     out, names = {}, {}
     for fast in (1, 0):
-        _lib.lib().fl_debug_set_rc_fast(fast)
+        prev = _lib.lib().fl_debug_set_rc_fast(fast)
         try:
             with torch.no_grad():
                 ops.kernel_timer.reset(True)
@@ -531,7 +531,7 @@ def test_cascade_float_evaluation_plain_response(gpu, kind):
             (H * c.conj()).real.sum().backward()
             out[fast] = (Hn.clone(), H.detach().clone(), mod.param.grad.clone())
         finally:
-            _lib.lib().fl_debug_set_rc_fast(1)
+            _lib.lib().fl_debug_set_rc_fast(prev)
     scale = out[0][0].abs().max()
     assert ((out[1][0] - out[0][0]).abs().max() / scale).item() < 2e-6       # forward-only: float against double
     cc("out_1_0", out[1][0], out[0][0], 1e-6, max_tol=float("inf"))

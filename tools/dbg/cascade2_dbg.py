@@ -56,7 +56,7 @@ for on in (3, 1):
     res[on] = (Hq.clone(), Gq[..., :m_local].clone(), timed(lambda: fwd()))
 L.fl_debug_set_rc_fast(0)
 Hd, Gd, _ = fwd()
-L.fl_debug_set_rc_fast(6)
+L.fl_debug_set_rc_fast(1)
 rel = lambda x, y: ((x - y).norm() / y.norm()).item()
 print(f"forward: first generation {res[3][2]:.1f} us, second {res[1][2]:.1f} us (eager call: host time included); second vs first: H {rel(res[1][0], res[3][0]):.2e} G {rel(res[1][1], res[3][1]):.2e};"
       f" vs the double evaluation: second H {rel(res[1][0], Hd):.2e} G {rel(res[1][1], Gd[..., :m_local]):.2e}, first H {rel(res[3][0], Hd):.2e} G {rel(res[3][1], Gd[..., :m_local]):.2e}")
